@@ -10,8 +10,14 @@ N > 1: frames shard across ranks (one process per GPU, launched by torch.distrib
 collective — one RCCL all_gather of a small metrics record at the end.  value = frames processed by
 all ranks / max-over-ranks wall time.
 
-Also in the JSON line: `roofline` for the dominant kernel (live HIP-event timing of every sv_conv_fwd launch in the
-timed region) and, at N = 1, `cpu_baseline` = the C oracle (oracle/sv_oracle.c, OpenMP) timed on the host cores.
+A plain run sets up, warms up, times exactly --steps steps once and prints the line.  --full adds everything else: the
+timed region repeated (median on the line), `roofline` for the dominant kernel (live HIP-event timing of every sv_conv_fwd
+launch in the timed region), `kernels_warmup`, the accuracy check against the C oracle, at N = 1 `cpu_baseline` = the C
+oracle (oracle/sv_oracle.c, OpenMP) timed on the host cores, and the secondary blocks (batched, one frame per launch,
+HBM-bound layers, engine, strong scaling, other configurations).
+
+--dump-outputs DIR: after the timed steps, the per-point results of the last step's frame (labels, confidence) go to
+DIR/<name>.npy as float32; inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -118,21 +124,26 @@ def make_frame(seed, device, n=POINTS, L=ROOM, batch=1):
             parts[0][2])
 
 
-def run_frames(model, pipe, frames, steps, hist=None, group=1):
+def run_frames(model, pipe, frames, steps, hist=None, group=1, last=None):
     """Process `steps` frames through the multi-stream pipeline (mrcc_amd/app/pipeline.py): while the U-Net of frame i
     runs on the compute stream, the host builds frame i+1's coordinate maps / plans on the prep stream.  Every frame
     is voxelised and mapped from scratch; all work of all `steps` frames is enqueued (and, by the caller's
     synchronize, finished) inside the caller's timed region.  group > 1: consecutive frames go through the network
     `group` at a time as one sparse tensor (FramePipeline.prepare_group: the concatenation is part of the timed work);
-    the last group of a region holds the remainder."""
+    the last group of a region holds the remainder.  last: a dict that receives the last step's per-point `label` /
+    `conf` (device tensors, valid once the caller has synchronised)."""
     voxels = 0
     cls = torch.arange(3, device=frames[0][1].device).unsqueeze(1)
+    keep = False
 
     def unet(x, field):
         if profiling.TIMER is not None:
             profiling.TIMER.frame_boundary()
         out = model(x)
         label, conf = out.slice_argmax(field)
+        if keep:  # the last step's frame is the group's last member: points are in frame order
+            n = frames[(steps - 1) % len(frames)][0].shape[0]
+            last.update(label=label[-n:], conf=conf[-n:])
         if hist is not None:  # asynchronous label histogram on the frame's own stream
             return (label.unsqueeze(0) == cls).sum(dim=1)
         return label
@@ -145,6 +156,7 @@ def run_frames(model, pipe, frames, steps, hist=None, group=1):
     nxt = pipe.prepare_group(members(0)) if starts else None
     for gi, i in enumerate(starts):
         cur = nxt
+        keep = last is not None and gi + 1 == len(starts)
         res = pipe.run(cur, unet)
         if hist is not None:
             partial.append(res)
@@ -435,6 +447,15 @@ def hbm_bound_layers(model, device, iters=60):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array the timed path handed back in its last step"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+    _log(f"outputs of the last step: {', '.join(sorted(arrays))} -> {path}")
+
+
 def launcher_selftest(args, world, rank):
     """What the N-rank launch does around the GPU work, on the CPU: pin the rank, init (gloo), rank r takes frames
     r, r + world, ... (weak: --steps frames per rank; strong: --total-frames in all), R repeats of a fake timed region,
@@ -506,6 +527,7 @@ def strong_scaling_block(model, device, rank, world, total_frames, streams, thre
     hist = np.zeros(3, dtype=np.int64)
     t0 = time.perf_counter()
     n = 0
+    labels = None
     for labels in stream.run(source(seeds)):
         hist += np.bincount(labels, minlength=3)[:3]
         n += 1
@@ -513,7 +535,7 @@ def strong_scaling_block(model, device, rank, world, total_frames, streams, thre
     elapsed = time.perf_counter() - t0
     barrier()
     hs = stream.host_s
-    return {"frames": n, "elapsed": elapsed, "hist": hist, "seed_sum": int(sum(seeds)),
+    return {"frames": n, "elapsed": elapsed, "hist": hist, "seed_sum": int(sum(seeds)), "last_labels": labels,
             "host_ms_per_frame": {k: round(v / max(hs["frames"], 1) * 1e3, 3) for k, v in hs.items() if k != "frames"}}
 
 
@@ -809,10 +831,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline: repeated timed regions, roofline and per-kernel "
+                         "figures, accuracy against the C oracle, CPU baselines and the secondary blocks (a plain run "
+                         "times the --steps steps once and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the per-point results of the last step's frame (labels, "
+                         "confidence) as float32 DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is run this many times; "
-                         "ms_per_step is the median, min / max are on the line.  Small --steps get more repeats "
-                         "(ceil(64 / steps)) so that the timed regions total about a second or more")
+                         "ms_per_step is the median, min / max are on the line.  Default: 1; with --full 5, and small "
+                         "--steps get more repeats (ceil(64 / steps)) so that the timed regions total about a second or more")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pool", type=int, default=4, help="distinct frames resident per rank")
     ap.add_argument("--no-kernel-timer", action="store_true", help="diagnostic: drop the per-launch HIP events")
@@ -836,8 +865,8 @@ def main():
                     help="frames of the secondary strong-scaling block of a default (weak) run; 0 = skip")
     ap.add_argument("--source-threads", type=int, default=0, help="host threads producing frames in the strong mode (0 = auto)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline measurement only: no batched / other-config / engine / strong blocks, no HBM-bound-layer "
-                         "block (PMC passes)")
+                    help="with --full: no batched / other-config / engine / strong blocks, no HBM-bound-layer block "
+                         "(PMC passes)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU rehearsal of the N-rank launch: pinning, rendezvous (gloo), frame sharding (weak or strong), "
                          "the one all_gather and the JSON line, without touching a GPU (tests/test_dist_cpu.py)")
@@ -846,6 +875,8 @@ def main():
     args = ap.parse_args()
     if args.gather_gemm_child:
         return gather_gemm_child(args.gather_gemm_child)
+    if args.repeats is None:
+        args.repeats = 5 if args.full or args.launcher_selftest else 1
     import faulthandler
 
     faulthandler.dump_traceback_later(300, repeat=True, file=sys.stderr)  # a stuck run says where it is stuck
@@ -890,7 +921,7 @@ def main():
     #      (every N) and, at N = 1, the timed CPU baseline.  With N > 1 it is capped to the quarter frame (~2.5 s) so that
     #      the other ranks wait at the first barrier for seconds, not for the 17 s of the full N = 1 pass.
     base = base_mm = checked = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         base, base_mm, checked = oracle_pass(model, budget_s=25.0 if world == 1 else 0.0, world=world)
     # rank r owns frames r, r + world, ... of the global seed sequence (Cfg-4 sharding rule)
     frames = [make_frame(rank + world * i, device, batch=args.frames_per_step) for i in range(args.pool)]
@@ -906,6 +937,8 @@ def main():
         with torch.no_grad():
             rec = strong_scaling_block(model, device, rank, world, args.total_frames, args.streams, src_threads, barrier,
                                        group=group)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"labels": rec["last_labels"]})
         agg = gather_metrics({"frames": rec["frames"], "elapsed": rec["elapsed"], "confusion": np.diag(rec["hist"]),
                               "seed_sum": rec["seed_sum"],
                               "per_rank": dict({f"host_{k}_ms": v for k, v in rec["host_ms_per_frame"].items()},
@@ -937,65 +970,77 @@ def main():
             dist.destroy_process_group()
         return
     with torch.no_grad():
-        # warm-up (untimed), part 1 on ONE compute stream: every conv launch is event-timed -> per-kernel table and the
-        # dominant kernel instance measured in isolation; part 2 warms the multi-stream pipeline used in the timed region
+        # warm-up (untimed), part 1: with --full on ONE compute stream, every conv launch event-timed -> per-kernel table
+        # and the dominant kernel instance measured in isolation (a plain run takes the pipeline's streams and no
+        # events); part 2 warms the multi-stream pipeline used in the timed region
         nwarm = -(-max(args.warmup, 2) // group) * group  # whole groups: every launch of the pass covers `group` frames
-        warm_timer = profiling.KernelTimer(capacity=2 * 64 * nwarm + 64)
-        profiling.TIMER = warm_timer
-        pipe.single = True
+        if args.full:
+            warm_timer = profiling.KernelTimer(capacity=2 * 64 * nwarm + 64)
+            profiling.TIMER = warm_timer
+            pipe.single = True
         warm_hist = torch.zeros(3, dtype=torch.int64, device=device)  # same code path as the timed region: the
         run_frames(model, pipe, frames, nwarm, warm_hist, group=group)  # first use of a torch kernel loads its code object
         pipe.drain()
         torch.cuda.synchronize()
         pipe.single = False
         profiling.TIMER = None
-        warm = warm_timer.summarize()
-        warm_by_layer = warm_timer.summarize(by_layer=True)
-        # dominant = the (kernel instance, layer shape) with the most algorithmic flops - launches that all process the
-        # same kind of unit, so that "flops per launch / average launch duration" means something (one instance serves
-        # several layer shapes: since the dispatch thresholds favour tall tiles, the dual-body kernel runs levels 0 AND
-        # 1).  Time-ranking would be fooled by the first launch after an idle gap, whose event interval absorbs the gap.
-        dominant_layer = max(warm_by_layer.items(), key=lambda kv: kv[1]["flops"])[0]
-        dominant = dominant_layer[0]
+        warm, warm_by_layer, dominant, dominant_layer = {}, {}, None, None
+        if args.full:
+            warm = warm_timer.summarize()
+            warm_by_layer = warm_timer.summarize(by_layer=True)
+            # dominant = the (kernel instance, layer shape) with the most algorithmic flops - launches that all process
+            # the same kind of unit, so that "flops per launch / average launch duration" means something (one instance
+            # serves several layer shapes: since the dispatch thresholds favour tall tiles, the dual-body kernel runs
+            # levels 0 AND 1).  Time-ranking would be fooled by the first launch after an idle gap, whose event interval
+            # absorbs the gap.
+            dominant_layer = max(warm_by_layer.items(), key=lambda kv: kv[1]["flops"])[0]
+            dominant = dominant_layer[0]
         run_frames(model, pipe, frames, max(nwarm, 2 * group), warm_hist, group=group)
         pipe.drain()
         torch.cuda.synchronize()
         # ---- the timed region, R times: each is EXACTLY --steps steps bracketed by barrier + synchronize on both sides
         elapsed_list, voxels, hist, timer = [], 0, None, None
+        last = {} if args.dump_outputs else None  # the last step's per-point results
 
         def timed_region():
             nonlocal voxels, hist, timer
-            timer_r = profiling.KernelTimer(capacity=2 * 32 * args.steps + 64)
-            timer_r.only = {dominant}
+            timer_r = None
+            if args.full:
+                timer_r = profiling.KernelTimer(capacity=2 * 32 * args.steps + 64)
+                timer_r.only = {dominant}
             profiling.TIMER = None if args.no_kernel_timer else timer_r
             torch.cuda.synchronize()
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             hist_r = torch.zeros(3, dtype=torch.int64, device=device)
-            voxels = run_frames(model, pipe, frames, args.steps, hist_r, group=group)
+            voxels = run_frames(model, pipe, frames, args.steps, hist_r, group=group, last=last)
             torch.cuda.synchronize()
             barrier()
             torch.cuda.synchronize()
             elapsed_list.append(time.perf_counter() - t0)
             profiling.TIMER = None
-            if timer is None:
+            if hist is None:
                 timer, hist = timer_r, hist_r
-            else:
+            elif timer is not None:
                 timer.records += timer_r.records
 
-        # R repeats; short regions (small --steps) get more of them so that the timed regions total about a second or more.
-        # The count is a pure function of the arguments - identical on every rank without a collective (the run's only
-        # collective stays the one all_gather of the metrics record; the barriers are the contract's).
-        repeats = min(max(1, args.repeats, -(-64 // max(args.steps * args.frames_per_step, 1))), 64)
+        # R repeats (--full); short regions (small --steps) get more of them so that the timed regions total about a second
+        # or more.  The count is a pure function of the arguments - identical on every rank without a collective (the
+        # run's only collective stays the one all_gather of the metrics record; the barriers are the contract's).
+        repeats = max(1, args.repeats)
+        if args.full:
+            repeats = min(max(repeats, -(-64 // max(args.steps * args.frames_per_step, 1))), 64)
         _log(f"warm-up done; timing {args.steps} steps x {repeats} repeats")
         for _ in range(repeats):
             timed_region()
     elapsed = _median(elapsed_list)
     _log(f"timed regions: median {elapsed * 1e3 / args.steps:.2f} ms/step over {len(elapsed_list)} repeats "
          f"(min {min(elapsed_list) * 1e3 / args.steps:.2f}, max {max(elapsed_list) * 1e3 / args.steps:.2f})")
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"labels": last["label"], "confidence": last["conf"]})
     # ---- secondary, separately named configurations (N = 1 only: with more ranks they would only make the others wait)
-    extras = world == 1 and not args.no_extras and args.frames_per_step == 1
+    extras = args.full and world == 1 and not args.no_extras and args.frames_per_step == 1
     batched = None
     if extras and args.batched_frames > 1:
         bsteps = max(4, args.steps // args.batched_frames)
@@ -1033,7 +1078,7 @@ def main():
         engine = engine_block(device)
     # the strong-scaling block runs at EVERY N (same total job), so the driver's N = 1, 2, 4, 8 lines carry the curve
     strong = None
-    if not args.no_extras and args.strong_frames > 0 and args.frames_per_step == 1:
+    if args.full and not args.no_extras and args.strong_frames > 0 and args.frames_per_step == 1:
         _log(f"strong-scaling block: {args.strong_frames} frames over {world} rank(s), {src_threads} source threads per rank")
         with torch.no_grad():
             strong = strong_scaling_block(model, device, rank, world, args.strong_frames, args.streams, src_threads, barrier,
@@ -1062,8 +1107,9 @@ def main():
     voxels_per_frame = voxels // max(args.steps * args.frames_per_step, 1)
 
     if rank == 0:
-        ksum = timer.summarize()
-        ksum_by_layer = timer.summarize(by_layer=True)
+        # a plain run has no kernel timer and no warm-up tables: roofline and kernels_warmup stay None
+        ksum = timer.summarize() if timer is not None else {}
+        ksum_by_layer = timer.summarize(by_layer=True) if timer is not None else {}
         roofline = None
         nwarm = -(-max(args.warmup, 2) // group) * group  # frames of the warm-up pass (see above)
         gflop_step = sum(v["flops"] for v in warm.values()) / nwarm / 1e9  # every conv launch of one step
@@ -1135,7 +1181,7 @@ def main():
                                       "frac": round(e2e / PEAK_F32_MFMA_TFLOPS, 4)}
         kernels = {k: {"launches_per_step": round(v["launches"] / nwarm, 2), "ms_per_step": round(v["ms"] / nwarm, 3),
                        "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2),
-                       "gather_GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} for k, v in warm.items()}
+                       "gather_GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} for k, v in warm.items()} if args.full else None
         per_step = [t / args.steps * 1e3 for t in reps_max]
         line = {
             "metric": "point-cloud frames/sec at 200k pts/frame", "value": round(total_frames / t_med, 3),

@@ -259,3 +259,45 @@ def test_bench_groups_consecutive_frames_and_keeps_the_remainder():
     events.clear()
     assert bench.run_frames(None, Pipe(), frames, 5, None, group=1) == 10 + 11 + 12 + 13 + 10
     assert [e[1] for e in events if e[0] == "run"] == [[0], [1], [2], [3], [0]]
+
+
+def test_bench_keeps_the_last_steps_outputs():
+    """bench.run_frames(last=...) (--dump-outputs): the per-point label / confidence of the LAST step's frame, cut from
+    its group (points in frame order), whatever the group size and remainder (stub pipeline and network)."""
+    import importlib.util
+    import os
+    import types
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    frames = [(torch.full((10 + i, 4), float(i)), torch.zeros(10 + i, 3), None, None, None) for i in range(4)]
+
+    class Out:
+        def __init__(self, ids):
+            self.ids = ids
+
+        def slice_argmax(self, field):
+            label = torch.cat([torch.full((10 + i,), i) for i in self.ids])
+            return label, label.float() / 8
+
+    class Pipe:
+        def prepare_group(self, members):
+            ids = [int(c[0, 1]) for c, _ in members]
+            return types.SimpleNamespace(x=types.SimpleNamespace(F=torch.zeros(1, 1), ids=ids), field=None)
+
+        def run(self, prepared, fn):
+            return fn(prepared.x, prepared.field)
+
+        def drain(self):
+            pass
+
+    for steps, group in ((10, 4), (7, 4), (8, 4), (3, 1)):
+        last = {}
+        bench.run_frames(lambda x: Out(x.ids), Pipe(), frames, steps, torch.zeros(3, dtype=torch.int64), group=group,
+                         last=last)
+        want = (steps - 1) % len(frames)
+        assert last["label"].tolist() == [want] * (10 + want)
+        assert torch.equal(last["conf"], torch.full((10 + want,), want / 8))

@@ -1,5 +1,5 @@
 run() {
-  SV_CONV_FORCE_RANGE="$2" python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
+  SV_CONV_FORCE_RANGE="$2" python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-34s %.2f frames/s (min %.2f max %.2f ms/step)' % ('$1', d['value'], d['repeats']['ms_per_step_min'], d['repeats']['ms_per_step_max']))

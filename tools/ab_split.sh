@@ -2,7 +2,7 @@
 # offset-range passes of the wide 3x3x3 layers inside the frame pipeline (MRCC_SPLIT_RULES = "min_rows:cuts;..."): which
 # levels, how many passes.  Two interleaved rounds in one lease.
 run() {
-  MRCC_SPLIT_RULES="$2" python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
+  MRCC_SPLIT_RULES="$2" python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

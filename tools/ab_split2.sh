@@ -1,7 +1,7 @@
 #!/bin/bash
 # with the offset-range passes in place (launches a third as long): re-check streams, tile heights, tail share, more rules
 run() {
-  env $2 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline $3 2>/dev/null | python -c "
+  env $2 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline $3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline'] or {}

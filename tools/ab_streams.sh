@@ -4,7 +4,7 @@
 for round in 1 2; do
   for cfg in "2 0" "2 1" "3 0" "3 1" "4 0" "4 1" "5 1"; do
     set -- $cfg
-    python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --streams $1 --stagger-level0 $2 2>/dev/null | python -c "
+    python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --streams $1 --stagger-level0 $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

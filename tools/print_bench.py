@@ -1,4 +1,4 @@
-"""One-line digest of a bench.py JSON line: python tools/print_bench.py <file>"""
+"""One-line digest of a `bench.py --full` JSON line: python tools/print_bench.py <file>"""
 import json
 import sys
 

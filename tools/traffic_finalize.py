@@ -1,4 +1,4 @@
-"""gpurun_out/traffic/traffic_raw.json (tools/pmc_traffic.sh) -> profiles/<round>_traffic.json.
+"""profile_out/traffic/traffic_raw.json (tools/pmc_traffic.sh) -> profiles/<round>_traffic.json.
     python tools/traffic_finalize.py [raw.json] [round tag, e.g. r02] [commit the counters were collected at]
 
 FETCH_SIZE / WRITE_SIZE are in KB; FETCH_SIZE under-reports this kernel's row gathers, so both are scaled by the factors
@@ -10,7 +10,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-raw = json.load(open(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out/traffic/traffic_raw.json")))
+raw = json.load(open(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profile_out/traffic/traffic_raw.json")))
 
 
 def fold(name):
@@ -31,7 +31,7 @@ known = raw["known"]
 ff = known["read_bytes"] / (cal["FETCH_SIZE"] * 1024)
 wf = known["write_bytes"] / (cal["WRITE_SIZE"] * 1024)
 out = {
-    "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --no-cpu-baseline --no-extras --steps 8 --warmup 4 --streams 1` (4 frames per sparse tensor: the default --group)",
+    "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `bench.py --full --no-cpu-baseline --no-extras --steps 8 --warmup 4 --streams 1` (4 frames per sparse tensor: the default --group)",
     "calibration": {"kernel": fold(cal_name), "known_read_bytes": known["read_bytes"],
                     "known_write_bytes": known["write_bytes"], "FETCH_SIZE_KB": cal["FETCH_SIZE"],
                     "WRITE_SIZE_KB": cal["WRITE_SIZE"], "fetch_factor": round(ff, 4), "write_factor": round(wf, 4),

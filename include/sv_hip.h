@@ -40,6 +40,7 @@ extern "C" {
 #define SV_ERR_WORKSPACE (-2) /* workspace too small */
 #define SV_ERR_HIP (-3)       /* HIP runtime error, see sv_last_error() */
 #define SV_ERR_RANGE (-4)     /* coordinate or batch index outside the key range (reported in counters) */
+#define SV_ERR_UNSUPPORTED (-5) /* valid arguments outside what a fused kernel covers: the caller takes its unfused path */
 
 #define SV_ACT_NONE 0
 #define SV_ACT_RELU 1
@@ -327,8 +328,8 @@ int sv_icp_point2point(const float* src, int64_t S, const float* tgt, int64_t T,
                        size_t workspace_bytes, double* out_T, double* out_stats, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * A8  PointNet++ sampling / grouping  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,
- *      :89-109 query_ball_point, utils/data.py:13-34 numpy FPS)
+ * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,
+ *      :89-109 query_ball_point, :178-204 the set abstraction's shared MLP + max, utils/data.py:13-34 numpy FPS)
  * ------------------------------------------------------------------------------------------- */
 /* xyz float32[B][N][3]; start int64[B] first centroid (the reference draws it at random: pass it in);
  * out int64[B][S].  Distances are float32 ((dx*dx + dy*dy) + dz*dz, no fma), argmax = first maximum. */
@@ -344,6 +345,30 @@ int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, d
  * out [B][N][C]. */
 int sv_three_nn_interpolate(const float* xyz1, const float* xyz2, const float* points2, int B, int N, int S, int C,
                             float* out, sv_stream_t stream);
+/* Farthest-point sampling of G clouds of different lengths in one launch (the end-effector crops of a group of frames,
+ * utils/data.py:13-34 per crop): cloud g = xyz rows offsets[g] .. offsets[g + 1], its out_offsets[g + 1] - out_offsets[g]
+ * samples go to out[out_offsets[g] ..] as indices relative to the cloud's first row, start[g] = its first centroid.
+ * offsets, out_offsets, start: DEVICE arrays (G + 1, G + 1, G entries); max_n (host) >= the longest cloud, at most 38400
+ * (sv_fps's limit; a longer cloud is read as its first max_n points).  Arithmetic and tie rule of sv_fps: cloud by cloud
+ * the result of sv_fps on that cloud alone. */
+int sv_fps_segmented(const float* xyz, const int64_t* offsets, const int64_t* out_offsets, const int64_t* start, int G,
+                     int max_n, int64_t* out, sv_stream_t stream);
+/* PointNetSetAbstraction.forward in eval mode after sampling and ball query (model/pointnet2_utils.py:178-204, grouping of
+ * :112-140) as one launch: for every centroid q = (b, s) and neighbour j the row [xyz[b][i] - new_xyz[b][s], points[b][i]]
+ * with i = group_idx[b][s][j] goes through L shared-MLP layers y = relu(fmaf(x @ W_l, scale_l, shift_l)) (Conv 1x1 + bias +
+ * BatchNorm folded: scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) * scale), then out[b][s][c] = max over
+ * the nsample rows.  xyz float32[B][N][3], points float32[B][N][D] (NULL when D = 0), new_xyz float32[B][S][3],
+ * group_idx int64[B][S][nsample] (sv_ball_query's output), out float32[B][S][widths[L]].
+ * params: one device buffer, per layer l in order W_l float32[widths[l]][widths[l + 1]], scale_l [widths[l + 1]],
+ * shift_l [widths[l + 1]]; widths: HOST int[L + 1], widths[0] = 3 + D.
+ * Every output element is one fma chain over the input channels ascending from 0 (as sv_conv_fwd's dense rows): the
+ * unfused path's bits.  Returns SV_ERR_UNSUPPORTED (nothing launched) when nsample is not 16 / 32 / 64, L is outside
+ * 1..SV_PN_MAX_LAYERS, a layer width is not a multiple of 16 in 16..1024, or the 64-row tile's two LDS buffers exceed
+ * 160 KiB. */
+#define SV_PN_MAX_LAYERS 4
+int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B, int N,
+                   int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
+                   sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  largest single-linkage cluster of the end-effector points

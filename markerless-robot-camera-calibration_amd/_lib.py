@@ -17,6 +17,8 @@ SV_ACT_NONE, SV_ACT_RELU, SV_ACT_LEAKY_RELU = 0, 1, 2
 SV_POOL_MAX, SV_POOL_AVG = 0, 1
 SV_REDUCE_MEAN, SV_REDUCE_FIRST = 0, 1
 SV_TILE_ROWS = 128
+SV_ERR_UNSUPPORTED = -5
+SV_PN_MAX_LAYERS = 4
 SV_COORD_BIAS = 1 << 17
 SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
@@ -87,6 +89,8 @@ SIGNATURES = {
     "sv_single_linkage_roots": (c_int, [_P, c_int, c_int64, _P, c_int64, c_double, _P, c_size_t, _P, _P, _P]),
     "sv_select_equal": (c_int, [_P, c_int, c_int64, c_int64, _P, _P, _P, _P]),
     "sv_ball_query": (c_int, [_P, _P, c_int, c_int, c_int, c_double, c_int, _P, _P]),
+    "sv_fps_segmented": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
+    "sv_pointnet_sa": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
 }
 
 _lib = None

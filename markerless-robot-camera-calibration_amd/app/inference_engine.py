@@ -297,6 +297,107 @@ class InferenceEngine:
                           one_frame=one_frame)
         return runner.download(list(outs))
 
+    def _pointnet_kp_enqueue(self, crops_pts, crops_rgb, conf_th):
+        """KEY_POINTS.backbone == "pointnet2" for the G crops of a group (reference :511-537 per frame): host preparation
+        and every random draw crop by crop in the order of predict_key_points (np.random.choice / the farthest-point start,
+        then the four set abstractions' torch.randint starts), one pinned upload, farthest-point sampling of all crops in
+        one launch (sv_fps_segmented), ONE PointNet2SSG forward over the crops that have num_of_dense_input_points points,
+        the per-crop selection (sv_key_point_predictions_batched), the selected rows mapped through each crop's sample
+        indices on the device.  Returns (host views [prob, idx, selected] [G, C], event, keep-alive) like
+        _key_points_enqueue; idx are rows of the crop, crops below the point count select nothing (:512-513).  Nothing here
+        waits for the GPU."""
+        from ctypes import c_float, c_int, c_int64, c_size_t
+
+        from .._lib import call, ptr, stream_ptr
+
+        cfg = self._config
+        kp = cfg.INFERENCE.KEY_POINTS
+        n_dense = int(cfg.INFERENCE.num_of_dense_input_points)
+        farthest = kp.pointcloud_sampling_method != "uniform"
+        model = self._key_points_model
+        levels = [n_dense] + [sa.npoint for sa in (model.sa1, model.sa2, model.sa3)]  # the points each SA samples from
+        runner = self._crop_runner()
+        dev = runner.device
+        G = len(crops_pts)
+        rows, pts, feats, draws, starts = [], [], [], [], []
+        with torch.cuda.stream(runner.stream):
+            for g, (p, f) in enumerate(zip(crops_pts, crops_rgb)):
+                points = np.array(np.asarray(p), copy=True)
+                if kp.center_at_origin:
+                    points, _ = preprocess.center_at_origin(points)
+                if kp.use_coordinates_as_features:
+                    f = preprocess.normalize_points(points)
+                if len(points) < n_dense:
+                    continue
+                if farthest:
+                    draws.append(np.random.randint(0, len(points)))
+                else:
+                    draws.append(np.random.choice(len(points), n_dense, replace=False))
+                starts.extend(torch.randint(0, n, (1,), dtype=torch.long, device=dev) for n in levels)
+                rows.append(g)
+                pts.append(np.asarray(points, dtype=np.float32))
+                feats.append(f.detach().cpu().numpy().astype(np.float32) if torch.is_tensor(f)
+                             else np.asarray(f, dtype=np.float32))
+            B = len(rows)
+            C = model.conv2.out_channels
+            prob = torch.zeros((G, C), dtype=torch.float32, device=dev)
+            idx = torch.zeros((G, C), dtype=torch.int64, device=dev)
+            sel = torch.zeros((G, C), dtype=torch.int32, device=dev)
+            keep = []
+            if B:
+                sizes = [len(q) for q in pts]
+                n = int(sum(sizes))
+                F = feats[0].shape[1]
+                offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+                # one pinned buffer: int64 [crop rows B | offsets B+1 | sample offsets B+1 | starts or samples],
+                # float32 [xyz | features]
+                n_int = B + 2 * (B + 1) + (B if farthest else B * n_dense)
+                slot, buf = runner.up.take(8 * n_int + 4 * n * (3 + F))
+                hi = buf[: 8 * n_int].view(torch.int64).numpy()
+                hf = buf[8 * n_int:].view(torch.float32).numpy()
+                hi[:B] = rows
+                hi[B: 2 * B + 1] = offs
+                hi[2 * B + 1: 3 * B + 2] = np.arange(B + 1, dtype=np.int64) * n_dense
+                hi[3 * B + 2:] = np.asarray(draws, dtype=np.int64).reshape(-1)
+                hx, hfe = hf[: 3 * n].reshape(n, 3), hf[3 * n:].reshape(n, F)
+                for b in range(B):
+                    hx[offs[b]:offs[b + 1]] = pts[b]
+                    hfe[offs[b]:offs[b + 1]] = feats[b]
+                d = buf.to(dev, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(runner.stream)
+                runner.up.busy_until(slot, ev)
+                di = d[: 8 * n_int].view(torch.int64)
+                df = d[8 * n_int:].view(torch.float32)
+                xyz, fe = df[: 3 * n].view(n, 3), df[3 * n:].view(n, F)
+                where, d_offs = di[:B], di[B: 2 * B + 1]
+                if farthest:  # utils/data.py:13-34 for every crop, one launch
+                    samp = torch.empty(B * n_dense, dtype=torch.int64, device=dev)
+                    call("sv_fps_segmented", ptr(xyz), ptr(d_offs), ptr(di[2 * B + 1: 3 * B + 2]),
+                         ptr(di[3 * B + 2:]), c_int(B), c_int(max(sizes)), ptr(samp), stream_ptr())
+                    samp = samp.view(B, n_dense)
+                else:
+                    samp = di[3 * B + 2:].view(B, n_dense)
+                gidx = samp + d_offs[:-1].view(B, 1)
+                inp = torch.cat((xyz[gidx], fe[gidx]), dim=-1)  # [B, n_dense, 3 + F]
+                fps_starts = torch.cat(starts).view(B, 4).t()
+                with torch.no_grad():
+                    logits, _ = model(inp.transpose(2, 1), fps_starts=fps_starts)
+                logits = logits.reshape(B * n_dense, -1)
+                bprob = torch.empty((B, C), dtype=torch.float32, device=dev)
+                bidx = torch.empty((B, C), dtype=torch.int64, device=dev)
+                bsel = torch.empty((B, C), dtype=torch.int32, device=dev)
+                work = torch.empty(B * C, dtype=torch.int64, device=dev)
+                segs = (c_int64 * (B + 1))(*[b * n_dense for b in range(B + 1)])
+                call("sv_key_point_predictions_batched", ptr(logits), c_int64(logits.stride(0)), c_int(C), segs, c_int(B),
+                     c_float(conf_th), ptr(work), c_size_t(8 * B * C), ptr(bprob), ptr(bidx), ptr(bsel), stream_ptr())
+                prob.index_copy_(0, where, bprob)
+                idx.index_copy_(0, where, torch.gather(samp, 1, bidx))  # kp_idx = sample_idx[kp_idx] (:535)
+                sel.index_copy_(0, where, bsel)
+                keep = [d, logits, work, samp]
+        host, ev, kept = runner.download([prob, idx, sel])
+        return host, ev, kept + keep
+
     def predict_key_points(self, raw_points, rgb, conf_th=None):
         cfg = self._config
         kp = cfg.INFERENCE.KEY_POINTS
@@ -477,8 +578,11 @@ class InferenceEngine:
                                                                       one_frame)
             else:
                 handle["rot"] = self._rotation_enqueue(pts, cols, one_frame)
-                if cfg.INFERENCE.KEY_POINTS.backbone != "pointnet2":
-                    handle["kp"] = self._key_points_enqueue(pts, cols, cfg.INFERENCE.KEY_POINTS.conf_threshold, one_frame)
+                th = cfg.INFERENCE.KEY_POINTS.conf_threshold
+                if cfg.INFERENCE.KEY_POINTS.backbone == "pointnet2":
+                    handle["kp"] = self._pointnet_kp_enqueue(pts, cols, th)
+                else:
+                    handle["kp"] = self._key_points_enqueue(pts, cols, th, one_frame)
         return handle
 
     def _pose_collect(self, handle):
@@ -502,15 +606,12 @@ class InferenceEngine:
             results.append(result)
             if crop is None:
                 continue
-            ee_pts, ee_rgb = crop
+            ee_pts, _ = crop
             q = rot[j][3:]
             pos, _ = self.predict_translation(ee_pts, None, q=q)
             result.ee_pose = np.concatenate((pos, q))
-            if kp is not None:
-                classes = np.where(kp[2][j] != 0)[0]
-                kp_coords = ee_pts[kp[1][j][classes]]
-            else:
-                kp_coords, classes, _ = self.predict_key_points(ee_pts, torch.from_numpy(ee_rgb).to(torch.float32))
+            classes = np.where(kp[2][j] != 0)[0]
+            kp_coords = ee_pts[kp[1][j][classes]]
             result.key_points = list(zip(classes, kp_coords))
             work.append((result, data, ee_pts, np.asarray(classes), np.asarray(kp_coords)))
             j += 1

@@ -1,0 +1,287 @@
+// A8: PointNet++ set abstraction (eval mode) as ONE launch: group gather -> shared MLP -> max over the group.
+//
+//  sv_pointnet_sa <- model/pointnet2_utils.py:178-204 PointNetSetAbstraction.forward: the grouped tensor of
+//                    sample_and_group (:112-140, [xyz[idx] - new_xyz, points[idx]]), Conv2d 1x1 + BatchNorm2d + ReLU per
+//                    layer, torch.max over the nsample neighbours.  The unfused eval path runs the same layers as dense
+//                    rows through sv_conv_fwd (one launch per layer, every intermediate in HBM) plus a torch gather / cat /
+//                    max; here a workgroup keeps all of it in LDS and writes only the pooled [S][C_last] rows.
+//
+// Work decomposition
+//   * a workgroup (4 waves) owns PN_ROWS = 64 rows = 64 / nsample centroids x nsample neighbours;
+//   * it gathers the rows into LDS (input channels zero-padded to a multiple of 4), then runs the layers one after
+//     another, ping-ponging between two LDS buffers; row strides are 4 * odd floats, so the 16 rows x 4 k of a
+//     v_mfma_f32_16x16x4_f32 A operand read hit 64 distinct banks;
+//   * per layer, a wave owns (16 * MR rows) x (16 * NT channels) units: A from LDS, B (weights) straight from L2 into
+//     registers, MR * NT independent accumulators;
+//   * the last layer never leaves the chip: ReLU, max over each 16-row sub-tile (registers + two lane shuffles) into
+//     LDS, then max over the sub-tiles of a centroid, written as out[centroid][c].
+// Numerics: every output element is ONE f32 fma chain over the input channels ascending, starting at 0 (the f32 MFMA is a
+// k-ordered fmaf chain), then fmaf(acc, scale, shift) and ReLU: the arithmetic of sv_conv_fwd's dense rows, so the result is
+// bit-identical to the unfused eval path on the same groups.  Zero-padded channels add fma(0, 0, acc) = acc.
+#include "sv_common.h"
+
+namespace sv {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int PN_ROWS = 64;
+constexpr int PN_THREADS = 256;
+constexpr size_t PN_LDS_MAX = 160 * 1024;  // LDS of one CU (MI355X): one workgroup per CU at the largest shapes
+
+// smallest row stride >= c that is 4 * odd (see the header comment)
+static inline int pn_stride(int c) {
+  int s = (c + 3) / 4 * 4;
+  if ((s / 4) % 2 == 0) s += 4;
+  return s;
+}
+
+struct PnLayer {
+  int cin, kpad, cout;
+  int sa_in, sa_out;  // LDS row strides of the layer's input and output
+  int64_t w, scale, shift;  // offsets into the packed parameter buffer (floats)
+};
+
+struct PnParams {
+  const float* xyz;
+  const float* points;
+  const float* new_xyz;
+  const int64_t* idx;
+  const float* params;
+  float* out;
+  int N, S, D, nsample, L;
+  int64_t nq;  // B * S
+  int buf1;    // float offset of the second LDS buffer
+  PnLayer layer[SV_PN_MAX_LAYERS];
+};
+
+template <int MR, int NT>
+__device__ __forceinline__ void pn_layer(const PnParams& p, const PnLayer& ly, const float* __restrict__ in_s,
+                                         float* __restrict__ out_s, const bool last, const int wave, const int lane) {
+  constexpr int RG = 4 / MR;  // row groups of the 64-row tile
+  const int li = lane & 15, lq = lane >> 4;
+  const float* __restrict__ W = p.params + ly.w;
+  const float* __restrict__ scale = p.params + ly.scale;
+  const float* __restrict__ shift = p.params + ly.shift;
+  const int units = ly.cout / (16 * NT) * RG;
+  for (int u = wave; u < units; u += PN_THREADS / 64) {
+    const int rg = u % RG, cg = u / RG;
+    const int r0 = rg * MR * 16, c0 = cg * NT * 16;
+    f32x4 acc[MR][NT];
+#pragma unroll
+    for (int s = 0; s < MR; ++s)
+#pragma unroll
+      for (int n = 0; n < NT; ++n) acc[s][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* __restrict__ wp = W + c0 + li;
+    const float* __restrict__ ap = in_s + (r0 + li) * ly.sa_in + lq;
+    int k0 = 0;
+    // four k-steps per round: their weight loads are issued together, ahead of the matrix ops
+    for (; k0 + 16 <= ly.kpad; k0 += 16) {
+      float b[4][NT];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + 4 * j + lq;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) b[j][n] = k < ly.cin ? wp[(int64_t)k * ly.cout + n * 16] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float a[MR];
+#pragma unroll
+        for (int s = 0; s < MR; ++s) a[s] = ap[s * 16 * ly.sa_in + k0 + 4 * j];
+#pragma unroll
+        for (int s = 0; s < MR; ++s)
+#pragma unroll
+          for (int n = 0; n < NT; ++n) acc[s][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[j][n], acc[s][n], 0, 0, 0);
+      }
+    }
+    for (; k0 < ly.kpad; k0 += 4) {
+      const int k = k0 + lq;
+      float b[NT];
+#pragma unroll
+      for (int n = 0; n < NT; ++n) b[n] = k < ly.cin ? wp[(int64_t)k * ly.cout + n * 16] : 0.f;
+#pragma unroll
+      for (int s = 0; s < MR; ++s) {
+        const float a = ap[s * 16 * ly.sa_in + k0];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[s][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[n], acc[s][n], 0, 0, 0);
+      }
+    }
+    // epilogue: C/D map of the 16x16x4 op - column = lane & 15, row = 4 * (lane >> 4) + reg
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const int c = c0 + n * 16 + li;
+      const float sc = scale[c], sh = shift[c];
+#pragma unroll
+      for (int s = 0; s < MR; ++s) {
+        float v[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const float y = __builtin_fmaf(acc[s][n][reg], sc, sh);
+          v[reg] = y < 0.f ? 0.f : y;  // NaN stays NaN, as torch.relu
+        }
+        if (!last) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) out_s[(r0 + s * 16 + lq * 4 + reg) * ly.sa_out + c] = v[reg];
+        } else {
+          // max over the sub-tile's 16 rows (NaN propagates, as torch.max)
+          float m = v[0];
+#pragma unroll
+          for (int reg = 1; reg < 4; ++reg) m = (v[reg] > m || v[reg] != v[reg]) ? v[reg] : m;
+#pragma unroll
+          for (int d = 16; d <= 32; d <<= 1) {
+            const float o = __shfl_xor(m, d);
+            m = (o > m || o != o) ? o : m;
+          }
+          if (lq == 0) out_s[(r0 / 16 + s) * ly.cout + c] = m;  // partial maxima [4 sub-tiles][cout]
+        }
+      }
+    }
+  }
+}
+
+template <int MR, int NT>
+__device__ __forceinline__ void pn_layer_nt(const PnParams& p, const PnLayer& ly, const float* in_s, float* out_s,
+                                            bool last, int wave, int lane) {
+  pn_layer<MR, NT>(p, ly, in_s, out_s, last, wave, lane);
+}
+
+__device__ __forceinline__ void pn_layer_any(const PnParams& p, const PnLayer& ly, const float* in_s, float* out_s,
+                                             bool last, int wave, int lane) {
+  // widest units that still give every wave work: NT = 2 column tiles when Cout % 32 == 0, MR = 4 row sub-tiles
+  // when there are at least four column groups (else the rows are split between the waves)
+  const int nt = ly.cout % 32 == 0 ? 2 : 1;
+  const int cgroups = ly.cout / (16 * nt);
+  if (nt == 2) {
+    if (cgroups >= 4) pn_layer_nt<4, 2>(p, ly, in_s, out_s, last, wave, lane);
+    else if (cgroups >= 2) pn_layer_nt<2, 2>(p, ly, in_s, out_s, last, wave, lane);
+    else pn_layer_nt<1, 2>(p, ly, in_s, out_s, last, wave, lane);
+  } else {
+    if (cgroups >= 4) pn_layer_nt<4, 1>(p, ly, in_s, out_s, last, wave, lane);
+    else if (cgroups >= 2) pn_layer_nt<2, 1>(p, ly, in_s, out_s, last, wave, lane);
+    else pn_layer_nt<1, 1>(p, ly, in_s, out_s, last, wave, lane);
+  }
+}
+
+__global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* bufs[2] = {lds, lds + p.buf1};
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ns = p.nsample;
+  const int tc = PN_ROWS / ns;  // centroids per workgroup
+  const int64_t q0 = (int64_t)blockIdx.x * tc;
+  // ---- gather: row r = (centroid q0 + r / ns, neighbour r % ns) -> [xyz[idx] - new_xyz, points[idx], 0 ...]
+  {
+    const PnLayer& l0 = p.layer[0];
+    const int c_real = 3 + p.D;
+    float* dst = bufs[0];
+    for (int e = tid; e < PN_ROWS * l0.kpad; e += PN_THREADS) {
+      const int r = e / l0.kpad, c = e - r * l0.kpad;
+      const int64_t q = q0 + r / ns;
+      float v = 0.f;
+      if (q < p.nq && c < c_real) {
+        const int64_t b = q / p.S;
+        int64_t j = p.idx[q * ns + r % ns];
+        j = j < 0 ? 0 : (j >= p.N ? p.N - 1 : j);  // ball-query indices are in range; never read outside the cloud
+        const int64_t row = b * p.N + j;
+        if (c < 3)
+          v = __fsub_rn(p.xyz[row * 3 + c], p.new_xyz[q * 3 + c]);
+        else
+          v = p.points[row * p.D + (c - 3)];
+      }
+      dst[r * l0.sa_in + c] = v;
+    }
+  }
+  __syncthreads();
+  // ---- layers: layer l reads bufs[l & 1], writes bufs[(l + 1) & 1]
+  for (int l = 0; l < p.L; ++l) {
+    const bool last = l == p.L - 1;
+    pn_layer_any(p, p.layer[l], bufs[l & 1], bufs[(l + 1) & 1], last, wave, lane);
+    __syncthreads();
+  }
+  // ---- max over the sub-tiles of each centroid
+  const int cout = p.layer[p.L - 1].cout;
+  const float* part = bufs[p.L & 1];
+  const int nsub = ns / 16;
+  for (int e = tid; e < tc * cout; e += PN_THREADS) {
+    const int cl = e / cout, c = e - cl * cout;
+    const int64_t q = q0 + cl;
+    if (q >= p.nq) continue;
+    float m = part[(cl * nsub) * cout + c];
+    for (int j = 1; j < nsub; ++j) {
+      const float o = part[(cl * nsub + j) * cout + c];
+      m = (o > m || o != o) ? o : m;
+    }
+    p.out[q * cout + c] = m;
+  }
+}
+
+}  // namespace sv
+
+using namespace sv;
+
+extern "C" int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B,
+                              int N, int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
+                              sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1 && D >= 0, "bad shape");
+  SV_CHECK_ARG(widths, "null pointer");
+  if (L < 1 || L > SV_PN_MAX_LAYERS) {
+    set_error("%s: %s", __func__, "layer count outside 1..SV_PN_MAX_LAYERS");
+    return SV_ERR_UNSUPPORTED;
+  }
+  SV_CHECK_ARG(widths[0] == 3 + D, "widths[0] must be 3 + D");
+  if (nsample != 16 && nsample != 32 && nsample != 64) {
+    set_error("%s: %s", __func__, "nsample must be 16, 32 or 64");
+    return SV_ERR_UNSUPPORTED;
+  }
+  for (int l = 1; l <= L; ++l)
+    if (widths[l] < 16 || widths[l] % 16 != 0 || widths[l] > 1024) {
+      set_error("%s: %s", __func__, "layer widths must be multiples of 16 in 16..1024");
+      return SV_ERR_UNSUPPORTED;
+    }
+  PnParams p;
+  p.N = N; p.S = S; p.D = D; p.nsample = nsample; p.L = L;
+  p.nq = (int64_t)B * S;
+  // LDS: buffer 0 holds the gathered input and the outputs of layers 1, 3; buffer 1 those of layers 0, 2; the partial
+  // maxima of the last layer ([4][C_last]) go to the buffer the last layer does not read
+  int64_t need[2] = {0, 0};
+  int64_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    PnLayer& ly = p.layer[l];
+    ly.cin = widths[l];
+    ly.kpad = (widths[l] + 3) / 4 * 4;
+    ly.cout = widths[l + 1];
+    ly.sa_in = pn_stride(ly.kpad);
+    ly.sa_out = l + 1 < L ? pn_stride(ly.cout) : 0;
+    ly.w = off;
+    off += (int64_t)ly.cin * ly.cout;
+    ly.scale = off;
+    off += ly.cout;
+    ly.shift = off;
+    off += ly.cout;
+    if (l == 0) need[0] = (int64_t)PN_ROWS * ly.sa_in;
+    const int64_t o = l + 1 < L ? (int64_t)PN_ROWS * ly.sa_out : 4 * (int64_t)ly.cout;
+    if (o > need[(l + 1) & 1]) need[(l + 1) & 1] = o;
+  }
+  for (int l = 1; l < L; ++l) p.layer[l].sa_in = p.layer[l - 1].sa_out;
+  const size_t lds_bytes = (size_t)(need[0] + need[1]) * sizeof(float);
+  if (lds_bytes > PN_LDS_MAX) {
+    set_error("%s: %s", __func__, "layer widths exceed the LDS of one CU");
+    return SV_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return SV_OK;
+  SV_CHECK_ARG(xyz && new_xyz && group_idx && params && out && (D == 0 || points), "null pointer");
+  const int tc = PN_ROWS / nsample;
+  const int64_t grid = (p.nq + tc - 1) / tc;
+  SV_CHECK_ARG(grid < (1ll << 31), "too many centroids");
+  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.idx = group_idx; p.params = params; p.out = out;
+  p.buf1 = (int)need[0];
+  static bool attr_set = false;
+  if (!attr_set) {
+    SV_HIP(hipFuncSetAttribute((const void*)pointnet_sa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PN_LDS_MAX));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(pointnet_sa_kernel, dim3((unsigned)grid), dim3(PN_THREADS), lds_bytes, stream, p);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}

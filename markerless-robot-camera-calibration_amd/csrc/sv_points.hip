@@ -15,15 +15,39 @@ namespace sv {
 
 constexpr int FPS_THREADS = 1024;
 
+// Cloud of workgroup b: uniform clouds (seg == NULL) are rows b * N .. and write out[b * S ..]; segmented ones (sv_fps_segmented)
+// are rows seg[b] .. seg[b + 1] (at most N of them) and write out[oseg[b] .. oseg[b + 1]).  Returns false for an empty cloud
+// (its samples are set to 0).
+__device__ __forceinline__ bool fps_cloud(const float* xyz, int& N, int& S, const int64_t* seg, const int64_t* oseg,
+                                          int64_t* out, const float*& P, int64_t*& o) {
+  const int b = blockIdx.x;
+  if (!seg) {
+    P = xyz + (int64_t)b * N * 3;
+    o = out + (int64_t)b * S;
+    return true;
+  }
+  const int64_t r0 = seg[b], n = seg[b + 1] - r0;
+  P = xyz + r0 * 3;
+  o = out + oseg[b];
+  S = (int)(oseg[b + 1] - oseg[b]);
+  N = (int)(n < (int64_t)N ? n : (int64_t)N);
+  if (N >= 1) return true;
+  for (int it = threadIdx.x; it < S; it += blockDim.x) o[it] = 0;
+  return false;
+}
+
 __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restrict__ xyz, int N, int S,
                                                            const int64_t* __restrict__ start,
-                                                           int64_t* __restrict__ out) {
+                                                           int64_t* __restrict__ out, const int64_t* __restrict__ seg,
+                                                           const int64_t* __restrict__ oseg) {
   extern __shared__ __attribute__((aligned(16))) float dist[];  // [N]
   __shared__ float red_v[FPS_THREADS / 64];
   __shared__ int red_i[FPS_THREADS / 64];
   __shared__ int cur_s;
   const int b = blockIdx.x;
-  const float* P = xyz + (int64_t)b * N * 3;
+  const float* P;
+  int64_t* o;
+  if (!fps_cloud(xyz, N, S, seg, oseg, out, P, o)) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   for (int i = tid; i < N; i += FPS_THREADS) dist[i] = 1e10f;
   if (tid == 0) {
@@ -33,7 +57,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
   __syncthreads();
   for (int it = 0; it < S; ++it) {
     const int cur = cur_s;
-    if (tid == 0) out[(int64_t)b * S + it] = cur;
+    if (tid == 0) o[it] = cur;
     const float cx = P[cur * 3], cy = P[cur * 3 + 1], cz = P[cur * 3 + 2];
     float best = -1.0f;
     int bi = 0x7fffffff;
@@ -120,13 +144,17 @@ __device__ __forceinline__ unsigned long long read_lane64(unsigned long long k, 
 template <int PPT, bool LDS_XYZ>
 __global__ __launch_bounds__(FPS_THREADS) void fps_reg_kernel(const float* __restrict__ xyz, int N, int S,
                                                                const int64_t* __restrict__ start,
-                                                               int64_t* __restrict__ out) {
+                                                               int64_t* __restrict__ out,
+                                                               const int64_t* __restrict__ seg,
+                                                               const int64_t* __restrict__ oseg) {
   constexpr int NW = FPS_THREADS / 64;
   static_assert(NW == 16, "the cross-wave reduction is one 16-lane row");
   __shared__ unsigned long long red_k[2][NW];
   extern __shared__ __attribute__((aligned(16))) float xyz_s[];  // [3 N] when LDS_XYZ
   const int b = blockIdx.x;
-  const float* P = xyz + (int64_t)b * N * 3;
+  const float* P;
+  int64_t* o;
+  if (!fps_cloud(xyz, N, S, seg, oseg, out, P, o)) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (LDS_XYZ) {
     for (int i = tid; i < 3 * N; i += FPS_THREADS) xyz_s[i] = P[i];
@@ -146,7 +174,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_reg_kernel(const float* __res
   int cur = (int)(s0 < 0 ? 0 : (s0 >= N ? N - 1 : s0));
   float cx = P[cur * 3], cy = P[cur * 3 + 1], cz = P[cur * 3 + 2];
   for (int it = 0; it < S; ++it) {
-    if (tid == 0) out[(int64_t)b * S + it] = cur;
+    if (tid == 0) o[it] = cur;
     float best = -1.0f;
     int bi = 0x7fffffff;
 #pragma unroll
@@ -307,12 +335,11 @@ int sv_three_nn_interpolate(const float* xyz1, const float* xyz2, const float* p
   return SV_OK;
 }
 
-int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t* out, sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1, "bad shape");
-  SV_CHECK_ARG((size_t)N * sizeof(float) <= 150 * 1024, "N too large for the LDS-resident distance array (38400)");
-  if (B == 0) return SV_OK;
-  SV_CHECK_ARG(xyz && out, "null pointer");
+}  // extern "C"
+
+// one workgroup per cloud; N = the (largest) cloud's length picks the instance and sizes the LDS
+static int launch_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t* out, const int64_t* seg,
+                      const int64_t* oseg, hipStream_t stream) {
   if (N <= 16 * FPS_THREADS) {  // register-resident cloud
     static bool reg_attr_set = false;
     if (!reg_attr_set) {
@@ -328,13 +355,13 @@ int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t*
     const bool lds_xyz = xyz_bytes <= 150 * 1024;
     const dim3 g((unsigned)B), t(FPS_THREADS);
     if (N <= 4 * FPS_THREADS)
-      hipLaunchKernelGGL((fps_reg_kernel<4, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out);
+      hipLaunchKernelGGL((fps_reg_kernel<4, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out, seg, oseg);
     else if (N <= 8 * FPS_THREADS)
-      hipLaunchKernelGGL((fps_reg_kernel<8, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out);
+      hipLaunchKernelGGL((fps_reg_kernel<8, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out, seg, oseg);
     else if (lds_xyz)
-      hipLaunchKernelGGL((fps_reg_kernel<16, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out);
+      hipLaunchKernelGGL((fps_reg_kernel<16, true>), g, t, xyz_bytes, stream, xyz, N, S, start, out, seg, oseg);
     else
-      hipLaunchKernelGGL((fps_reg_kernel<16, false>), g, t, 0, stream, xyz, N, S, start, out);
+      hipLaunchKernelGGL((fps_reg_kernel<16, false>), g, t, 0, stream, xyz, N, S, start, out, seg, oseg);
     SV_LAUNCH_CHECK();
     return SV_OK;
   }
@@ -344,9 +371,30 @@ int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t*
     attr_set = true;
   }
   hipLaunchKernelGGL(fps_kernel, dim3((unsigned)B), dim3(FPS_THREADS), (size_t)N * sizeof(float), stream, xyz, N, S,
-                     start, out);
+                     start, out, seg, oseg);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+extern "C" {
+
+int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t* out, sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1, "bad shape");
+  SV_CHECK_ARG((size_t)N * sizeof(float) <= 150 * 1024, "N too large for the LDS-resident distance array (38400)");
+  if (B == 0) return SV_OK;
+  SV_CHECK_ARG(xyz && out, "null pointer");
+  return launch_fps(xyz, B, N, S, start, out, nullptr, nullptr, stream);
+}
+
+int sv_fps_segmented(const float* xyz, const int64_t* offsets, const int64_t* out_offsets, const int64_t* start, int G,
+                     int max_n, int64_t* out, sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(G >= 0 && max_n >= 1, "bad shape");
+  SV_CHECK_ARG((size_t)max_n * sizeof(float) <= 150 * 1024, "max_n too large for the LDS-resident distance array (38400)");
+  if (G == 0) return SV_OK;
+  SV_CHECK_ARG(xyz && offsets && out_offsets && start && out, "null pointer");
+  return launch_fps(xyz, G, max_n, 0, start, out, offsets, out_offsets, stream);
 }
 
 int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, double radius, int nsample, int64_t* out,

@@ -4,10 +4,12 @@ propagation stages, 1x1 conv head.  Same attribute names as the reference -> sam
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction
+from .. import nn as svnn
+from .._lib import SV_ACT_NONE, SV_ACT_RELU
+from .pointnet2_utils import FoldCache, PointNetFeaturePropagation, PointNetSetAbstraction, _fold_conv_bn
 
 
-class PointNet2SSG(nn.Module):
+class PointNet2SSG(FoldCache):
     def __init__(self, num_classes=10, in_channels=3):
         super().__init__()
         self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, in_channels + 3, [32, 32, 64], False)
@@ -23,17 +25,38 @@ class PointNet2SSG(nn.Module):
         self.drop1 = nn.Dropout(0.5)
         self.conv2 = nn.Conv1d(128, num_classes, 1)
 
-    def forward(self, xyz):
-        """xyz [B, in_channels, N] with the coordinates in the first three channels -> ([B, N, classes], l4 features)."""
+    def _head(self, l0_points):
+        """eval head on libsvhip: conv1 + bn1 + relu as one folded layer, conv2 with its bias as the shift (Dropout is the
+        identity in eval) -> [B, N, classes]"""
+        def build():
+            w1, s1, h1 = _fold_conv_bn(self.conv1, self.bn1)
+            w2 = self.conv2.weight.detach().reshape(self.conv2.out_channels, -1).t().contiguous().unsqueeze(0)
+            b2 = self.conv2.bias.detach().float().contiguous() if self.conv2.bias is not None else None
+            return w1, s1, h1, w2, b2
+
+        w1, s1, h1, w2, b2 = self._fold_get(build, (self.conv1, self.bn1, self.conv2))  # keyed on the head alone
+        B, C, N = l0_points.shape
+        rows = l0_points.permute(0, 2, 1).reshape(B * N, C)
+        x = svnn.conv_forward(rows, w1, None, B * N, s1, h1, None, SV_ACT_RELU)
+        x = svnn.conv_forward(x, w2, None, B * N, None, b2, None, SV_ACT_NONE)
+        return x.view(B, N, -1)
+
+    def forward(self, xyz, fps_starts=None):
+        """xyz [B, in_channels, N] with the coordinates in the first three channels -> ([B, N, classes], l4 features).
+        fps_starts int64 [4, B]: the first farthest-point centroid of every set abstraction (None: drawn as the reference
+        draws them)."""
+        st = [None] * 4 if fps_starts is None else [fps_starts[i] for i in range(4)]
         l0_xyz = xyz[:, :3, :]
-        l1_xyz, l1_points = self.sa1(l0_xyz, xyz)
-        l2_xyz, l2_points = self.sa2(l1_xyz, l1_points)
-        l3_xyz, l3_points = self.sa3(l2_xyz, l2_points)
-        l4_xyz, l4_points = self.sa4(l3_xyz, l3_points)
+        l1_xyz, l1_points = self.sa1(l0_xyz, xyz, fps_start=st[0])
+        l2_xyz, l2_points = self.sa2(l1_xyz, l1_points, fps_start=st[1])
+        l3_xyz, l3_points = self.sa3(l2_xyz, l2_points, fps_start=st[2])
+        l4_xyz, l4_points = self.sa4(l3_xyz, l3_points, fps_start=st[3])
         l3_points = self.fp4(l3_xyz, l4_xyz, l3_points, l4_points)
         l2_points = self.fp3(l2_xyz, l3_xyz, l2_points, l3_points)
         l1_points = self.fp2(l1_xyz, l2_xyz, l1_points, l2_points)
         l0_points = self.fp1(l0_xyz, l1_xyz, None, l1_points)
+        if not self.training and l0_points.is_cuda:
+            return self._head(l0_points), l4_points
         x = self.drop1(F.relu(self.bn1(self.conv1(l0_points))))
         x = self.conv2(x)
         return x.permute(0, 2, 1), l4_points

@@ -49,15 +49,21 @@ def square_distance(src, dst):
     return dist
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False):
-    """reference :112-140."""
-    B, N, C = xyz.shape
-    fps_idx = farthest_point_sample(xyz, npoint)
+def _group(xyz, points, new_xyz, idx):
+    """[xyz[idx] - new_xyz, points[idx]] -> [B, S, nsample, 3 + D] (reference :131-137)."""
+    B, S, C = new_xyz.shape
+    grouped_xyz = index_points(xyz, idx)
+    grouped_xyz_norm = grouped_xyz - new_xyz.view(B, S, 1, C)
+    new_points = grouped_xyz_norm if points is None else torch.cat([grouped_xyz_norm, index_points(points, idx)], -1)
+    return grouped_xyz, new_points
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, fps_start=None):
+    """reference :112-140.  fps_start int64 [B] pins the first centroids (None: drawn as the reference draws them)."""
+    fps_idx = farthest_point_sample(xyz, npoint, start=fps_start)
     new_xyz = index_points(xyz, fps_idx)
     idx = query_ball_point(radius, nsample, xyz, new_xyz)
-    grouped_xyz = index_points(xyz, idx)
-    grouped_xyz_norm = grouped_xyz - new_xyz.view(B, npoint, 1, C)
-    new_points = grouped_xyz_norm if points is None else torch.cat([grouped_xyz_norm, index_points(points, idx)], -1)
+    grouped_xyz, new_points = _group(xyz, points, new_xyz, idx)
     if returnfps:
         return new_xyz, new_points, grouped_xyz, fps_idx
     return new_xyz, new_points
@@ -90,12 +96,45 @@ def _fold_conv_bn(conv, bn):
     return w, torch.from_numpy(scale).to(dev), torch.from_numpy(shift).to(dev)
 
 
-def _mlp_rows(rows, convs, bns):
-    """rows [R, Cin] -> relu(bn(conv(.))) stack, one fused launch per layer."""
-    for conv, bn in zip(convs, bns):
-        w, scale, shift = _fold_conv_bn(conv, bn)
+def _mlp_rows(rows, convs, bns, folds=None):
+    """rows [R, Cin] -> relu(bn(conv(.))) stack, one fused launch per layer (folds: the layers' _fold_conv_bn results)."""
+    if folds is None:
+        folds = [_fold_conv_bn(conv, bn) for conv, bn in zip(convs, bns)]
+    for w, scale, shift in folds:
         rows = svnn.conv_forward(rows, w, None, rows.shape[0], scale, shift, None, SV_ACT_RELU)
     return rows
+
+
+class FoldCache(nn.Module):
+    """Eval-mode modules whose Conv + BatchNorm pairs run folded (W, scale, shift): the folds are computed once (host
+    arithmetic of _fold_conv_bn, i.e. one read-back of the BatchNorm tensors) and reused, so an eval forward after the
+    first one has no host synchronisation.  Dropped on train() / eval(), load_state_dict and .to() / _apply; an in-place
+    change of a parameter or buffer (its version counter) also rebuilds them."""
+
+    def _folds_drop(self):
+        self.__dict__["_fold_cache"] = None
+
+    def _fold_get(self, build, modules=None):
+        """build() once; rebuilt when a parameter or buffer of `modules` (default: the whole module) changed in place"""
+        mods = (self,) if modules is None else modules
+        ver = svnn._tensor_versions(*(t for m in mods for t in (*m.parameters(), *m.buffers())))
+        cache = self.__dict__.get("_fold_cache")
+        if cache is None or cache[0] != ver:
+            cache = (ver, build())
+            self.__dict__["_fold_cache"] = cache
+        return cache[1]
+
+    def train(self, mode=True):
+        self._folds_drop()
+        return super().train(mode)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._folds_drop()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._folds_drop()
+        return super()._load_from_state_dict(*args, **kwargs)
 
 
 def sample_and_group_all(xyz, points):
@@ -106,7 +145,7 @@ def sample_and_group_all(xyz, points):
     return new_xyz, new_points
 
 
-class PointNetSetAbstraction(nn.Module):
+class PointNetSetAbstraction(FoldCache):
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
         super().__init__()
         self.npoint, self.radius, self.nsample, self.group_all = npoint, radius, nsample, group_all
@@ -118,25 +157,72 @@ class PointNetSetAbstraction(nn.Module):
             self.mlp_bns.append(nn.BatchNorm2d(out))
             last = out
 
-    def forward(self, xyz, points):
-        """xyz [B,3,N], points [B,D,N] -> new_xyz [B,3,S], new_points [B,D',S]."""
+    def _folded(self):
+        """(per-layer folds, packed sv_pointnet_sa parameters, host widths) - built once per weights / device"""
+        def build():
+            folds = [_fold_conv_bn(conv, bn) for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
+            packed = torch.cat([t.reshape(-1).to(torch.float32) for f in folds for t in f]).contiguous()
+            widths = [self.mlp_convs[0].in_channels] + [conv.out_channels for conv in self.mlp_convs]
+            return folds, packed, (c_int * len(widths))(*widths)
+
+        return self._fold_get(build)
+
+    def _fused(self, xyz, points, new_xyz, idx, folds):
+        """sv_pointnet_sa: gather + shared MLP + max in one launch -> [B, S, C_last], or None where the kernel does not
+        cover the shape (SV_ERR_UNSUPPORTED: nothing was launched, the caller runs the layers one by one)."""
+        from .. import _lib
+
+        _, packed, widths = folds
+        B, N, _ = xyz.shape
+        S = new_xyz.shape[1]
+        x = xyz.to(torch.float32).contiguous()
+        p = points.to(torch.float32).contiguous() if points is not None else None
+        D = p.shape[2] if p is not None else 0
+        if widths[0] != 3 + D:
+            raise ValueError(f"set abstraction expects {widths[0] - 3} point features, got {D}")
+        q = new_xyz.to(torch.float32).contiguous()
+        out = torch.empty((B, S, widths[len(widths) - 1]), dtype=torch.float32, device=xyz.device)
+        lib = _lib.load()
+        rc = lib.sv_pointnet_sa(ptr(x), ptr(p), ptr(q), ptr(idx), B, N, D, S, self.nsample, ptr(packed), widths,
+                                len(widths) - 1, ptr(out), stream_ptr())
+        if rc == _lib.SV_ERR_UNSUPPORTED:
+            return None
+        _lib._check(rc, "sv_pointnet_sa")
+        return out
+
+    def forward(self, xyz, points, fps_start=None):
+        """xyz [B,3,N], points [B,D,N] -> new_xyz [B,3,S], new_points [B,D',S].  fps_start int64 [B] pins the first
+        farthest-point centroids (None: drawn as the reference draws them, torch.randint on the device)."""
         xyz = xyz.permute(0, 2, 1)
         if points is not None:
             points = points.permute(0, 2, 1)
-        if self.group_all:
-            new_xyz, new_points = sample_and_group_all(xyz, points)
-        else:
-            new_xyz, new_points = sample_and_group(self.npoint, self.radius, self.nsample, xyz, points)
-        B, S, Kn, C = new_points.shape  # [B, npoint, nsample, C+D]
-        if self.training:
-            t = new_points.permute(0, 3, 2, 1)
-            for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-                t = F.relu(bn(conv(t)))
-            pooled = torch.max(t, 2)[0]
-        else:
-            rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns)
-            pooled = rows.view(B, S, Kn, -1).max(dim=2)[0].permute(0, 2, 1)  # [B, D', S]
-        return new_xyz.permute(0, 2, 1), pooled
+        if self.training or self.group_all:
+            if self.group_all:
+                new_xyz, new_points = sample_and_group_all(xyz, points)
+            else:
+                new_xyz, new_points = sample_and_group(self.npoint, self.radius, self.nsample, xyz, points,
+                                                       fps_start=fps_start)
+            if self.training:
+                t = new_points.permute(0, 3, 2, 1)
+                for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+                    t = F.relu(bn(conv(t)))
+                return new_xyz.permute(0, 2, 1), torch.max(t, 2)[0]
+            B, S, Kn, C = new_points.shape
+            rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns,
+                             self._folded()[0])
+            return new_xyz.permute(0, 2, 1), rows.view(B, S, Kn, -1).max(dim=2)[0].permute(0, 2, 1)
+        # eval: sampling and ball query on libsvhip, then the fused set abstraction (sv_pointnet_sa)
+        fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
+        new_xyz = index_points(xyz, fps_idx)
+        idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz)
+        folds = self._folded()
+        pooled = self._fused(xyz, points, new_xyz, idx, folds) if xyz.is_cuda else None
+        if pooled is None:  # shapes outside the fused kernel: the layers one launch each, then torch.max
+            _, new_points = _group(xyz, points, new_xyz, idx)
+            B, S, Kn, C = new_points.shape
+            rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns, folds[0])
+            pooled = rows.view(B, S, Kn, -1).max(dim=2)[0]
+        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)  # [B, D', S]
 
 
 def three_nn_interpolate(xyz1, xyz2, points2):
@@ -155,7 +241,7 @@ def three_nn_interpolate(xyz1, xyz2, points2):
     return out
 
 
-class PointNetFeaturePropagation(nn.Module):
+class PointNetFeaturePropagation(FoldCache):
     def __init__(self, in_channel, mlp):
         super().__init__()
         self.mlp_convs = nn.ModuleList()
@@ -188,5 +274,6 @@ class PointNetFeaturePropagation(nn.Module):
             for conv, bn in zip(self.mlp_convs, self.mlp_bns):
                 t = F.relu(bn(conv(t)))
             return t
-        rows = _mlp_rows(new_points.reshape(B * N, -1).contiguous(), self.mlp_convs, self.mlp_bns)
+        folds = self._fold_get(lambda: [_fold_conv_bn(conv, bn) for conv, bn in zip(self.mlp_convs, self.mlp_bns)])
+        rows = _mlp_rows(new_points.reshape(B * N, -1).contiguous(), self.mlp_convs, self.mlp_bns, folds)
         return rows.view(B, N, -1).permute(0, 2, 1)

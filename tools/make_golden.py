@@ -260,12 +260,113 @@ def gen_output_ops(rng):
                 seg_conf=conf.astype(np.float32))
 
 
+def _pointnet2_weights(sd, seed):
+    """the fixture's weight recipe (tests/test_gpu_pointnet2.py restates it): every state_dict tensor except
+    num_batches_tracked, in sorted-key order, from np.random.default_rng(seed) - conv weights N(0, 1/fan_in), conv biases
+    and BatchNorm biases N(0, 0.1^2), BatchNorm weights U(0.75, 1.25), running means N(0, 0.1^2), running variances
+    U(0.5, 1.5), the other conv weights N(0, 1.44/fan_in) but the head's conv1 / conv2 weights N(0, 9/fan_in); float32.  Returns (values, SHA-256 of the concatenated
+    float32 bytes)."""
+    import hashlib
+
+    rng = np.random.default_rng(seed)
+    vals = {}
+    for k in sorted(sd):
+        if k.endswith("num_batches_tracked"):
+            continue
+        shape = tuple(sd[k].shape)
+        if k.endswith("running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        elif k.endswith("running_mean"):
+            v = rng.standard_normal(shape) * 0.1
+        elif "bns" in k or k.startswith("bn"):
+            v = rng.uniform(0.75, 1.25, shape) if k.endswith("weight") else rng.standard_normal(shape) * 0.1
+        elif k.endswith("weight"):
+            gain = 3.0 if k.startswith("conv") else 1.2
+            v = rng.standard_normal(shape) * gain / np.sqrt(int(np.prod(shape[1:])))
+        else:
+            v = rng.standard_normal(shape) * 0.1
+        vals[k] = v.astype(np.float32)
+    blob = b"".join(vals[k].tobytes() for k in sorted(vals))
+    return vals, hashlib.sha256(blob).hexdigest()
+
+
+def gen_pointnet2(rng):
+    """model/pointnet2.py:9-43 PointNet2SSG(num_classes=6, in_channels=6), eval, CPU, with the seeded weights of
+    _pointnet2_weights (not stored: the test regenerates them and checks the hash) on three seeded inputs [B, 6, 2048];
+    every FPS start the reference draws (torch.randint, model/pointnet2_utils.py:77) recorded as starts [4, B]; outputs
+    logits [B, 2048, 6], l4_points and utils/output.py:81-87 get_key_point_predictions at conf_th = 0.75.
+    With random statistics every BatchNorm leaves the head's input nearly the same at every point (the logits' spread over
+    the points would be ~1e-3, key-point probabilities ~1/6, nothing selected); so bn1's running statistics are set to
+    the per-channel mean / variance of conv1's output on a seeded calibration batch (stored: bn1_running_mean / _var), and
+    the logits vary by ~1 over the points.  Inputs span [-1, 1] (xyz) and [-3, 3] (features): with end-effector-sized
+    clouds the per-point part of the features is small against the BatchNorm shifts, and the calibrated bn1 would magnify
+    plain fp32 rounding of the stages before it."""
+    from model.pointnet2 import PointNet2SSG as RefSSG
+
+    def cloud(B):
+        xyz = rng.uniform(-1.0, 1.0, size=(B, 3, 2048)) * [[[1.0], [0.6], [1.2]]]
+        feat = rng.uniform(-3.0, 3.0, size=(B, 3, 2048))
+        return np.concatenate([xyz, feat], axis=1).astype(np.float32)
+
+    seed = 2024
+    net = RefSSG(num_classes=6, in_channels=6)
+    sd = net.state_dict()
+    assert len(sd) == 156
+    vals, digest = _pointnet2_weights(sd, seed)
+    net.load_state_dict({k: torch.from_numpy(vals[k]) if k in vals else sd[k] for k in sd})
+    net.eval()
+    seen = {}
+    hook = net.conv1.register_forward_hook(lambda m, i, o: seen.__setitem__("conv1", o))
+    torch.manual_seed(400)
+    with torch.no_grad():
+        net(torch.from_numpy(cloud(2)))
+    hook.remove()
+    h = seen["conv1"].double()
+    bn_mean, bn_var = h.mean((0, 2)).float(), h.var((0, 2)).float()
+    with torch.no_grad():
+        net.bn1.running_mean.copy_(bn_mean)
+        net.bn1.running_var.copy_(bn_var)
+    out = dict(seed=np.int64(seed), weights_sha256=np.array(digest), n_cases=np.int64(3),
+               bn1_running_mean=bn_mean.numpy(), bn1_running_var=bn_var.numpy())
+    real_randint = torch.randint
+    for i, B in enumerate((1, 2, 1)):
+        x = cloud(B)
+        drawn = []
+
+        def recording_randint(*args, **kwargs):
+            t = real_randint(*args, **kwargs)
+            drawn.append(t.clone())
+            return t
+
+        torch.manual_seed(500 + i)
+        torch.randint = recording_randint
+        try:
+            with torch.no_grad():
+                logits, l4 = net(torch.from_numpy(x))
+        finally:
+            torch.randint = real_randint
+        assert len(drawn) == 4 and all(d.shape == (B,) for d in drawn)
+        out[f"x{i}"] = x
+        out[f"starts{i}"] = torch.stack(drawn).numpy().astype(np.int64)
+        out[f"logits{i}"] = logits.numpy().astype(np.float32)
+        out[f"l4{i}"] = l4.numpy().astype(np.float32)
+        for b in range(B):
+            idx, classes, _ = Out.get_key_point_predictions(logits[b], conf_th=0.75)
+            out[f"kp_idx{i}_{b}"] = np.asarray(idx, np.int64).reshape(-1)
+            out[f"kp_cls{i}_{b}"] = np.asarray(classes, np.int64).reshape(-1)
+            assert len(out[f"kp_cls{i}_{b}"]) >= 1, "the reference must select key points for the check to mean anything"
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
                            ("fps", gen_fps, 103), ("ball_query", gen_ball_query, 104),
                            ("preprocess", gen_preprocess, 105), ("metrics", gen_metrics, 106),
-                           ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108)]:
+                           ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
+                           ("pointnet2_ssg", gen_pointnet2, 109)]:
+        if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
+            continue
         data = fn(np.random.default_rng(seed))
         path = os.path.join(OUT, name + ".npz")
         np.savez_compressed(path, **data)

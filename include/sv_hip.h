@@ -238,6 +238,32 @@ const char* sv_conv_last_instance(void);
  * the instance (one fma chain per output element in every one of them). */
 int sv_conv_set_dispatch(double want_scale, double tail_fraction);
 
+/* ---------------------------------------------------------------------------------------------
+ * A3/A5 at reduced precision: the opt-in bf16 matrix-core path of the wide layers (the same ME.MinkowskiConvolution /
+ *   ConvolutionTranspose / Linear + BN(eval) + residual + ReLU/LeakyReLU calls as sv_conv_fwd: model/backbone/minkunet.py:125-187,
+ *   model/robotnet_segmentation.py:55-64; 41 of the 51 conv / linear layers of RobotNetSegmentation(MinkUNet18D))
+ *
+ *   Wp = bf16(W) (round to nearest even, NaN stays NaN), packed once per weight by sv_pack_weights_bf16;
+ *   acc[o][n] = acc_init[o][n] + sum over k ascending, 32-channel chunks c ascending of  bf16(in[nbr[k][o]][c..c+31]) . Wp[k][c..c+31][n]
+ *     (activations stay fp32 in memory and are rounded to bf16 in registers; products summed in fp32 by the matrix op,
+ *      one v_mfma_f32_16x16x32_bf16 per (offset, chunk): ONE accumulator chain per output element, so the result does not
+ *      depend on the tile, the launch, sv_conv_set_dispatch, offset-range passes or the frames grouped into a tensor)
+ *   epilogue in fp32, sv_conv_fwd's:  out[o][n] = act(fmaf(acc, scale[n], shift[n]) + residual[o][n])
+ * sv_pack_weights_bf16: W float32[K][Cin][Cout] -> Wp uint16 (bf16 bits)[K * Cin * Cout] in B-fragment order:
+ *     Wp[((k * Cin/32 + cb) * Cout/16 + t) * 512 + 8 l + j] = bf16(W[k][32 cb + 8 (l >> 4) + j][16 t + (l & 15)]),
+ *   l = 0..63, j = 0..7; offsets stay outermost, so the block of offsets k0.. is Wp + k0 * Cin * Cout.  Needs Cin % 32 == 0
+ *   and Cout % 16 == 0 (else SV_ERR_UNSUPPORTED); Wp 16-byte aligned.
+ * sv_conv_fwd_bf16: sv_conv_fwd_acc's arguments with Wp in place of W (acc_init NULL = start at 0), same plans (perm / nbr_s /
+ *   submask / tile_order, NULL = dense rows).  Returns SV_ERR_UNSUPPORTED, before looking at any pointer, unless
+ *   Cin % 32 == 0, Cin >= 64, Cout % 16 == 0, Cout >= 64 and K <= 27; `in` must be 16-byte aligned with in_ld % 4 == 0.
+ *   sv_conv_last_instance() then reports "conv_bf16_kernel<128, TN>".
+ * ------------------------------------------------------------------------------------------- */
+int sv_pack_weights_bf16(const float* W, int K, int Cin, int Cout, uint16_t* Wp, sv_stream_t stream);
+int sv_conv_fwd_bf16(const float* in, int64_t V_in, int64_t in_ld, int Cin, const uint16_t* Wp, int K, int Cout,
+                     const int32_t* perm, const int32_t* nbr_s, const uint32_t* submask, const int32_t* tile_order, int64_t V_out,
+                     int64_t Vpad, const float* acc_init, int64_t acc_ld, const float* scale, const float* shift,
+                     const float* residual, int64_t res_ld, int act, float slope, float* out, int64_t out_ld, sv_stream_t stream);
+
 /* Stand-alone BN(eval)/bias + residual + activation on feature rows, same arithmetic as the conv epilogue:
  *   out[v][c] = act( fmaf(in[v][c], scale[c], shift[c]) + residual[v][c] )
  * (ME.MinkowskiBatchNorm / MinkowskiReLU / MinkowskiLeakyReLU when not fused behind a conv, e.g.

@@ -57,6 +57,12 @@ SIGNATURES = {
         [_P, c_int64, c_int64, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int,
          c_float, _P, c_int64, _P],
     ),
+    "sv_pack_weights_bf16": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "sv_conv_fwd_bf16": (
+        c_int,
+        [_P, c_int64, c_int64, c_int, _P, c_int, c_int, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int,
+         c_float, _P, c_int64, _P],
+    ),
     "sv_conv_last_instance": (c_char_p, []),
     "sv_conv_set_dispatch": (c_int, [c_double, c_double]),
     "sv_frame_maps_arena_bytes": (c_size_t, [c_int64, c_int]),

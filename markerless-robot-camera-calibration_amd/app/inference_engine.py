@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import MinkowskiEngine as ME
+from .. import nn as svnn
 from ..model.backbone import minkunet
 from ..model.pointnet2 import PointNet2SSG
 from ..model.robotnet import make_robotnet, make_robotnet_encode
@@ -55,9 +56,18 @@ def checkpoint_restore(model, f=None, device="cuda"):
 
 
 class InferenceEngine:
-    def __init__(self, calibration_only=False, device="cuda", allow_random_init=False, seed=1, cad_points=None):
+    def __init__(self, calibration_only=False, device="cuda", allow_random_init=False, seed=1, cad_points=None,
+                 seg_precision=None):
+        """seg_precision: "fp32" or "bf16" compute precision of the segmentation network's wide conv / linear layers
+        (nn.set_compute_precision; None = INFERENCE.SEGMENTATION.precision when the config has it, else fp32).  The pose
+        networks always run fp32."""
         self._config = config.Config()
         cfg = self._config
+        if seg_precision is None:
+            seg_precision = cfg()["INFERENCE"]["SEGMENTATION"].get("precision") or "fp32"
+        if seg_precision not in svnn.PRECISIONS:
+            raise ValueError(f"seg_precision must be one of {svnn.PRECISIONS}, got {seg_precision!r}")
+        self.seg_precision = seg_precision
         self.device = torch.device(device)
         # CAD-to-crop ICP (utils/icp.py): the reference samples its CAD points from app/hand_files/hand_notblender.obj,
         # which does not ship with this build -> the caller supplies the model points
@@ -89,6 +99,7 @@ class InferenceEngine:
         seg_cls = make_robotnet_segmentation(cfg.INFERENCE.SEGMENTATION.backbone)
         self._segmentation_model = restore(
             seg_cls(in_channels=cfg.DATA.input_channel, num_classes=cfg.DATA.classes), "SEGMENTATION")
+        svnn.set_compute_precision(self._segmentation_model, seg_precision)
         compute_confidence = cfg()["STRUCTURE"].get("compute_confidence", False)
         rot_cls = (make_robotnet_encode if cfg.INFERENCE.ROTATION.encode_only else make_robotnet)(
             cfg.INFERENCE.ROTATION.backbone)

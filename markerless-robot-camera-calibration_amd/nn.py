@@ -64,8 +64,9 @@ def split_points_for(rows):
 # functional layer: one libsvhip call per op
 # ------------------------------------------------------------------------------------------------------------------
 def conv_forward(feats, weight3, plan, V_out, scale=None, shift=None, residual=None, act=SV_ACT_NONE, slope=0.01,
-                 out=None):
-    """out[o] = act(BN(sum_k in[nbr_k(o)] @ W[k]) + residual[o]); plan None = dense rows (kernel_size 1 / Linear)."""
+                 out=None, weight_bf16=None):
+    """out[o] = act(BN(sum_k in[nbr_k(o)] @ W[k]) + residual[o]); plan None = dense rows (kernel_size 1 / Linear).
+    weight_bf16: pack_weights_bf16(weight3) - the layer then runs on the bf16 matrix-core path (sv_conv_fwd_bf16)."""
     K, Cin, Cout = weight3.shape
     if feats.shape[1] != Cin:
         raise ValueError(f"input has {feats.shape[1]} channels, kernel expects {Cin}")
@@ -74,11 +75,21 @@ def conv_forward(feats, weight3, plan, V_out, scale=None, shift=None, residual=N
     if out is None:
         out = torch.empty((V_out, Cout), dtype=torch.float32, device=feats.device)
     if isinstance(plan, SplitPlan):
-        return _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out)
-    return _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, None)
+        return _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, weight_bf16)
+    return _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, None, wp=weight_bf16)
 
 
-def _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out):
+def pack_weights_bf16(weight3):
+    """W float32 [K, Cin, Cout] (CUDA) -> bf16 [K * Cin * Cout] in the fragment order of sv_conv_fwd_bf16
+    (sv_pack_weights_bf16: round to nearest even; offsets outermost, so offsets k0.. start at element k0 * Cin * Cout)."""
+    K, Cin, Cout = weight3.shape
+    w = weight3.detach().float().contiguous()
+    wp = torch.empty(K * Cin * Cout, dtype=torch.bfloat16, device=w.device)
+    call("sv_pack_weights_bf16", ptr(w), c_int(K), c_int(Cin), c_int(Cout), ptr(wp), stream_ptr())
+    return wp
+
+
+def _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, weight_bf16=None):
     """A layer as passes over ascending offset ranges (sparse.SplitPlan): every pass but the last writes the raw
     accumulators (no epilogue), the next one continues the chains from them (sv_conv_fwd_acc)."""
     K, Cin, Cout = weight3.shape
@@ -93,11 +104,12 @@ def _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act
     acc = None
     for i, (k0, k1, sub) in enumerate(plan.parts):  # timed=False: the passes are ONE layer for the per-kernel table
         w = weight3[k0:k1]
+        wp = weight_bf16[k0 * Cin * Cout:k1 * Cin * Cout] if weight_bf16 is not None else None
         if i == len(plan.parts) - 1:
-            _conv_forward_one(feats, w, sub, V_out, scale, shift, residual, act, slope, out, acc, timed=False)
+            _conv_forward_one(feats, w, sub, V_out, scale, shift, residual, act, slope, out, acc, timed=False, wp=wp)
         else:
             nxt = torch.empty((V_out, Cout), dtype=torch.float32, device=feats.device)
-            _conv_forward_one(feats, w, sub, V_out, None, None, None, SV_ACT_NONE, slope, nxt, acc, timed=False)
+            _conv_forward_one(feats, w, sub, V_out, None, None, None, SV_ACT_NONE, slope, nxt, acc, timed=False, wp=wp)
             acc = nxt
     if t0 is not None:
         timer.stop(t0, _lib.conv_last_instance()[0], K, Cin, Cout, V_out, plan.pairs_device(), level=plan.out_stride,
@@ -105,7 +117,7 @@ def _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act
     return out
 
 
-def _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, acc_init, timed=True):
+def _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, slope, out, acc_init, timed=True, wp=None):
     K, Cin, Cout = weight3.shape
     if plan is None:
         Vpad = (max(V_out, 1) + _lib.SV_TILE_ROWS - 1) // _lib.SV_TILE_ROWS * _lib.SV_TILE_ROWS
@@ -123,8 +135,10 @@ def _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, 
 
     acc_ld = acc_init.stride(0) if acc_init is not None else 0
 
+    fn, w_arg = ("sv_conv_fwd_acc", weight3) if wp is None else ("sv_conv_fwd_bf16", wp)
+
     def launch(f, pl, o, r, v_out, v_pad, a=None):
-        call("sv_conv_fwd_acc", ptr(f), c_int64(f.shape[0]), c_int64(f.stride(0)), c_int(Cin), ptr(weight3), c_int(K),
+        call(fn, ptr(f), c_int64(f.shape[0]), c_int64(f.stride(0)), c_int(Cin), ptr(w_arg), c_int(K),
              c_int(Cout), ptr(pl.perm if pl else None), ptr(pl.nbr_s if pl else None), ptr(pl.submask if pl else None),
              ptr(pl.tile_order if pl else None), c_int64(v_out), c_int64(v_pad), ptr(a), c_int64(acc_ld), ptr(scale), ptr(shift),
              ptr(r), c_int64(res_ld), c_int(act), c_float(slope), ptr(o), c_int64(o.stride(0)), stream_ptr())
@@ -194,9 +208,63 @@ def _tensor_versions(*ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# compute precision of the conv / linear layers
+# ------------------------------------------------------------------------------------------------------------------
+PRECISIONS = ("fp32", "bf16")
+
+
+def _layer_channels(m):
+    if isinstance(m, MinkowskiLinear):
+        return m.linear.in_features, m.linear.out_features, 1
+    return m.in_channels, m.out_channels, m.kernel_volume
+
+
+def bf16_eligible(m):
+    """What sv_conv_fwd_bf16 covers: Cin % 32 == 0, Cin >= 64, Cout % 16 == 0, Cout >= 64, kernel volume <= 27."""
+    cin, cout, kv = _layer_channels(m)
+    return cin % 32 == 0 and cin >= 64 and cout % 16 == 0 and cout >= 64 and kv <= 27
+
+
+def set_compute_precision(module, precision):
+    """Mark the conv / linear layers of `module` (itself included) for `precision`: "bf16" marks exactly the layers
+    bf16_eligible() accepts (the rest stay fp32), "fp32" marks every layer fp32 (the default).  Returns the qualified
+    names of the layers that now run at `precision`.  Parameters and state_dict are untouched."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"compute precision must be one of {PRECISIONS}, got {precision!r}")
+    marked = []
+    for name, m in module.named_modules():
+        if isinstance(m, (_ConvBase, MinkowskiLinear)):
+            p = precision if precision == "fp32" or bf16_eligible(m) else "fp32"
+            m.compute_precision = p
+            if p == precision:
+                marked.append(name)
+    return marked
+
+
+class _Bf16Weights:
+    """Per-module cache of the packed bf16 weights (plain attributes, not buffers: state_dict does not change),
+    re-packed when the weight tensor changes (the _tensor_versions pattern)."""
+
+    def _packed_bf16(self, weight, weight3):
+        ver = _tensor_versions(weight)
+        if self.__dict__.get("_wp") is None or self.__dict__.get("_wp_ver") != ver:
+            self._wp = pack_weights_bf16(weight3)
+            self._wp_ver = ver
+        return self._wp
+
+    def _weight_bf16(self):
+        """packed weights when this layer runs in bf16, else None"""
+        if self.compute_precision == "fp32":
+            return None
+        if self.compute_precision != "bf16":
+            raise ValueError(f"compute precision must be one of {PRECISIONS}, got {self.compute_precision!r}")
+        return self.packed_weights_bf16()
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # modules
 # ------------------------------------------------------------------------------------------------------------------
-class _ConvBase(nn.Module):
+class _ConvBase(_Bf16Weights, nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3,
                  transposed=False):
         super().__init__()
@@ -212,6 +280,7 @@ class _ConvBase(nn.Module):
         else:
             self.kernel = nn.Parameter(torch.empty(in_channels, out_channels))
         self.bias = nn.Parameter(torch.empty(1, out_channels)) if bias else None
+        self.compute_precision = "fp32"  # "bf16": sv_conv_fwd_bf16 (set_compute_precision)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -226,6 +295,9 @@ class _ConvBase(nn.Module):
     def weight3(self):
         w = self.kernel
         return w if w.dim() == 3 else w.unsqueeze(0)
+
+    def packed_weights_bf16(self):
+        return self._packed_bf16(self.kernel, self.weight3())
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):
@@ -278,15 +350,17 @@ class _ConvBase(nn.Module):
         elif self.bias is not None:
             shift = self.bias.detach().reshape(-1)
         res = residual.F if isinstance(residual, SparseTensor) else residual
+        wp = self._weight_bf16()
+        bf16 = {} if wp is None else {"weight_bf16": wp}  # fp32 layers: the call conv_forward always got
         if cat_with is None:
-            out = conv_forward(x.F, self.weight3().detach(), plan, V_out, scale, shift, res, act, slope)
+            out = conv_forward(x.F, self.weight3().detach(), plan, V_out, scale, shift, res, act, slope, **bf16)
             return x.new(out, tensor_stride=out_stride)
         if cat_with.coordinate_manager is not x.coordinate_manager or cat_with.tensor_stride != out_stride:
             raise ValueError("ME.cat needs tensors on the same coordinate map")
         skip = cat_with.F
         C = self.out_channels
         buf = torch.empty((V_out, C + skip.shape[1]), dtype=torch.float32, device=x.F.device)
-        conv_forward(x.F, self.weight3().detach(), plan, V_out, scale, shift, res, act, slope, out=buf[:, :C])
+        conv_forward(x.F, self.weight3().detach(), plan, V_out, scale, shift, res, act, slope, out=buf[:, :C], **bf16)
         buf[:, C:].copy_(skip)
         return x.new(buf, tensor_stride=out_stride)
 
@@ -366,12 +440,13 @@ class MinkowskiSigmoid(nn.Module):
         return x.new(torch.sigmoid(x.F))
 
 
-class MinkowskiLinear(nn.Module):
+class MinkowskiLinear(_Bf16Weights, nn.Module):
     def __init__(self, in_features, out_features, bias=True):
         super().__init__()
         self.linear = nn.Linear(in_features, out_features, bias=bias)
         self._wt = None
         self._wt_ver = None
+        self.compute_precision = "fp32"  # "bf16": sv_conv_fwd_bf16 (set_compute_precision)
 
     def weight3(self):
         """[1, Cin, Cout] view of linear.weight^T, cached (the kernel wants W[k][c][n])."""
@@ -381,10 +456,15 @@ class MinkowskiLinear(nn.Module):
             self._wt_ver = ver
         return self._wt
 
+    def packed_weights_bf16(self):
+        return self._packed_bf16(self.linear.weight, self.weight3())
+
     def forward_fused(self, x, act=SV_ACT_NONE, slope=0.01):
         F = x.F if isinstance(x, SparseTensor) else x
         shift = self.linear.bias.detach() if self.linear.bias is not None else None
-        out = conv_forward(F, self.weight3(), None, F.shape[0], None, shift, None, act, slope)
+        wp = self._weight_bf16()
+        bf16 = {} if wp is None else {"weight_bf16": wp}  # fp32 layers: the call conv_forward always got
+        out = conv_forward(F, self.weight3(), None, F.shape[0], None, shift, None, act, slope, **bf16)
         return x.new(out) if isinstance(x, SparseTensor) else out
 
     def forward(self, x):

@@ -1,5 +1,5 @@
 """Single-layer microbenchmark of sv_conv_fwd on the Cfg-2 cloud (200k pts, 2 cm): k27 Cin->Cout at a chosen level.
-    python tools/conv_microbench.py [--cin 384 --cout 384 --level 0 --iters 10]
+    python tools/conv_microbench.py [--cin 384 --cout 384 --level 0 --iters 10] [--precision bf16]
 Prints algorithmic TFLOP/s (2 P Cin Cout / time) and the plan's MFMA row-slot efficiency."""
 import argparse
 import os
@@ -25,6 +25,7 @@ ap.add_argument("--kind", default="k3")
 ap.add_argument("--cube", type=int, default=0, help="solid cube of this edge length (voxels) instead of the room cloud")
 ap.add_argument("--split", default="0", help="run the 3x3x3 layer as passes over offset ranges: 14 -> [0,14) [14,27); 9,18 -> three")
 ap.add_argument("--frames", type=int, default=1, help="this many room clouds (seeds 0, 1, ...) in one sparse tensor: the headline's launch size is 4")
+ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"), help="bf16: the opt-in matrix-core path (sv_conv_fwd_bf16)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -56,6 +57,7 @@ elif args.kind == "dense":
 torch.manual_seed(0)
 feats = torch.randn(V_in, args.cin, device=dev)
 W = torch.randn(K, args.cin, args.cout, device=dev) * 0.05
+wp = svnn.pack_weights_bf16(W) if args.precision == "bf16" else None
 P = plan.num_pairs() if plan is not None else V
 subs = [plan.submask.cpu().numpy()] if plan is not None else []
 cuts = tuple(int(v) for v in args.split.split(",") if int(v))
@@ -67,17 +69,17 @@ if subs:
     print(f"V={V} pairs={P} row-slots={slots} slot-efficiency={P / slots:.3f} tiles={subs[0].shape[0]}"
           + (f" ({len(subs)} passes)" if len(subs) > 1 else ""))
 for _ in range(2):
-    out = svnn.conv_forward(feats, W, plan, V)
+    out = svnn.conv_forward(feats, W, plan, V, weight_bf16=wp)
 torch.cuda.synchronize()
 s = torch.cuda.Event(enable_timing=True)
 e = torch.cuda.Event(enable_timing=True)
 s.record()
 for _ in range(args.iters):
-    out = svnn.conv_forward(feats, W, plan, V)
+    out = svnn.conv_forward(feats, W, plan, V, weight_bf16=wp)
 e.record()
 torch.cuda.synchronize()
 ms = s.elapsed_time(e) / args.iters
 fl = 2.0 * P * args.cin * args.cout
 gb = P * (4.0 * args.cin + 8) + 4.0 * V * args.cout + 4.0 * K * args.cin * args.cout  # SURVEY.md 8(d) gather-bytes
-print(f"{args.kind} level{args.level} {args.cin}->{args.cout}: {ms:.3f} ms/launch, {fl / ms / 1e9:.1f} TFLOP/s algorithmic "
+print(f"{args.kind} level{args.level} {args.cin}->{args.cout} {args.precision} [{mrcc_amd._lib.conv_last_instance()[0]}]: {ms:.3f} ms/launch, {fl / ms / 1e9:.1f} TFLOP/s algorithmic "
       f"({fl / 1e9:.1f} GFLOP), gather {gb / ms / 1e6:.0f} GB/s algorithmic ({gb / 1e6:.1f} MB)")

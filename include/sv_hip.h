@@ -90,7 +90,8 @@ int sv_voxelize(const void* coords4, int coords_are_int, int64_t N, void* worksp
                 int32_t* counters, sv_stream_t stream);
 
 /* per-voxel feature reduction: out[v][c] = mean (or first) of feats[order[j]][c], j in the voxel's segment,
- * summed sequentially in ascending original point index (deterministic). */
+ * summed sequentially in ascending original point index (deterministic).  IEEE sums: a NaN feature makes its voxel's
+ * mean NaN, +inf and -inf together give NaN.  Segments are never empty (sv_voxelize's seg_start). */
 int sv_voxel_reduce(const float* feats, int C, const int32_t* order, const int32_t* seg_start, int64_t V, int mode,
                     float* out, sv_stream_t stream);
 
@@ -293,19 +294,29 @@ int sv_center_scale(const float* x, int64_t ld, int64_t N, int C, const float* s
  *   (replace ME.MinkowskiGlobalMaxPooling/AvgPooling model/robotnet.py:43, robotnet_encode.py:41;
  *    SparseTensor.slice app/inference_engine.py:417,551; utils/output.py:67-73)
  * ------------------------------------------------------------------------------------------- */
-/* batch_start[b] = first row with batch index >= b, b = 0..B  (rows are sorted by batch first). */
+/* batch_start[b] = first row with batch index >= b, b = 0..B  (rows are sorted by batch first; an empty batch b has
+ * batch_start[b] == batch_start[b + 1], V = 0 gives all zeros). */
 int sv_batch_offsets(const uint64_t* keys, int64_t V, int B, int32_t* batch_start, sv_stream_t stream);
+/* out[b][c] over rows batch_start[b] .. batch_start[b + 1] of F (row stride ld >= C; out is [B][C] dense).
+ * SV_POOL_MAX: torch.amax - a NaN in the column gives NaN, otherwise the exact maximum (+-inf included).
+ * SV_POOL_AVG: float32 sum / row count (+inf with -inf gives NaN, as torch.mean); the summation order is the kernel's
+ * (4 strided partial sums), so the last bits are not a sequential sum's.
+ * An empty batch gives 0 in both modes (torch would raise for the max and give NaN for the mean). */
 int sv_global_pool(const float* F, int64_t ld, int C, const int32_t* batch_start, int B, int mode, float* out,
                    sv_stream_t stream);
+/* out[i][0..C) = F[inverse[i]][0..C) (a bit-exact gather; out is [N][C] dense). */
 int sv_slice_rows(const float* F, int64_t ld, int C, const int64_t* inverse, int64_t N, float* out,
                   sv_stream_t stream);
-/* label[i] = first index of the row maximum of F[inverse[i]][0..C), conf[i] = sigmoid(max). */
+/* label[i] = first index of the row maximum of F[inverse[i]][0..C), conf[i] = sigmoid(max) (conf may be NULL): torch's
+ * max(1) - among equal maxima the first column, and the first NaN of a row is its maximum (conf NaN). */
 int sv_slice_argmax(const float* F, int64_t ld, int C, const int64_t* inverse, int64_t N, int64_t* label,
                     float* conf, sv_stream_t stream);
 /* Key-point selection (utils/output.py:81-87 get_key_point_predictions): softmax over the C <= 32 classes of each of
  * the N rows of `logits`, then per class c: prob[c] = max over rows of softmax[:, c], idx[c] = the LOWEST row that attains
  * it (-1 and 0 when N = 0), selected[c] = prob[c] > conf_th.  workspace: 8 C bytes.  One pass over the logits, no host
- * round trip between softmax, max and threshold. */
+ * round trip between softmax, max and threshold.  NaN as in torch's softmax(1).max(0): a row holding a NaN, a +inf or
+ * only -inf logits has a NaN softmax; if any row does, every class gets prob NaN, idx = the lowest such row and
+ * selected 0. */
 int sv_key_point_predictions(const float* logits, int64_t ld, int C, int64_t N, float conf_th, void* workspace,
                              size_t workspace_bytes, float* prob, int64_t* idx, int32_t* selected, sv_stream_t stream);
 

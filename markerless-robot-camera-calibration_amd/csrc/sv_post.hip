@@ -7,6 +7,14 @@
 
 namespace sv {
 
+// numpy's min() / max() and torch.amax propagate NaN (fminf / fmaxf drop it): a NaN colour or point must steer the
+// data-dependent branches of utils/preprocess.py:20-37 on the device exactly as on the host, and a NaN feature must reach
+// a global max pool's output as it does through ME / torch
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : fminf(a, b)); }
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
+__device__ __forceinline__ double nan_min(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmin(a, b)); }
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmax(a, b)); }
+
 __global__ __launch_bounds__(256) void batch_offsets_kernel(const uint64_t* __restrict__ keys, int64_t V, int B,
                                                              int32_t* __restrict__ batch_start) {
   int b = blockIdx.x * 256 + threadIdx.x;
@@ -24,7 +32,8 @@ __global__ __launch_bounds__(256) void batch_offsets_kernel(const uint64_t* __re
 }
 
 // one workgroup per (batch, 64-channel slab); 4 waves stride the rows, lanes = channels (coalesced 256 B rows);
-// per-wave partials are combined in fixed wave order -> deterministic.
+// per-wave partials are combined in fixed wave order -> deterministic.  MAX propagates NaN (torch.amax); an empty batch
+// gives 0 in both modes.
 __global__ __launch_bounds__(256) void global_pool_kernel(const float* __restrict__ F, int64_t ld, int C,
                                                            const int32_t* __restrict__ batch_start, int mode,
                                                            float* __restrict__ out) {
@@ -37,14 +46,14 @@ __global__ __launch_bounds__(256) void global_pool_kernel(const float* __restric
   if (c < C) {
     for (int r = s + w; r < e; r += 4) {
       float v = F[(int64_t)r * ld + c];
-      acc = (mode == SV_POOL_MAX) ? fmaxf(acc, v) : acc + v;
+      acc = (mode == SV_POOL_MAX) ? nan_max(acc, v) : acc + v;
     }
   }
   part[w][threadIdx.x & 63] = acc;
   __syncthreads();
   if (w == 0 && c < C) {
     float a = part[0][threadIdx.x];
-    for (int i = 1; i < 4; ++i) a = (mode == SV_POOL_MAX) ? fmaxf(a, part[i][threadIdx.x]) : a + part[i][threadIdx.x];
+    for (int i = 1; i < 4; ++i) a = (mode == SV_POOL_MAX) ? nan_max(a, part[i][threadIdx.x]) : a + part[i][threadIdx.x];
     if (mode == SV_POOL_AVG) a = (e > s) ? a / (float)(e - s) : 0.0f;
     if (mode == SV_POOL_MAX && e <= s) a = 0.0f;
     out[(int64_t)b * C + c] = a;
@@ -71,7 +80,7 @@ __global__ __launch_bounds__(256) void slice_argmax_kernel(const float* __restri
   int bi = 0;
   for (int c = 1; c < C; ++c) {
     float v = row[c];
-    if (v > best) {
+    if (v > best || (v != v && best == best)) {  // torch's max(1): the first maximum, and the first NaN beats any number
       best = v;
       bi = c;
     }
@@ -108,12 +117,6 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
 // Stage 1: every workgroup reduces a contiguous slab of rows to one record; stage 2: one workgroup reduces the records
 // in slab order (deterministic: no atomics).
 constexpr int STAT_REC = 16;  // doubles per record: min[4], max[4], sum[4], normmax, pad
-// numpy's min() / max() propagate NaN (fminf / fmaxf drop it): a NaN colour or point must steer the data-dependent
-// branches of utils/preprocess.py:20-37 on the device exactly as on the host
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : fminf(a, b)); }
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
-__device__ __forceinline__ double nan_min(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmin(a, b)); }
-__device__ __forceinline__ double nan_max(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmax(a, b)); }
 __global__ __launch_bounds__(256) void col_stats_partial_kernel(const float* __restrict__ x, int64_t ld, int64_t N, int C,
                                                                  const float* __restrict__ sub, int64_t rows_per_block,
                                                                  double* __restrict__ rec) {
@@ -206,7 +209,9 @@ __global__ __launch_bounds__(256) void center_scale_kernel(const float* __restri
 //      probability over all points and the point that has it.  One thread per point: the row's softmax lives in
 //      registers; per class a wave reduction over packed (probability bits << 32 | ~index) keys - probabilities are
 //      positive floats, so their bit patterns order like the values, and among equal probabilities the LOWEST point index
-//      wins - and one 64-bit atomicMax per wave and class (max is associative and commutative: deterministic).
+//      wins - and one 64-bit atomicMax per wave and class (max is associative and commutative: deterministic).  A row
+//      holding a NaN, a +inf or only -inf logits has a NaN softmax (as in torch); its key carries the canonical quiet NaN,
+//      whose bits order above every probability, so torch's max(0) result follows: the lowest NaN row, probability NaN.
 template <int CMAX>
 __global__ __launch_bounds__(256) void kp_softmax_max_kernel(const float* __restrict__ logits, int64_t ld, int C,
                                                               int64_t N, unsigned long long* __restrict__ best) {
@@ -233,8 +238,9 @@ __global__ __launch_bounds__(256) void kp_softmax_max_kernel(const float* __rest
   for (int c = 0; c < CMAX; ++c) {
     if (c >= C) break;
     unsigned long long key = 0ull;
-    if (ok && p[c] == p[c])  // a NaN row never wins
-      key = ((unsigned long long)__float_as_uint(p[c]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)r);
+    if (ok)
+      key = ((unsigned long long)(p[c] == p[c] ? __float_as_uint(p[c]) : 0x7fc00000u) << 32) |
+            (unsigned long long)(0xffffffffu - (unsigned)r);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
       const unsigned long long o = __shfl_xor(key, off, 64);
@@ -252,7 +258,7 @@ __global__ void kp_finalize_kernel(const unsigned long long* __restrict__ best, 
   const float pr = key ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
   prob[c] = pr;
   idx[c] = key ? (int64_t)(0xffffffffu - (unsigned)(key & 0xffffffffull)) : -1;
-  selected[c] = pr > conf_th ? 1 : 0;
+  selected[c] = pr > conf_th ? 1 : 0;  // NaN: not selected
 }
 
 // ---- top-k of one column (utils/output.py:45-64 get_pred_center: `out[:, 1].sort(descending=True)[1][:8]` - a full sort
@@ -467,6 +473,7 @@ int sv_key_point_predictions(const float* logits, int64_t ld, int C, int64_t N, 
 int sv_key_point_predictions_batched(const float* logits, int64_t ld, int C, const int64_t* seg_start_host, int G, float conf_th,
                                      void* workspace, size_t workspace_bytes, float* prob, int64_t* idx, int32_t* selected,
                                      sv_stream_t stream_) {
+  SV_CHECK_ARG(C >= 1 && C <= 32, "bad shape (1 <= C <= 32)");  // checked here too: G = 0 makes no single call
   SV_CHECK_ARG(G >= 0 && seg_start_host, "bad segment table");
   SV_CHECK_ARG(workspace_bytes >= (size_t)G * (size_t)C * sizeof(unsigned long long), "workspace too small (8 C G bytes)");
   for (int g = 0; g < G; ++g) {

@@ -651,7 +651,8 @@ class SparseTensor:
                            inverse_mapping=inv)
 
     def slice_argmax(self, field, with_conf=True):
-        """Fused slice + utils/output.py:67-73: per-point label (first row maximum) and sigmoid(max)."""
+        """Fused slice + utils/output.py:67-73: per-point label (first row maximum, a row's first NaN beating any number, as
+        torch's max(1)) and sigmoid(max)."""
         inv = field.inverse_mapping
         if inv is None or field.coordinate_manager is not self.coordinate_manager:
             raise ValueError("the field was not voxelised into this tensor's coordinate manager")

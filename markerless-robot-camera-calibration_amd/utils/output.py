@@ -15,7 +15,8 @@ def get_key_point_predictions(logits, conf_th=0.999):
     """softmax over classes, max over points per class, threshold (utils/output.py:81-87).  CUDA logits: one libsvhip
     pass (sv_key_point_predictions: softmax in registers, per-class packed (probability, index) max) and ONE read-back of
     the C per-class results; the reference's torch formulation leaves the device three times.  Ties take the lowest point
-    index.  Host tensors (golden vectors of the reference on CPU) keep the reference formulation."""
+    index; a row whose softmax is NaN makes every class NaN and unselected, as in the torch formulation.  Host tensors
+    (golden vectors of the reference on CPU) keep the reference formulation."""
     if torch.is_tensor(logits) and logits.is_cuda:
         from ctypes import c_float, c_int, c_int64, c_size_t
 

@@ -109,9 +109,13 @@ int or_voxel_reduce(const float* feats, int C, const int32_t* order, const int32
   return 0;
 }
 
+/* torch.amax / torch.max: a NaN operand wins (fmaxf drops it) */
+static inline float nan_maxf(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
+
 /* ME.MinkowskiGlobalMaxPooling / GlobalAvgPooling over rows [bs[b], bs[b+1]) (model/robotnet.py:43, robotnet_encode.py:41).
- * MAX is order-free.  AVG: a plain sequential float32 sum in row order divided by the row count - the oracle states the
- * operation, not the device kernel's reduction tree; a float32 mean depends on the summation order in its last bits, so
+ * MAX is order-free and propagates NaN, as torch.amax; an empty batch gives 0 in both modes.  AVG: a plain sequential
+ * float32 sum in row order divided by the row count - the oracle states the operation, not the device kernel's reduction
+ * tree; a float32 mean depends on the summation order in its last bits, so
  * comparisons with the GPU's pooled values carry a tolerance (1e-4, the north_star's on pose floats; tests/test_gpu_model.py)
  * and the order-free float64 check lives in tests/test_gpu_dense_grid.py. */
 int or_global_pool(const float* F, int64_t ld, int C, const int32_t* batch_start, int B, int mode, float* out) {
@@ -121,7 +125,7 @@ int or_global_pool(const float* F, int64_t ld, int C, const int32_t* batch_start
       float a = mode == 0 ? -INFINITY : 0.0f;
       for (int r = s; r < e; ++r) {
         float v = F[(int64_t)r * ld + c];
-        a = mode == 0 ? fmaxf(a, v) : a + v;
+        a = mode == 0 ? nan_maxf(a, v) : a + v;
       }
       if (mode == 1) a = e > s ? a / (float)(e - s) : 0.0f;
       if (mode == 0 && e <= s) a = 0.0f;
@@ -131,7 +135,8 @@ int or_global_pool(const float* F, int64_t ld, int C, const int32_t* batch_start
   return 0;
 }
 
-/* utils/output.py:67-73 after SparseTensor.slice: label = first row maximum, conf = sigmoid(max) */
+/* utils/output.py:67-73 after SparseTensor.slice: label = first row maximum, conf = sigmoid(max); as torch's max(1), the
+ * first NaN of a row is its maximum (conf NaN) */
 int or_slice_argmax(const float* F, int64_t ld, int C, const int64_t* inverse, int64_t N, int64_t* label,
                     float* conf) {
   for (int64_t i = 0; i < N; ++i) {
@@ -139,7 +144,7 @@ int or_slice_argmax(const float* F, int64_t ld, int C, const int64_t* inverse, i
     float best = row[0];
     int bi = 0;
     for (int c = 1; c < C; ++c)
-      if (row[c] > best) {
+      if (row[c] > best || (row[c] != row[c] && best == best)) {
         best = row[c];
         bi = c;
       }

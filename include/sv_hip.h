@@ -338,15 +338,25 @@ int sv_topk_indices(const float* x, int64_t ld, int64_t N, int k, void* workspac
  *   (replace utils/transformation.py:178-222 get_rigid_transform_3D + :80-84 get_q_from_matrix,
  *    utils/calibration.py:69-95 compute_quaternions_weighted_average, utils/metrics.py:139-150 compute_ADD_np)
  * ------------------------------------------------------------------------------------------- */
-/* ref,tgt: double[B][Kmax][3]; K: int32[B] points used per problem (>= 3).  R: double[B][9] row-major,
- * t: double[B][3], q: double[B][4] (w,x,y,z), sign as scipy's Rotation.from_matrix leaves it. */
+/* Counts: B >= 0 (0 = nothing to do); Kmax, Mmax, Pmax >= 1; every K[b], M[b], P[b] must lie in [1, max] (NULL = max).
+ * The Python wrappers reject other counts before anything reaches the device; a kernel clamps a count to [0, max], so it
+ * never reads outside its problem, and a count of 0 gives NaN.  Rows past a problem's count are never read.
+ * NaN rule: a NaN or inf among the values a problem reads makes all of that problem's outputs NaN (not the identity
+ * rotation or quaternion the Jacobi iterations would leave); other problems of the batch are unaffected, and each
+ * problem's result has the same bits whatever else is in the batch. */
+/* ref,tgt: double[B][Kmax][3]; K: int32[B] points used per problem.  R: double[B][9] row-major, t: double[B][3],
+ * q: double[B][4] (w,x,y,z) or NULL, sign as scipy's Rotation.from_matrix leaves it (the branch of the largest of
+ * trace and diagonal, the first on ties).  R is the proper rotation minimising sum |R a + t - b|^2, t = c_B - R c_A.
+ * K = 1 or 2, or collinear points, give *a* proper rotation reaching that minimum: it is not unique there. */
 int sv_kabsch_batched(const double* ref, const double* tgt, const int32_t* K, int Kmax, int B, double* R, double* t,
                       double* q_wxyz, sv_stream_t stream);
-/* Q: double[B][Mmax][4] (w,x,y,z), w: double[B][Mmax], M: int32[B].  out: double[B][4] principal eigenvector of
- * sum w_i q_i q_i^T / sum w_i, normalised, sign such that the largest-magnitude component is positive. */
+/* Q: double[B][Mmax][4] (w,x,y,z), w: double[B][Mmax] or NULL (all 1), M: int32[B].  out: double[B][4] principal
+ * eigenvector of sum w_i q_i q_i^T / sum w_i, normalised, sign such that the largest-magnitude component is positive.
+ * A weight sum <= 0 gives NaN, as a NaN does. */
 int sv_quat_avg_batched(const double* Q, const double* w, const int32_t* M, int Mmax, int B, double* out,
                         sv_stream_t stream);
-/* ADD = mean_p || (R_gt p + t_gt) - (R_pr p + t_pr) ||, poses (x,y,z,qw,qx,qy,qz).  points double[B][Pmax][3]. */
+/* ADD = mean_p || (R_gt p + t_gt) - (R_pr p + t_pr) ||, poses (x,y,z,qw,qx,qy,qz) with R(q) of the reference's
+ * formula (q not normalised).  points double[B][Pmax][3].  Identical poses give exactly 0. */
 int sv_add_metric_batched(const double* points, const int32_t* P, int Pmax, const double* gt_pose,
                           const double* pred_pose, int B, double* add_out, sv_stream_t stream);
 
@@ -357,6 +367,12 @@ int sv_add_metric_batched(const double* points, const int32_t* P, int Pmax, cons
  *   source->target (NULL = identity).  Correspondence = nearest target point within max_distance; update = Kabsch on
  *   the correspondences; stops when |d fitness| < rel_fitness and |d rmse| < rel_rmse between two evaluations or after
  *   max_iterations updates.  out_T double[16]; out_stats double[3] = {fitness, inlier rmse, updates applied}.
+ *   Nearest neighbour: float32 squared distances of the transformed source point (transformed in float64, rounded to
+ *   float32) to every target point; ties go to the lowest target index; a NaN distance never matches, so NaN or inf
+ *   target or source points have no correspondence.  Inlier: d^2 <= (float)(max_distance^2), a point at exactly
+ *   max_distance included.  fitness = inliers / S, rmse over the inliers (0 with none).  With fewer than 3 inliers the
+ *   iteration stops with no update (0 inliers: out_T = init_T bit for bit).  A non-finite update makes T NaN.
+ *   S in [3, 2^24), T in [1, 2^24), max_distance > 0, max_iterations >= 0.
  *   The whole iteration runs on the stream without host read-backs.
  * ------------------------------------------------------------------------------------------- */
 size_t sv_icp_workspace_bytes(int64_t S);

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void kabsch_kernel(const double* __restrict__ 
   const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (prob >= B) return;  // whole wave exits together
   const int lane = threadIdx.x & 63;
-  const int K = Kp ? Kp[prob] : Kmax;
+  const int K = Kp ? min(max(Kp[prob], 0), Kmax) : Kmax;  // never read past the problem; K = 0 gives NaN
   const double* A = ref + (int64_t)prob * Kmax * 3;
   const double* Bm = tgt + (int64_t)prob * Kmax * 3;
   double sa[3] = {0, 0, 0}, sb[3] = {0, 0, 0};
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void quat_avg_kernel(const double* __restrict_
   const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (prob >= B) return;
   const int lane = threadIdx.x & 63;
-  const int M = Mp ? Mp[prob] : Mmax;
+  const int M = Mp ? min(max(Mp[prob], 0), Mmax) : Mmax;
   const double* Qp = Q + (int64_t)prob * Mmax * 4;
   const double* wp = w ? w + (int64_t)prob * Mmax : nullptr;
   double A[4][4];
@@ -184,10 +184,21 @@ __global__ __launch_bounds__(256) void quat_avg_kernel(const double* __restrict_
       for (int j = 0; j < 4; ++j) A[i][j] += wm * q[i] * q[j];
   }
   wsum = wave_sum(wsum);
+  bool finite = wsum > 0.0;  // false for NaN too
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) A[i][j] = wave_sum(A[i][j]) / wsum;
+    for (int j = 0; j < 4; ++j) {
+      A[i][j] = wave_sum(A[i][j]) / wsum;
+      finite = finite && isfinite(A[i][j]);
+    }
+  if (!finite) {  // a NaN / inf quaternion or weight, or no positive weight sum: NaN, not the identity Jacobi leaves
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) out[(int64_t)prob * 4 + i] = __builtin_nan("");
+    }
+    return;
+  }
   double E[4][4];
   jacobi_eig4(A, E);
   int best = 0;
@@ -236,7 +247,7 @@ __global__ __launch_bounds__(256) void add_metric_kernel(const double* __restric
   const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (prob >= B) return;
   const int lane = threadIdx.x & 63;
-  const int P = Pp ? Pp[prob] : Pmax;
+  const int P = Pp ? min(max(Pp[prob], 0), Pmax) : Pmax;
   const double* pts = points + (int64_t)prob * Pmax * 3;
   const double* g = gt + (int64_t)prob * 7;
   const double* r = pr + (int64_t)prob * 7;
@@ -256,7 +267,7 @@ __global__ __launch_bounds__(256) void add_metric_kernel(const double* __restric
     acc += sqrt(d2);
   }
   acc = wave_sum(acc);
-  if (lane == 0) out[prob] = P > 0 ? acc / (double)P : 0.0;
+  if (lane == 0) out[prob] = acc / (double)P;  // P = 0: the mean over no points is NaN
 }
 
 }  // namespace sv

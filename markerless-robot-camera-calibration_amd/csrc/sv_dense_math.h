@@ -58,8 +58,26 @@ __device__ __forceinline__ double det3(const double M[3][3]) {
 
 // Kabsch from the 3x3 cross-covariance H = sum (a - cA)(b - cB)^T: R = V diag(1,1,det V) U^T with H = U S V^T
 // (utils/transformation.py:203-220: R = Vt.T @ U.T, third row of Vt negated when det R < 0), t = cB - R cA.
+// A non-finite centroid or H gives NaN in all of R and t (the Jacobi sweep would otherwise leave R = I).
 __device__ __forceinline__ void kabsch_from_covariance(const double H[3][3], const double cA[3], const double cB[3],
                                                         double R[3][3], double t[3]) {
+  bool finite = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    finite = finite && isfinite(cA[r]) && isfinite(cB[r]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) finite = finite && isfinite(H[r][c]);
+  }
+  if (!finite) {
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      t[r] = nan;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) R[r][c] = nan;
+    }
+    return;
+  }
   double G[3][3], V[3][3];
 #pragma unroll
   for (int r = 0; r < 3; ++r)

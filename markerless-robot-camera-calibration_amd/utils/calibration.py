@@ -12,12 +12,26 @@ from .._lib import call, ptr, stream_ptr
 
 
 def compute_quaternions_weighted_average_batched(Q, w=None, M=None, device=None):
-    """Q [B, Mmax, 4] (w,x,y,z); w [B, Mmax]; M int[B].  Returns [B,4] float64."""
+    """Q [B, Mmax, 4] (w,x,y,z); w [B, Mmax] (None: all 1); M int[B] in [1, Mmax] (None: Mmax).  Returns [B,4] float64.
+    A NaN / inf in a problem's first M quaternions or weights, or a weight sum <= 0, gives NaN for that problem."""
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.ndim != 3 or Q.shape[2] != 4 or Q.shape[1] < 1:
+        raise ValueError(f"Q must be B x Mmax x 4 with Mmax >= 1, got {Q.shape}")
+    B, Mmax, _ = Q.shape
+    if w is not None:
+        w = np.asarray(w, dtype=np.float64)
+        if w.shape != (B, Mmax):
+            raise ValueError(f"w must have shape {(B, Mmax)}, got {w.shape}")
+    if M is not None:
+        M = np.asarray(M, dtype=np.int32)
+        if M.shape != (B,):
+            raise ValueError(f"M must have shape ({B},), got {M.shape}")
+        if (M < 1).any() or (M > Mmax).any():
+            raise ValueError(f"M out of range: every M[b] must lie in [1, {Mmax}]")
     dev = torch.device("cuda" if device is None else device)
-    Qt = torch.as_tensor(np.ascontiguousarray(Q, dtype=np.float64)).to(dev)
-    B, Mmax, _ = Qt.shape
-    wt = None if w is None else torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
-    Mt = None if M is None else torch.as_tensor(np.asarray(M, dtype=np.int32)).to(dev)
+    Qt = torch.as_tensor(np.ascontiguousarray(Q)).to(dev)
+    wt = None if w is None else torch.as_tensor(np.ascontiguousarray(w)).to(dev)
+    Mt = None if M is None else torch.as_tensor(M).to(dev)
     out = torch.empty((B, 4), dtype=torch.float64, device=dev)
     call("sv_quat_avg_batched", ptr(Qt), ptr(wt), ptr(Mt), c_int(Mmax), c_int(B), ptr(out), stream_ptr())
     return out.cpu().numpy()

@@ -14,13 +14,26 @@ from .._lib import call, ptr, stream_ptr
 
 
 def compute_ADD_batched(points, P, gt_pose, pred_pose, device=None):
-    """points [B,Pmax,3], P int[B], poses [B,7] (x,y,z,qw,qx,qy,qz) -> ADD [B] float64."""
+    """points [B,Pmax,3], P int[B] in [1, Pmax] (None: Pmax), poses [B,7] (x,y,z,qw,qx,qy,qz) -> ADD [B] float64."""
+    points = np.asarray(points, dtype=np.float64)
+    gt_pose = np.asarray(gt_pose, dtype=np.float64)
+    pred_pose = np.asarray(pred_pose, dtype=np.float64)
+    if points.ndim != 3 or points.shape[2] != 3 or points.shape[1] < 1:
+        raise ValueError(f"points must be B x Pmax x 3 with Pmax >= 1, got {points.shape}")
+    B, Pmax, _ = points.shape
+    if gt_pose.shape != (B, 7) or pred_pose.shape != (B, 7):
+        raise ValueError(f"gt_pose and pred_pose must both have shape {(B, 7)}, got {gt_pose.shape} and {pred_pose.shape}")
+    if P is not None:
+        P = np.asarray(P, dtype=np.int32)
+        if P.shape != (B,):
+            raise ValueError(f"P must have shape ({B},), got {P.shape}")
+        if (P < 1).any() or (P > Pmax).any():
+            raise ValueError(f"P out of range: every P[b] must lie in [1, {Pmax}]")
     dev = torch.device("cuda" if device is None else device)
-    pts = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float64)).to(dev)
-    B, Pmax, _ = pts.shape
-    Pt = None if P is None else torch.as_tensor(np.asarray(P, dtype=np.int32)).to(dev)
-    gt = torch.as_tensor(np.ascontiguousarray(gt_pose, dtype=np.float64)).to(dev)
-    pr = torch.as_tensor(np.ascontiguousarray(pred_pose, dtype=np.float64)).to(dev)
+    pts = torch.as_tensor(np.ascontiguousarray(points)).to(dev)
+    Pt = None if P is None else torch.as_tensor(P).to(dev)
+    gt = torch.as_tensor(np.ascontiguousarray(gt_pose)).to(dev)
+    pr = torch.as_tensor(np.ascontiguousarray(pred_pose)).to(dev)
     out = torch.empty(B, dtype=torch.float64, device=dev)
     call("sv_add_metric_batched", ptr(pts), ptr(Pt), c_int(Pmax), ptr(gt), ptr(pr), c_int(B), ptr(out), stream_ptr())
     return out.cpu().numpy()

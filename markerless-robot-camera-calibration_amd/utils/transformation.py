@@ -24,6 +24,18 @@ def get_rigid_transform_3D_batched(reference, target, K=None, device=None, as_te
     (default Kmax).  Returns (R [B,3,3], t [B,3], q_wxyz [B,4]) as float64 numpy arrays - or, as_tensors=True, as CUDA
     tensors on the current stream with nothing downloaded and no host synchronisation (a caller inside a frame pipeline
     collects them later)."""
+    ref_shape, tgt_shape = tuple(np.shape(reference)), tuple(np.shape(target))
+    if ref_shape != tgt_shape or len(ref_shape) != 3 or ref_shape[2] != 3:
+        raise ValueError(f"reference/target must both be BxKx3, got {ref_shape} and {tgt_shape}")
+    B, Kmax, _ = ref_shape
+    if Kmax < 1:
+        raise ValueError("reference/target need Kmax >= 1 points")
+    if K is not None:
+        K = np.asarray(K, dtype=np.int32)
+        if K.shape != (B,):
+            raise ValueError(f"K must have shape ({B},), got {K.shape}")
+        if (K < 1).any() or (K > Kmax).any():
+            raise ValueError(f"K out of range: every K[b] must lie in [1, {Kmax}]")
     dev = _dev(device)
     if torch.is_tensor(reference) and torch.is_tensor(target) and reference.is_cuda and target.is_cuda:
         ref = reference.to(dtype=torch.float64).contiguous()
@@ -31,15 +43,7 @@ def get_rigid_transform_3D_batched(reference, target, K=None, device=None, as_te
     else:
         ref = torch.as_tensor(np.ascontiguousarray(reference, dtype=np.float64)).to(dev)
         tgt = torch.as_tensor(np.ascontiguousarray(target, dtype=np.float64)).to(dev)
-    if ref.shape != tgt.shape or ref.dim() != 3 or ref.shape[2] != 3:
-        raise Exception(f"reference/target must both be Bx{'K'}x3, got {tuple(ref.shape)} and {tuple(tgt.shape)}")
-    B, Kmax, _ = ref.shape
-    Kt = None
-    if K is not None:
-        K = np.asarray(K, dtype=np.int32)
-        if (K < 1).any() or (K > Kmax).any():
-            raise Exception("K out of range")
-        Kt = torch.as_tensor(K).to(dev)
+    Kt = None if K is None else torch.as_tensor(K).to(dev)
     R = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
     t = torch.empty((B, 3), dtype=torch.float64, device=dev)
     q = torch.empty((B, 4), dtype=torch.float64, device=dev)
@@ -55,7 +59,7 @@ def get_rigid_transform_3D(reference, target):
     B = np.asarray(target)
     assert A.shape == B.shape
     if A.ndim != 2 or A.shape[1] != 3:
-        raise Exception(f"matrix A is not 3xN, it is {A.shape[1] if A.ndim == 2 else '?'}x{A.shape[0]}")
+        raise ValueError(f"matrix A is not 3xN, it is {A.shape[1] if A.ndim == 2 else '?'}x{A.shape[0]}")
     R, t, _ = get_rigid_transform_3D_batched(A[None], B[None])
     return R[0], t[0].reshape(-1)
 

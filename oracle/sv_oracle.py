@@ -620,7 +620,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
 # ------------------------------------------------------------------------------------------------------------------
 def icp_point2point(src, tgt, init_T=None, max_distance=0.1, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6):
     """Returns (T 4x4, fitness, inlier rmse, updates applied).  Nearest neighbour by brute force in float32 (first
-    minimum), inliers d <= max_distance, update = Kabsch on the inlier pairs, stop when fitness and rmse both move by
+    minimum; a NaN distance never matches), inliers d <= max_distance, update = Kabsch on the inlier pairs, stop when fitness and rmse both move by
     less than the tolerances between two evaluations."""
     src = np.asarray(src, dtype=np.float32)
     tgt = np.asarray(tgt, dtype=np.float32)
@@ -635,6 +635,7 @@ def icp_point2point(src, tgt, init_T=None, max_distance=0.1, max_iterations=30, 
         for s in range(0, len(p), 512):  # blocked brute force
             d = p[s:s + 512, None, :] - tgt[None, :, :]
             dd = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            dd[np.isnan(dd)] = np.inf  # a NaN distance never matches (argmin would pick it)
             nn[s:s + 512] = dd.argmin(axis=1)
             d2[s:s + 512] = dd[np.arange(dd.shape[0]), nn[s:s + 512]]
         inl = d2 <= max_d2

@@ -392,6 +392,14 @@ int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t*
  * scalar radius**2); the distance uses the reference's expanded form (-2ab + a^2 + b^2) in float32. */
 int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, double radius, int nsample,
                   int64_t* out, sv_stream_t stream);
+/* The R ball queries of one PointNetSetAbstractionMsg layer (model/pointnet2_utils.py:242-244, query_ball_point per radius
+ * over the same centroids) in one scan over the cloud: out[r] int64[B][S][nsamples[r]] is exactly sv_ball_query with
+ * (radii[r], nsamples[r]) - the same float32 distance, r^2 = (float)(radius*radius), ascending order and first-hit
+ * padding.  radii, nsamples and out are HOST arrays of R entries (out: device pointers); the radii need not be sorted.
+ * Returns SV_ERR_UNSUPPORTED (nothing launched) when R is outside 1..SV_BQ_MAX_RADII. */
+#define SV_BQ_MAX_RADII 4
+int sv_ball_query_multi(const float* xyz, const float* new_xyz, int B, int N, int S, int R, const double* radii,
+                        const int* nsamples, int64_t* const* out, sv_stream_t stream);
 /* PointNetFeaturePropagation's interpolation (model/pointnet2_utils.py:298-305): out[b][n][:] = sum over the three
  * nearest xyz2 points of points2 rows weighted by 1 / (d + 1e-8), normalised; d in the reference's expanded float32
  * form, nearest first, ties to the lower index.  xyz1 float32[B][N][3], xyz2 [B][S][3] (S >= 3), points2 [B][S][C],
@@ -422,6 +430,21 @@ int sv_fps_segmented(const float* xyz, const int64_t* offsets, const int64_t* ou
 int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B, int N,
                    int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
                    sv_stream_t stream);
+/* PointNetSetAbstractionMsg.forward in eval mode after sampling and ball query (model/pointnet2_utils.py:207-264) as one
+ * launch over R scales that share the centroids new_xyz.  Scale r groups the rows [points[b][i], xyz[b][i] - new_xyz[b][s]]
+ * with i = group_idx[r][b][s][j] (features FIRST, :247-250), runs its nlayers[r] shared-MLP layers as sv_pointnet_sa does
+ * and writes the max over its nsamples[r] rows into columns col_r .. col_r + C_r of out float32[B][S][sum C_r]
+ * (col_r = C_0 + .. + C_{r-1}, C_r its last width: the reference's torch.cat, :262).
+ * nsamples, group_idx (device pointers), params (device pointers, sv_pointnet_sa's packing per scale), nlayers: HOST
+ * arrays of R entries; widths: HOST, the R scales' width lists concatenated (nlayers[r] + 1 entries each, first 3 + D).
+ * Same arithmetic as sv_pointnet_sa: every scale's columns are bit-identical to the unfused eval path on its groups.
+ * Returns SV_ERR_UNSUPPORTED (nothing launched) when R is outside 1..SV_PN_MAX_SCALES, a scale's nsample is not
+ * 16 / 32 / 64 / 128, its layer count or widths are outside sv_pointnet_sa's limits, or its LDS (two 64-row buffers, plus
+ * C_r floats of running maxima when nsample = 128) exceeds 160 KiB. */
+#define SV_PN_MAX_SCALES 4
+int sv_pointnet_sa_msg(const float* xyz, const float* points, const float* new_xyz, int B, int N, int D, int S, int R,
+                       const int* nsamples, const int64_t* const* group_idx, const float* const* params,
+                       const int* widths, const int* nlayers, float* out, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  largest single-linkage cluster of the end-effector points

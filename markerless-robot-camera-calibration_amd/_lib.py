@@ -19,6 +19,8 @@ SV_REDUCE_MEAN, SV_REDUCE_FIRST = 0, 1
 SV_TILE_ROWS = 128
 SV_ERR_UNSUPPORTED = -5
 SV_PN_MAX_LAYERS = 4
+SV_PN_MAX_SCALES = 4
+SV_BQ_MAX_RADII = 4
 SV_COORD_BIAS = 1 << 17
 SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
@@ -97,6 +99,8 @@ SIGNATURES = {
     "sv_ball_query": (c_int, [_P, _P, c_int, c_int, c_int, c_double, c_int, _P, _P]),
     "sv_fps_segmented": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
     "sv_pointnet_sa": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
+    "sv_ball_query_multi": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "sv_pointnet_sa_msg": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -5,6 +5,9 @@
 //                    layer, torch.max over the nsample neighbours.  The unfused eval path runs the same layers as dense
 //                    rows through sv_conv_fwd (one launch per layer, every intermediate in HBM) plus a torch gather / cat /
 //                    max; here a workgroup keeps all of it in LDS and writes only the pooled [S][C_last] rows.
+//  sv_pointnet_sa_msg <- model/pointnet2_utils.py:207-264 PointNetSetAbstractionMsg.forward: the R scales of one
+//                    multi-scale layer (grouping [points[idx], xyz[idx] - new_xyz], :247-250; nsample up to 128) in one
+//                    launch, every scale's pooled rows written into its columns of the concatenated output (:262).
 //
 // Work decomposition
 //   * a workgroup (4 waves) owns PN_ROWS = 64 rows = 64 / nsample centroids x nsample neighbours;
@@ -18,6 +21,8 @@
 // Numerics: every output element is ONE f32 fma chain over the input channels ascending, starting at 0 (the f32 MFMA is a
 // k-ordered fmaf chain), then fmaf(acc, scale, shift) and ReLU: the arithmetic of sv_conv_fwd's dense rows, so the result is
 // bit-identical to the unfused eval path on the same groups.  Zero-padded channels add fma(0, 0, acc) = acc.
+#include <atomic>
+
 #include "sv_common.h"
 
 namespace sv {
@@ -55,13 +60,14 @@ struct PnParams {
 };
 
 template <int MR, int NT>
-__device__ __forceinline__ void pn_layer(const PnParams& p, const PnLayer& ly, const float* __restrict__ in_s,
-                                         float* __restrict__ out_s, const bool last, const int wave, const int lane) {
+__device__ __forceinline__ void pn_layer(const float* __restrict__ params, const PnLayer& ly,
+                                         const float* __restrict__ in_s, float* __restrict__ out_s, const bool last,
+                                         const int wave, const int lane) {
   constexpr int RG = 4 / MR;  // row groups of the 64-row tile
   const int li = lane & 15, lq = lane >> 4;
-  const float* __restrict__ W = p.params + ly.w;
-  const float* __restrict__ scale = p.params + ly.scale;
-  const float* __restrict__ shift = p.params + ly.shift;
+  const float* __restrict__ W = params + ly.w;
+  const float* __restrict__ scale = params + ly.scale;
+  const float* __restrict__ shift = params + ly.shift;
   const int units = ly.cout / (16 * NT) * RG;
   for (int u = wave; u < units; u += PN_THREADS / 64) {
     const int rg = u % RG, cg = u / RG;
@@ -140,25 +146,25 @@ __device__ __forceinline__ void pn_layer(const PnParams& p, const PnLayer& ly, c
 }
 
 template <int MR, int NT>
-__device__ __forceinline__ void pn_layer_nt(const PnParams& p, const PnLayer& ly, const float* in_s, float* out_s,
+__device__ __forceinline__ void pn_layer_nt(const float* params, const PnLayer& ly, const float* in_s, float* out_s,
                                             bool last, int wave, int lane) {
-  pn_layer<MR, NT>(p, ly, in_s, out_s, last, wave, lane);
+  pn_layer<MR, NT>(params, ly, in_s, out_s, last, wave, lane);
 }
 
-__device__ __forceinline__ void pn_layer_any(const PnParams& p, const PnLayer& ly, const float* in_s, float* out_s,
+__device__ __forceinline__ void pn_layer_any(const float* params, const PnLayer& ly, const float* in_s, float* out_s,
                                              bool last, int wave, int lane) {
   // widest units that still give every wave work: NT = 2 column tiles when Cout % 32 == 0, MR = 4 row sub-tiles
   // when there are at least four column groups (else the rows are split between the waves)
   const int nt = ly.cout % 32 == 0 ? 2 : 1;
   const int cgroups = ly.cout / (16 * nt);
   if (nt == 2) {
-    if (cgroups >= 4) pn_layer_nt<4, 2>(p, ly, in_s, out_s, last, wave, lane);
-    else if (cgroups >= 2) pn_layer_nt<2, 2>(p, ly, in_s, out_s, last, wave, lane);
-    else pn_layer_nt<1, 2>(p, ly, in_s, out_s, last, wave, lane);
+    if (cgroups >= 4) pn_layer_nt<4, 2>(params, ly, in_s, out_s, last, wave, lane);
+    else if (cgroups >= 2) pn_layer_nt<2, 2>(params, ly, in_s, out_s, last, wave, lane);
+    else pn_layer_nt<1, 2>(params, ly, in_s, out_s, last, wave, lane);
   } else {
-    if (cgroups >= 4) pn_layer_nt<4, 1>(p, ly, in_s, out_s, last, wave, lane);
-    else if (cgroups >= 2) pn_layer_nt<2, 1>(p, ly, in_s, out_s, last, wave, lane);
-    else pn_layer_nt<1, 1>(p, ly, in_s, out_s, last, wave, lane);
+    if (cgroups >= 4) pn_layer_nt<4, 1>(params, ly, in_s, out_s, last, wave, lane);
+    else if (cgroups >= 2) pn_layer_nt<2, 1>(params, ly, in_s, out_s, last, wave, lane);
+    else pn_layer_nt<1, 1>(params, ly, in_s, out_s, last, wave, lane);
   }
 }
 
@@ -195,7 +201,7 @@ __global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams 
   // ---- layers: layer l reads bufs[l & 1], writes bufs[(l + 1) & 1]
   for (int l = 0; l < p.L; ++l) {
     const bool last = l == p.L - 1;
-    pn_layer_any(p, p.layer[l], bufs[l & 1], bufs[(l + 1) & 1], last, wave, lane);
+    pn_layer_any(p.params, p.layer[l], bufs[l & 1], bufs[(l + 1) & 1], last, wave, lane);
     __syncthreads();
   }
   // ---- max over the sub-tiles of each centroid
@@ -215,9 +221,151 @@ __global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams 
   }
 }
 
+// ---- multi-scale grouping (PointNetSetAbstractionMsg): R scales over the same centroids in ONE launch.  Workgroups
+// blk0[r] .. blk0[r + 1] - 1 serve scale r, each with its own ball (group_idx_r, nsample_r), layers and parameters; LDS is
+// sized for the largest scale.  Differences from pointnet_sa_kernel:
+//   * the gather follows the MSG row layout [points[idx], xyz[idx] - new_xyz, 0 ...] (features first);
+//   * nsample 128: a centroid is two 64-row passes; pass 0's per-channel maxima wait in LDS (`run`, [C_last]) and pass 1
+//     folds its own into them with the same NaN-propagating rule;
+//   * scale r writes its pooled rows into columns col_r .. col_r + C_r of the [B][S][sum C_r] output (no cat).
+struct PnScale {
+  const int64_t* idx;
+  const float* params;
+  int nsample, L, col;
+  int buf1;  // float offset of the scale's second LDS buffer
+  int run;   // float offset of the running maxima (two-pass balls)
+  int64_t blk0;  // first workgroup of the scale
+  PnLayer layer[SV_PN_MAX_LAYERS];
+};
+
+struct PnMsgParams {
+  const float* xyz;
+  const float* points;
+  const float* new_xyz;
+  float* out;
+  int N, S, D, R, ctot;
+  int64_t nq;
+  PnScale sc[SV_PN_MAX_SCALES];
+};
+
+__global__ __launch_bounds__(PN_THREADS) void pointnet_sa_msg_kernel(const PnMsgParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int r = 0;
+  while (r + 1 < p.R && (int64_t)blockIdx.x >= p.sc[r + 1].blk0) ++r;
+  const PnScale& sc = p.sc[r];
+  float* bufs[2] = {lds, lds + sc.buf1};
+  float* run = lds + sc.run;
+  const int ns = sc.nsample;
+  const int rows_c = ns < PN_ROWS ? ns : PN_ROWS;  // rows of one centroid in one pass
+  const int tc = PN_ROWS / rows_c;                 // centroids per workgroup
+  const int npass = ns / rows_c;
+  const int64_t q0 = ((int64_t)blockIdx.x - sc.blk0) * tc;
+  const int cout = sc.layer[sc.L - 1].cout;
+  const int nsub = rows_c / 16;
+  for (int pass = 0; pass < npass; ++pass) {
+    // ---- gather: row rr = (centroid q0 + rr / rows_c, neighbour pass * rows_c + rr % rows_c)
+    {
+      const PnLayer& l0 = sc.layer[0];
+      const int c_real = p.D + 3;
+      float* dst = bufs[0];
+      for (int e = tid; e < PN_ROWS * l0.kpad; e += PN_THREADS) {
+        const int rr = e / l0.kpad, c = e - rr * l0.kpad;
+        const int64_t q = q0 + rr / rows_c;
+        float v = 0.f;
+        if (q < p.nq && c < c_real) {
+          const int64_t b = q / p.S;
+          int64_t j = sc.idx[q * ns + pass * rows_c + rr % rows_c];
+          j = j < 0 ? 0 : (j >= p.N ? p.N - 1 : j);  // ball-query indices are in range; never read outside the cloud
+          const int64_t row = b * p.N + j;
+          if (c < p.D)
+            v = p.points[row * p.D + c];
+          else
+            v = __fsub_rn(p.xyz[row * 3 + (c - p.D)], p.new_xyz[q * 3 + (c - p.D)]);
+        }
+        dst[rr * l0.sa_in + c] = v;
+      }
+    }
+    __syncthreads();
+    for (int l = 0; l < sc.L; ++l) {
+      pn_layer_any(sc.params, sc.layer[l], bufs[l & 1], bufs[(l + 1) & 1], l == sc.L - 1, wave, lane);
+      __syncthreads();
+    }
+    // ---- max over the sub-tiles of each centroid (and over the passes of a two-pass ball)
+    const float* part = bufs[sc.L & 1];
+    for (int e = tid; e < tc * cout; e += PN_THREADS) {
+      const int cl = e / cout, c = e - cl * cout;
+      const int64_t q = q0 + cl;
+      if (q >= p.nq) continue;
+      float m = part[(cl * nsub) * cout + c];
+      for (int j = 1; j < nsub; ++j) {
+        const float o = part[(cl * nsub + j) * cout + c];
+        m = (o > m || o != o) ? o : m;
+      }
+      if (pass + 1 < npass) {
+        if (pass > 0) {
+          const float o = run[c];
+          m = (m > o || m != m) ? m : o;
+        }
+        run[c] = m;  // tc == 1 for a multi-pass ball
+      } else {
+        if (pass > 0) {
+          const float o = m;
+          m = run[c];
+          m = (o > m || o != o) ? o : m;
+        }
+        p.out[q * p.ctot + sc.col + c] = m;
+      }
+    }
+    if (pass + 1 < npass) __syncthreads();  // the next gather overwrites bufs[0]
+  }
+}
+
 }  // namespace sv
 
 using namespace sv;
+
+// hipFuncSetAttribute acts on the current device: remembered per device ordinal, not once per process
+static int pn_allow_lds(const void* fn, std::atomic<bool>* done, int ndone) {
+  int dev = 0;
+  SV_HIP(hipGetDevice(&dev));
+  if (dev < ndone && done[dev].load(std::memory_order_acquire)) return SV_OK;
+  SV_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PN_LDS_MAX));
+  if (dev < ndone) done[dev].store(true, std::memory_order_release);
+  return SV_OK;
+}
+
+// Layer table and LDS plan of one shared MLP on the 64-row tile.  Buffer 0 holds the gathered input and the outputs of
+// layers 1, 3; buffer 1 those of layers 0, 2; the partial maxima of the last layer ([4][C_last]) go to the buffer the last
+// layer does not read.  Returns SV_OK or SV_ERR_UNSUPPORTED (message set) for widths the kernel does not cover.
+static int pn_plan(const char* fn, const int* widths, int L, PnLayer* layer, int64_t need[2]) {
+  for (int l = 1; l <= L; ++l)
+    if (widths[l] < 16 || widths[l] % 16 != 0 || widths[l] > 1024) {
+      set_error("%s: %s", fn, "layer widths must be multiples of 16 in 16..1024");
+      return SV_ERR_UNSUPPORTED;
+    }
+  need[0] = need[1] = 0;
+  int64_t off = 0;
+  for (int l = 0; l < L; ++l) {
+    PnLayer& ly = layer[l];
+    ly.cin = widths[l];
+    ly.kpad = (widths[l] + 3) / 4 * 4;
+    ly.cout = widths[l + 1];
+    ly.sa_in = pn_stride(ly.kpad);
+    ly.sa_out = l + 1 < L ? pn_stride(ly.cout) : 0;
+    ly.w = off;
+    off += (int64_t)ly.cin * ly.cout;
+    ly.scale = off;
+    off += ly.cout;
+    ly.shift = off;
+    off += ly.cout;
+    if (l == 0) need[0] = (int64_t)PN_ROWS * ly.sa_in;
+    const int64_t o = l + 1 < L ? (int64_t)PN_ROWS * ly.sa_out : 4 * (int64_t)ly.cout;
+    if (o > need[(l + 1) & 1]) need[(l + 1) & 1] = o;
+  }
+  for (int l = 1; l < L; ++l) layer[l].sa_in = layer[l - 1].sa_out;
+  return SV_OK;
+}
 
 extern "C" int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B,
                               int N, int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
@@ -234,36 +382,12 @@ extern "C" int sv_pointnet_sa(const float* xyz, const float* points, const float
     set_error("%s: %s", __func__, "nsample must be 16, 32 or 64");
     return SV_ERR_UNSUPPORTED;
   }
-  for (int l = 1; l <= L; ++l)
-    if (widths[l] < 16 || widths[l] % 16 != 0 || widths[l] > 1024) {
-      set_error("%s: %s", __func__, "layer widths must be multiples of 16 in 16..1024");
-      return SV_ERR_UNSUPPORTED;
-    }
   PnParams p;
   p.N = N; p.S = S; p.D = D; p.nsample = nsample; p.L = L;
   p.nq = (int64_t)B * S;
-  // LDS: buffer 0 holds the gathered input and the outputs of layers 1, 3; buffer 1 those of layers 0, 2; the partial
-  // maxima of the last layer ([4][C_last]) go to the buffer the last layer does not read
-  int64_t need[2] = {0, 0};
-  int64_t off = 0;
-  for (int l = 0; l < L; ++l) {
-    PnLayer& ly = p.layer[l];
-    ly.cin = widths[l];
-    ly.kpad = (widths[l] + 3) / 4 * 4;
-    ly.cout = widths[l + 1];
-    ly.sa_in = pn_stride(ly.kpad);
-    ly.sa_out = l + 1 < L ? pn_stride(ly.cout) : 0;
-    ly.w = off;
-    off += (int64_t)ly.cin * ly.cout;
-    ly.scale = off;
-    off += ly.cout;
-    ly.shift = off;
-    off += ly.cout;
-    if (l == 0) need[0] = (int64_t)PN_ROWS * ly.sa_in;
-    const int64_t o = l + 1 < L ? (int64_t)PN_ROWS * ly.sa_out : 4 * (int64_t)ly.cout;
-    if (o > need[(l + 1) & 1]) need[(l + 1) & 1] = o;
-  }
-  for (int l = 1; l < L; ++l) p.layer[l].sa_in = p.layer[l - 1].sa_out;
+  int64_t need[2];
+  const int rc = pn_plan(__func__, widths, L, p.layer, need);
+  if (rc != SV_OK) return rc;
   const size_t lds_bytes = (size_t)(need[0] + need[1]) * sizeof(float);
   if (lds_bytes > PN_LDS_MAX) {
     set_error("%s: %s", __func__, "layer widths exceed the LDS of one CU");
@@ -276,12 +400,77 @@ extern "C" int sv_pointnet_sa(const float* xyz, const float* points, const float
   SV_CHECK_ARG(grid < (1ll << 31), "too many centroids");
   p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.idx = group_idx; p.params = params; p.out = out;
   p.buf1 = (int)need[0];
-  static bool attr_set = false;
-  if (!attr_set) {
-    SV_HIP(hipFuncSetAttribute((const void*)pointnet_sa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PN_LDS_MAX));
-    attr_set = true;
-  }
+  static std::atomic<bool> attr_set[64];
+  const int arc = pn_allow_lds((const void*)pointnet_sa_kernel, attr_set, 64);
+  if (arc != SV_OK) return arc;
   hipLaunchKernelGGL(pointnet_sa_kernel, dim3((unsigned)grid), dim3(PN_THREADS), lds_bytes, stream, p);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+extern "C" int sv_pointnet_sa_msg(const float* xyz, const float* points, const float* new_xyz, int B, int N, int D, int S,
+                                  int R, const int* nsamples, const int64_t* const* group_idx,
+                                  const float* const* params, const int* widths, const int* nlayers, float* out,
+                                  sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1 && D >= 0, "bad shape");
+  SV_CHECK_ARG(nsamples && group_idx && params && widths && nlayers, "null pointer");
+  if (R < 1 || R > SV_PN_MAX_SCALES) {
+    set_error("%s: %s", __func__, "scale count outside 1..SV_PN_MAX_SCALES");
+    return SV_ERR_UNSUPPORTED;
+  }
+  PnMsgParams p;
+  p.N = N; p.S = S; p.D = D; p.R = R;
+  p.nq = (int64_t)B * S;
+  size_t lds_max = 0;
+  int ctot = 0, wofs = 0;
+  int64_t blocks = 0;
+  for (int r = 0; r < R; ++r) {
+    PnScale& sc = p.sc[r];
+    const int L = nlayers[r], ns = nsamples[r];
+    if (L < 1 || L > SV_PN_MAX_LAYERS) {
+      set_error("%s: %s", __func__, "layer count outside 1..SV_PN_MAX_LAYERS");
+      return SV_ERR_UNSUPPORTED;
+    }
+    const int* w = widths + wofs;
+    wofs += L + 1;
+    SV_CHECK_ARG(w[0] == 3 + D, "widths[0] of every scale must be 3 + D");
+    if (ns != 16 && ns != 32 && ns != 64 && ns != 128) {
+      set_error("%s: %s", __func__, "nsample must be 16, 32, 64 or 128");
+      return SV_ERR_UNSUPPORTED;
+    }
+    int64_t need[2];
+    const int rc = pn_plan(__func__, w, L, sc.layer, need);
+    if (rc != SV_OK) return rc;
+    const int64_t cout = w[L];
+    const int64_t floats = need[0] + need[1] + (ns > PN_ROWS ? cout : 0);  // + running maxima of a two-pass ball
+    const size_t bytes = (size_t)floats * sizeof(float);
+    if (bytes > PN_LDS_MAX) {
+      set_error("%s: %s", __func__, "layer widths exceed the LDS of one CU");
+      return SV_ERR_UNSUPPORTED;
+    }
+    if (bytes > lds_max) lds_max = bytes;
+    sc.nsample = ns; sc.L = L; sc.col = ctot;
+    sc.buf1 = (int)need[0];
+    sc.run = (int)(need[0] + need[1]);
+    ctot += (int)cout;
+    const int tc = PN_ROWS / (ns < PN_ROWS ? ns : PN_ROWS);
+    sc.blk0 = blocks;
+    blocks += (p.nq + tc - 1) / tc;
+  }
+  if (B == 0) return SV_OK;
+  SV_CHECK_ARG(xyz && new_xyz && out && (D == 0 || points), "null pointer");
+  for (int r = 0; r < R; ++r) {
+    SV_CHECK_ARG(group_idx[r] && params[r], "null pointer");
+    p.sc[r].idx = group_idx[r];
+    p.sc[r].params = params[r];
+  }
+  SV_CHECK_ARG(blocks < (1ll << 31), "too many centroids");
+  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.out = out; p.ctot = ctot;
+  static std::atomic<bool> attr_set[64];
+  const int arc = pn_allow_lds((const void*)pointnet_sa_msg_kernel, attr_set, 64);
+  if (arc != SV_OK) return arc;
+  hipLaunchKernelGGL(pointnet_sa_msg_kernel, dim3((unsigned)blocks), dim3(PN_THREADS), lds_max, stream, p);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

@@ -3,6 +3,7 @@
 //  sv_fps        <- model/pointnet2_utils.py:65-86 farthest_point_sample (torch, sequential python loop of npoint
 //                   kernel launches) and utils/data.py:13-34 get_farthest_point_sample_idx (numpy)
 //  sv_ball_query <- model/pointnet2_utils.py:89-109 query_ball_point (full [B,S,N] distance matrix + sort)
+//  sv_ball_query_multi <- the R query_ball_point calls of PointNetSetAbstractionMsg.forward (:242-244), one scan
 //
 // FPS: one workgroup per cloud, S sequential argmax rounds (first maximum wins, like numpy/torch argmax on CPU).
 // Up to 16k points the cloud and the running min-distances live in registers and a round is a DPP argmax + one
@@ -250,6 +251,68 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict
   for (int j = count + lane; j < nsample; j += 64) dst[j] = first;
 }
 
+// R radii of one multi-scale grouping layer in one scan over the cloud: per radius its own r^2, cap, count, first hit and
+// output, each the exact result of ball_query_kernel with that (radius, nsample): the same distance, compare, ascending
+// order and padding.  The scan stops once every ball is full (a full ball takes no more writes, and its first hit is set).
+struct BallQueryMulti {
+  float r2[SV_BQ_MAX_RADII];
+  int nsample[SV_BQ_MAX_RADII];
+  int64_t* out[SV_BQ_MAX_RADII];
+  int R;
+};
+
+__global__ __launch_bounds__(256) void ball_query_multi_kernel(const float* __restrict__ xyz,
+                                                                const float* __restrict__ new_xyz, int B, int N, int S,
+                                                                const BallQueryMulti a) {
+  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= (int64_t)B * S) return;
+  const int lane = threadIdx.x & 63;
+  const int b = (int)(q / S);
+  const float* P = xyz + (int64_t)b * N * 3;
+  const float qx = new_xyz[q * 3], qy = new_xyz[q * 3 + 1], qz = new_xyz[q * 3 + 2];
+  const float qq = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
+  int count[SV_BQ_MAX_RADII], first[SV_BQ_MAX_RADII];
+#pragma unroll
+  for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
+    count[r] = 0;
+    first[r] = N;
+  }
+  for (int base = 0; base < N; base += 64) {
+    bool open = false;
+#pragma unroll
+    for (int r = 0; r < SV_BQ_MAX_RADII; ++r) open |= r < a.R && count[r] < a.nsample[r];
+    if (!open) break;
+    const int i = base + lane;
+    float d = 0.f;
+    if (i < N) {
+      const float x = P[i * 3], y = P[i * 3 + 1], z = P[i * 3 + 2];
+      const float dot = __fadd_rn(__fadd_rn(__fmul_rn(qx, x), __fmul_rn(qy, y)), __fmul_rn(qz, z));
+      const float pp = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
+      d = __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), qq), pp);
+    }
+#pragma unroll
+    for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
+      if (r >= a.R) break;
+      const bool hit = i < N && !(d > a.r2[r]);
+      const unsigned long long m = __ballot(hit);
+      if (m) {
+        if (first[r] == N) first[r] = base + (int)__builtin_ctzll(m);
+        const int pos = count[r] + __popcll(m & ((1ull << lane) - 1ull));
+        if (hit && pos < a.nsample[r]) a.out[r][q * a.nsample[r] + pos] = i;
+        count[r] += __popcll(m);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
+    if (r >= a.R) break;
+    const int ns = a.nsample[r];
+    const int c = count[r] > ns ? ns : count[r];
+    int64_t* dst = a.out[r] + q * ns;
+    for (int j = c + lane; j < ns; j += 64) dst[j] = first[r];
+  }
+}
+
 // ---- 3-nearest-neighbour inverse-distance interpolation (PointNetFeaturePropagation.forward,
 //      model/pointnet2_utils.py:298-305): a workgroup serves 64 query points.  Phase 1: one thread per query walks the S
 //      source points (staged through LDS, 256 at a time) with the reference's expanded float32 distance
@@ -407,6 +470,40 @@ int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, d
   const int64_t nq = (int64_t)B * S;
   hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz, new_xyz, B, N, S, r2,
                      nsample, out);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+int sv_ball_query_multi(const float* xyz, const float* new_xyz, int B, int N, int S, int R, const double* radii,
+                        const int* nsamples, int64_t* const* out, sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1, "bad shape");
+  SV_CHECK_ARG(radii && nsamples && out, "null pointer");
+  if (R < 1 || R > SV_BQ_MAX_RADII) {
+    set_error("%s: %s", __func__, "radius count outside 1..SV_BQ_MAX_RADII");
+    return SV_ERR_UNSUPPORTED;
+  }
+  BallQueryMulti a;
+  a.R = R;
+  for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
+    a.r2[r] = 0.f;
+    a.nsample[r] = 0;
+    a.out[r] = nullptr;
+  }
+  for (int r = 0; r < R; ++r) {
+    SV_CHECK_ARG(nsamples[r] >= 1, "bad shape");
+    a.r2[r] = (float)(radii[r] * radii[r]);
+    a.nsample[r] = nsamples[r];
+  }
+  if (B == 0) return SV_OK;
+  SV_CHECK_ARG(xyz && new_xyz, "null pointer");
+  for (int r = 0; r < R; ++r) {
+    SV_CHECK_ARG(out[r], "null pointer");
+    a.out[r] = out[r];
+  }
+  const int64_t nq = (int64_t)B * S;
+  hipLaunchKernelGGL(ball_query_multi_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz, new_xyz, B, N,
+                     S, a);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

@@ -1,12 +1,16 @@
 """PointNet2SSG: the key-point network the reference configures for inference (model/pointnet2.py:9-43,
 config/override_inference_test.yaml:97).  SA 1024/256/64/16 centroids (radii .1/.2/.4/.8, 32 neighbours), four feature
-propagation stages, 1x1 conv head.  Same attribute names as the reference -> same state_dict keys."""
+propagation stages, 1x1 conv head.
+PointNet2MSGEncoder: the pose regressor of STRUCTURE.backbone = pointnet2 with encode_only (model/pointnet2.py:46-77,
+train.py:259-263): two multi-scale set abstractions (512 / 128 centroids, three radii each), a group-all one, three
+fully connected layers.  Same attribute names as the reference -> same state_dict keys."""
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import nn as svnn
 from .._lib import SV_ACT_NONE, SV_ACT_RELU
-from .pointnet2_utils import FoldCache, PointNetFeaturePropagation, PointNetSetAbstraction, _fold_conv_bn
+from .pointnet2_utils import (FoldCache, PointNetFeaturePropagation, PointNetSetAbstraction,
+                              PointNetSetAbstractionMsg, _fold_conv_bn)
 
 
 class PointNet2SSG(FoldCache):
@@ -60,3 +64,59 @@ class PointNet2SSG(FoldCache):
         x = self.drop1(F.relu(self.bn1(self.conv1(l0_points))))
         x = self.conv2(x)
         return x.permute(0, 2, 1), l4_points
+
+
+class PointNet2MSGEncoder(FoldCache):
+    def __init__(self, num_class, normal_channel=True):
+        super().__init__()
+        in_channel = 3 if normal_channel else 0
+        self.normal_channel = normal_channel
+        self.sa1 = PointNetSetAbstractionMsg(512, [0.1, 0.2, 0.4], [16, 32, 128], in_channel,
+                                             [[32, 32, 64], [64, 64, 128], [64, 96, 128]])
+        self.sa2 = PointNetSetAbstractionMsg(128, [0.2, 0.4, 0.8], [32, 64, 128], 320,
+                                             [[64, 64, 128], [128, 128, 256], [128, 128, 256]])
+        # group-all over 128 centroids, 643 -> 256 -> 512 -> 1024: dense rows (its rows do not fit the fused kernel's LDS)
+        self.sa3 = PointNetSetAbstraction(None, None, None, 640 + 3, [256, 512, 1024], True)
+        self.fc1 = nn.Linear(1024, 512)
+        self.bn1 = nn.BatchNorm1d(512)
+        self.drop1 = nn.Dropout(0.4)
+        self.fc2 = nn.Linear(512, 256)
+        self.bn2 = nn.BatchNorm1d(256)
+        self.drop2 = nn.Dropout(0.5)
+        self.fc3 = nn.Linear(256, num_class)
+
+    def _head(self, x):
+        """eval head on libsvhip: fc1 + bn1 + relu and fc2 + bn2 + relu as folded layers, fc3 with its bias as the shift
+        (Dropout is the identity in eval) -> [B, num_class]"""
+        def build():
+            w3 = self.fc3.weight.detach().t().contiguous().unsqueeze(0)
+            b3 = self.fc3.bias.detach().float().contiguous() if self.fc3.bias is not None else None
+            return _fold_conv_bn(self.fc1, self.bn1), _fold_conv_bn(self.fc2, self.bn2), (w3, b3)
+
+        (w1, s1, h1), (w2, s2, h2), (w3, b3) = self._fold_get(build, (self.fc1, self.bn1, self.fc2, self.bn2, self.fc3))
+        B = x.shape[0]
+        x = svnn.conv_forward(x.contiguous(), w1, None, B, s1, h1, None, SV_ACT_RELU)
+        x = svnn.conv_forward(x, w2, None, B, s2, h2, None, SV_ACT_RELU)
+        return svnn.conv_forward(x, w3, None, B, None, b3, None, SV_ACT_NONE)
+
+    def forward(self, xyz, fps_starts=None):
+        """xyz [B, 6, N] (coordinates, then normals; [B, 3, N] with normal_channel False) -> (x [B, num_class],
+        l3_points [B, 1024, 1]).  fps_starts int64 [2, B]: the first farthest-point centroid of sa1 and sa2 (None: drawn
+        as the reference draws them)."""
+        want = 6 if self.normal_channel else 3
+        if xyz.dim() != 3 or xyz.shape[1] != want:
+            raise ValueError(f"PointNet2MSGEncoder(normal_channel={self.normal_channel}) expects [B, {want}, N] input, "
+                             f"got {tuple(xyz.shape)}")
+        B = xyz.shape[0]
+        st = [None, None] if fps_starts is None else [fps_starts[0], fps_starts[1]]
+        norm = xyz[:, 3:, :] if self.normal_channel else None
+        xyz = xyz[:, :3, :]
+        l1_xyz, l1_points = self.sa1(xyz, norm, fps_start=st[0])
+        l2_xyz, l2_points = self.sa2(l1_xyz, l1_points, fps_start=st[1])
+        _, l3_points = self.sa3(l2_xyz, l2_points)
+        x = l3_points.reshape(B, 1024)
+        if not self.training and x.is_cuda:
+            return self._head(x), l3_points
+        x = self.drop1(F.relu(self.bn1(self.fc1(x))))
+        x = self.drop2(F.relu(self.bn2(self.fc2(x))))
+        return self.fc3(x), l3_points

@@ -2,6 +2,7 @@
 
 farthest_point_sample(xyz [B,N,3], npoint) -> int64 [B,npoint]     reference :65-86 (python loop of npoint launches)
 query_ball_point(radius, nsample, xyz, new_xyz) -> int64 [B,S,nsample]   reference :89-109 ([B,S,N] matrix + sort)
+query_ball_point_multi(radii, nsamples, xyz, new_xyz) -> R of those      one scan for a multi-scale layer's radii
 index_points, square_distance: thin torch helpers with the reference's semantics (:21-62).
 """
 from ctypes import c_double, c_int
@@ -33,6 +34,27 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     call("sv_ball_query", ptr(x), ptr(q), c_int(B), c_int(N), c_int(S), c_double(float(radius)), c_int(nsample),
          ptr(out), stream_ptr())
     return out
+
+
+def query_ball_point_multi(radius_list, nsample_list, xyz, new_xyz):
+    """[query_ball_point(radius_list[r], nsample_list[r], xyz, new_xyz) for r], the radii of one multi-scale layer in one
+    scan over the cloud per launch (sv_ball_query_multi, up to SV_BQ_MAX_RADII radii a launch); bit-identical per radius."""
+    from ctypes import c_void_p
+
+    from .._lib import SV_BQ_MAX_RADII
+
+    require_cuda(xyz, "xyz")
+    B, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    x = xyz.to(torch.float32).contiguous()
+    q = new_xyz.to(torch.float32).contiguous()
+    outs = [torch.empty((B, S, k), dtype=torch.int64, device=xyz.device) for k in nsample_list]
+    for r0 in range(0, len(outs), SV_BQ_MAX_RADII):
+        rs = range(r0, min(r0 + SV_BQ_MAX_RADII, len(outs)))
+        call("sv_ball_query_multi", ptr(x), ptr(q), c_int(B), c_int(N), c_int(S), c_int(len(rs)),
+             (c_double * len(rs))(*[float(radius_list[r]) for r in rs]), (c_int * len(rs))(*[nsample_list[r] for r in rs]),
+             (c_void_p * len(rs))(*[outs[r].data_ptr() for r in rs]), stream_ptr())
+    return outs
 
 
 def index_points(points, idx):
@@ -83,8 +105,8 @@ from .._lib import SV_ACT_RELU  # noqa: E402
 
 
 def _fold_conv_bn(conv, bn):
-    """1x1 conv (+bias) followed by BatchNorm(eval) -> W[1,Cin,Cout], scale, shift with the conv bias folded in."""
-    w = conv.weight.detach().reshape(conv.out_channels, conv.in_channels).t().contiguous().unsqueeze(0)
+    """1x1 conv or Linear (+bias) followed by BatchNorm(eval) -> W[1,Cin,Cout], scale, shift with the bias folded in."""
+    w = conv.weight.detach().reshape(conv.weight.shape[0], -1).t().contiguous().unsqueeze(0)  # Conv 1x1 or Linear
     g = bn.weight.detach().float().cpu().numpy()
     b = bn.bias.detach().float().cpu().numpy()
     mean = bn.running_mean.detach().float().cpu().numpy()
@@ -223,6 +245,122 @@ class PointNetSetAbstraction(FoldCache):
             rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns, folds[0])
             pooled = rows.view(B, S, Kn, -1).max(dim=2)[0]
         return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)  # [B, D', S]
+
+
+def _group_msg(xyz, points, new_xyz, idx):
+    """[points[idx], xyz[idx] - new_xyz] -> [B, S, nsample, D + 3]: the multi-scale grouping's order, features first
+    (reference :245-250)."""
+    B, S, C = new_xyz.shape
+    grouped_xyz = index_points(xyz, idx) - new_xyz.view(B, S, 1, C)
+    return grouped_xyz if points is None else torch.cat([index_points(points, idx), grouped_xyz], dim=-1)
+
+
+class PointNetSetAbstractionMsg(FoldCache):
+    """Multi-scale grouping (reference :207-264): R radii around the same farthest-point centroids, one shared MLP per
+    radius, the pooled features concatenated.  Parameter names conv_blocks.i.j / bn_blocks.i.j as in the reference.  Eval
+    on the GPU: sv_fps, sv_ball_query_multi, then sv_pointnet_sa_msg (all scales in one launch); shapes the fused kernel
+    declines, or `fused = False`, run every scale's layers one launch each (sv_conv_fwd dense rows), torch.max and
+    torch.cat - the same bits."""
+
+    def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
+        super().__init__()
+        self.npoint = npoint
+        self.radius_list = list(radius_list)
+        self.nsample_list = list(nsample_list)
+        self.fused = True  # False: the unfused eval path (tests, timing)
+        self.conv_blocks = nn.ModuleList()
+        self.bn_blocks = nn.ModuleList()
+        for mlp in mlp_list:
+            convs, bns = nn.ModuleList(), nn.ModuleList()
+            last = in_channel + 3
+            for out in mlp:
+                convs.append(nn.Conv2d(last, out, 1))
+                bns.append(nn.BatchNorm2d(out))
+                last = out
+            self.conv_blocks.append(convs)
+            self.bn_blocks.append(bns)
+
+    def _folded(self):
+        """(per-scale layer folds, per-scale packed parameters, host arrays of sv_pointnet_sa_msg) - built once per
+        weights / device"""
+        from ctypes import c_void_p
+
+        def build():
+            folds = [[_fold_conv_bn(c, b) for c, b in zip(convs, bns)]
+                     for convs, bns in zip(self.conv_blocks, self.bn_blocks)]
+            packed = [torch.cat([t.reshape(-1).to(torch.float32) for f in fs for t in f]).contiguous() for fs in folds]
+            widths = [w for convs in self.conv_blocks for w in [convs[0].in_channels] + [c.out_channels for c in convs]]
+            R = len(folds)
+            host = ((c_int * R)(*self.nsample_list), (c_void_p * R)(*[p.data_ptr() for p in packed]),
+                    (c_int * len(widths))(*widths), (c_int * R)(*[len(convs) for convs in self.conv_blocks]))
+            return folds, packed, host
+
+        return self._fold_get(build)
+
+    def _fused(self, xyz, points, new_xyz, idxs, folds):
+        """sv_pointnet_sa_msg: every scale's gather + shared MLP + max in one launch -> [B, S, sum C_r], or None where the
+        kernel does not cover the shapes (SV_ERR_UNSUPPORTED: nothing was launched)."""
+        from ctypes import c_void_p
+
+        from .. import _lib
+
+        _, _, (nsamples, params, widths, nlayers) = folds
+        B, N, _ = xyz.shape
+        S = new_xyz.shape[1]
+        x = xyz.to(torch.float32).contiguous()
+        p = points.to(torch.float32).contiguous() if points is not None else None
+        D = p.shape[2] if p is not None else 0
+        q = new_xyz.to(torch.float32).contiguous()
+        R = len(idxs)
+        ctot = sum(convs[-1].out_channels for convs in self.conv_blocks)
+        out = torch.empty((B, S, ctot), dtype=torch.float32, device=xyz.device)
+        rc = _lib.load().sv_pointnet_sa_msg(ptr(x), ptr(p), ptr(q), B, N, D, S, R, nsamples,
+                                            (c_void_p * R)(*[t.data_ptr() for t in idxs]), params, widths, nlayers,
+                                            ptr(out), stream_ptr())
+        if rc == _lib.SV_ERR_UNSUPPORTED:
+            return None
+        _lib._check(rc, "sv_pointnet_sa_msg")
+        return out
+
+    def _unfused(self, xyz, points, new_xyz, idxs, folds):
+        """every scale: MSG-order gather, its layers one launch each (dense rows), torch.max; then torch.cat"""
+        pooled = []
+        for i, idx in enumerate(idxs):
+            grouped = _group_msg(xyz, points, new_xyz, idx)
+            B, S, Kn, C = grouped.shape
+            rows = _mlp_rows(grouped.reshape(B * S * Kn, C).contiguous(), self.conv_blocks[i], self.bn_blocks[i],
+                             folds[0][i])
+            pooled.append(rows.view(B, S, Kn, -1).max(dim=2)[0])
+        return torch.cat(pooled, dim=-1)
+
+    def forward(self, xyz, points, fps_start=None):
+        """xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points [B, sum C_r, S].  fps_start int64 [B] pins
+        the first farthest-point centroids (None: drawn as the reference draws them)."""
+        D = 0 if points is None else points.shape[1]
+        want = self.conv_blocks[0][0].in_channels - 3
+        if xyz.dim() != 3 or xyz.shape[1] != 3 or D != want:
+            raise ValueError(f"multi-scale set abstraction expects xyz [B, 3, N] and {want} point features, got "
+                             f"xyz {tuple(xyz.shape)} and {D} features")
+        xyz = xyz.permute(0, 2, 1)
+        if points is not None:
+            points = points.permute(0, 2, 1)
+        fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
+        new_xyz = index_points(xyz, fps_idx)
+        if self.training:  # the reference's torch path (:238-262)
+            pooled = []
+            for i, (radius, K) in enumerate(zip(self.radius_list, self.nsample_list)):
+                idx = query_ball_point(radius, K, xyz, new_xyz)
+                t = _group_msg(xyz, points, new_xyz, idx).permute(0, 3, 2, 1)
+                for conv, bn in zip(self.conv_blocks[i], self.bn_blocks[i]):
+                    t = F.relu(bn(conv(t)))
+                pooled.append(torch.max(t, 2)[0])
+            return new_xyz.permute(0, 2, 1), torch.cat(pooled, dim=1)
+        idxs = query_ball_point_multi(self.radius_list, self.nsample_list, xyz, new_xyz)
+        folds = self._folded()
+        pooled = self._fused(xyz, points, new_xyz, idxs, folds) if self.fused and xyz.is_cuda else None
+        if pooled is None:
+            pooled = self._unfused(xyz, points, new_xyz, idxs, folds)
+        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)
 
 
 def three_nn_interpolate(xyz1, xyz2, points2):

@@ -1,0 +1,263 @@
+"""PointNet++ multi-scale grouping on the GPU: sv_ball_query_multi against per-radius sv_ball_query, the fused multi-scale
+set abstraction (sv_pointnet_sa_msg) against the unfused eval path bit for bit, PointNet2MSGEncoder batching, and the
+reference pin (tests/golden/pointnet2_msg.npz, tools/make_golden.py pointnet2_msg)."""
+import hashlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pointnet2_msg.npz")
+# (N, npoint, radii, nsamples, in_channel, mlps) of PointNet2MSGEncoder's two multi-scale layers (model/pointnet2.py)
+MSG_SHAPES = [
+    (2048, 512, [0.1, 0.2, 0.4], [16, 32, 128], 3, [[32, 32, 64], [64, 64, 128], [64, 96, 128]]),
+    (512, 128, [0.2, 0.4, 0.8], [32, 64, 128], 320, [[64, 64, 128], [128, 128, 256], [128, 128, 256]]),
+]
+
+
+def _randomize(model, seed):
+    """conv / linear weights ~ N(0, 1/fan_in), BatchNorm affine and running statistics random (torch generator, CPU)"""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, (torch.nn.Conv1d, torch.nn.Conv2d, torch.nn.Linear)):
+                fan_in = m.weight[0].numel()
+                m.weight.copy_(torch.randn(m.weight.shape, generator=g) / fan_in ** 0.5)
+                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
+            elif isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+                n = m.num_features
+                m.weight.copy_(torch.rand(n, generator=g) * 0.5 + 0.75)
+                m.bias.copy_(torch.randn(n, generator=g) * 0.1)
+                m.running_mean.copy_(torch.randn(n, generator=g) * 0.1)
+                m.running_var.copy_(torch.rand(n, generator=g) * 0.5 + 0.75)
+
+
+def _same(a, b):
+    """bit-for-bit equal values, NaN where the other has NaN"""
+    na, nb = torch.isnan(a), torch.isnan(b)
+    return a.shape == b.shape and torch.equal(na, nb) and torch.equal(a[~na], b[~nb])
+
+
+@pytest.mark.parametrize("case", ["sa1", "sa2", "unsorted", "sparse", "duplicates"])
+def test_ball_query_multi_equals_per_radius_ball_query(gpu, case):
+    """sv_ball_query_multi: every radius's output is exactly sv_ball_query with that (radius, nsample) - both encoder
+    radius sets, unsorted radii, a sparse cloud whose balls are padded with the first hit, and duplicate points."""
+    from mrcc_amd.model.pointnet2_utils import query_ball_point, query_ball_point_multi
+
+    g = torch.Generator().manual_seed(7)
+    B, N, S = 2, 2048, 300
+    radii, ns = {"sa1": ([0.1, 0.2, 0.4], [16, 32, 128]), "sa2": ([0.2, 0.4, 0.8], [32, 64, 128]),
+                 "unsorted": ([0.4, 0.1, 0.8, 0.2], [128, 16, 64, 32]), "sparse": ([0.05, 0.3, 0.1], [64, 128, 16]),
+                 "duplicates": ([0.1, 0.2, 0.4], [16, 32, 128])}[case]
+    xyz = torch.rand(B, N, 3, generator=g) - 0.5
+    if case == "sparse":
+        xyz = xyz * 4.0
+    if case == "duplicates":
+        xyz[:, 500:700] = xyz[:, 3:4]
+        xyz[:, 1000:1100] = xyz[:, 900:1000]
+    xyz = xyz.to(gpu)
+    new_xyz = xyz[:, torch.randperm(N, generator=g)[:S].to(gpu)]
+    got = query_ball_point_multi(radii, ns, xyz, new_xyz)
+    padded = 0
+    for r, k, o in zip(radii, ns, got):
+        want = query_ball_point(r, k, xyz, new_xyz)
+        assert torch.equal(o, want), (r, k)
+        padded += int((want[..., -1] == want[..., 0]).sum())
+    assert padded > 0  # first-hit padding occurs in every case
+
+
+def _layer(gpu, shape, seed, B=2, S=None, D=None, N=None):
+    from mrcc_amd.model import pointnet2_utils as P2
+
+    N0, S0, radii, ns, cin, mlps = shape
+    N, S = N or N0, S or S0
+    D = cin if D is None else D
+    sa = P2.PointNetSetAbstractionMsg(S, radii, ns, D, mlps)
+    _randomize(sa, seed)
+    sa = sa.to(gpu).eval()
+    g = torch.Generator().manual_seed(seed)
+    xyz = ((torch.rand(B, 3, N, generator=g) - 0.5) * 0.8).to(gpu)
+    pts = torch.randn(B, D, N, generator=g).to(gpu) if D else None
+    start = torch.randint(0, N, (B,), generator=g).to(gpu)
+    return sa, xyz, pts, start
+
+
+def _fused_and_unfused(sa, xyz, pts, start):
+    with torch.no_grad():
+        sa.fused = True
+        nx, got = sa(xyz, pts, fps_start=start)
+        sa.fused = False
+        nx2, want = sa(xyz, pts, fps_start=start)
+        sa.fused = True
+    assert torch.equal(nx, nx2)
+    return got, want
+
+
+@pytest.mark.parametrize("layer", [0, 1])
+def test_fused_msg_layer_is_the_unfused_eval_path(gpu, layer):
+    """sv_pointnet_sa_msg on both encoder layers (nsample 16 / 32 / 128 and 32 / 64 / 128): bit-identical to the
+    per-scale gather in MSG order, dense-row layers, torch.max and torch.cat; and within fp32 rounding of an fp64
+    restatement of the reference's eval forward (model/pointnet2_utils.py:238-262)."""
+    import torch.nn.functional as F
+
+    from mrcc_amd.model import pointnet2_utils as P2
+
+    sa, xyz, pts, start = _layer(gpu, MSG_SHAPES[layer], 20 + layer)
+    got, want = _fused_and_unfused(sa, xyz, pts, start)
+    assert got.shape == (2, sum(m[-1] for m in MSG_SHAPES[layer][5]), sa.npoint)
+    assert torch.equal(got, want), (got - want).abs().max().item()
+    # fp64 reference arithmetic on the same groups
+    x, p = xyz.permute(0, 2, 1), pts.permute(0, 2, 1)
+    nx = P2.index_points(x, P2.farthest_point_sample(x, sa.npoint, start=start))
+    cols = []
+    for i, (r, k) in enumerate(zip(sa.radius_list, sa.nsample_list)):
+        t = P2._group_msg(x, p, nx, P2.query_ball_point(r, k, x, nx)).double().permute(0, 3, 2, 1)
+        for conv, bn in zip(sa.conv_blocks[i], sa.bn_blocks[i]):
+            t = F.relu(F.batch_norm(F.conv2d(t, conv.weight.double(), conv.bias.double()), bn.running_mean.double(),
+                                    bn.running_var.double(), bn.weight.double(), bn.bias.double(), False, 0.0, bn.eps))
+        cols.append(torch.max(t, 2)[0])
+    ref = torch.cat(cols, dim=1)
+    assert (got.double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+
+
+@pytest.mark.parametrize("S", [1, 3, 5])
+def test_fused_msg_tail_workgroups_and_no_features(gpu, S):
+    """S not a multiple of the 64 / nsample centroids a workgroup serves (nsample 16: 4, 32: 2), with D = 0 (points
+    NULL): bit-identical to the unfused path; the kernel alone writes nothing past B * S rows."""
+    from ctypes import c_void_p
+
+    from mrcc_amd._lib import load, ptr, stream_ptr
+    from mrcc_amd.model import pointnet2_utils as P2
+
+    shape = (600, S, [0.3, 0.15, 0.5], [16, 32, 128], 0, [[32, 48], [16, 32, 64], [32, 32]])
+    sa, xyz, pts, start = _layer(gpu, shape, 30 + S, B=1, D=0)
+    assert pts is None
+    got, want = _fused_and_unfused(sa, xyz, None, start)
+    assert torch.equal(got, want)
+    x = xyz.permute(0, 2, 1).contiguous()
+    nx = P2.index_points(x, P2.farthest_point_sample(x, S, start=start)).contiguous()
+    idxs = P2.query_ball_point_multi(sa.radius_list, sa.nsample_list, x, nx)
+    _, _, (nsamples, params, widths, nlayers) = sa._folded()
+    out = torch.full((S + 4, 48 + 64 + 32), -3.0, device=gpu)
+    rc = load().sv_pointnet_sa_msg(ptr(x), None, ptr(nx), 1, 600, 0, S, 3, nsamples,
+                                   (c_void_p * 3)(*[t.data_ptr() for t in idxs]), params, widths, nlayers, ptr(out),
+                                   stream_ptr())
+    assert rc == 0
+    assert torch.equal(out[:S].t()[None], want)
+    assert (out[S:] == -3.0).all()
+
+
+def test_fused_msg_propagates_nan(gpu):
+    """a NaN feature of one point reaches every pooled channel of the balls that hold it, through the two-pass max of
+    nsample 128 included - at the same places as the unfused path (torch.max propagates NaN)"""
+    sa, xyz, pts, start = _layer(gpu, MSG_SHAPES[0], 40, B=1)
+    pts = pts.clone()
+    pts[0, 1, 777] = float("nan")
+    got, want = _fused_and_unfused(sa, xyz, pts, start)
+    assert torch.isnan(got).any() and not torch.isnan(got).all()
+    assert _same(got, want)
+    # the 128-neighbour scale (columns 192..319) sees the NaN point from more centroids than the 16-neighbour one
+    assert torch.isnan(got[0, 192:]).any()
+
+
+def test_msg_encoder_batch_equals_single_clouds(gpu):
+    """PointNet2MSGEncoder at B = 4 equals four B = 1 forwards with the same starts, bit for bit."""
+    from mrcc_amd.model.pointnet2 import PointNet2MSGEncoder
+
+    torch.manual_seed(0)
+    net = PointNet2MSGEncoder(7)
+    _randomize(net, 1)
+    net = net.to(gpu).eval()
+    x = torch.cat([torch.rand(4, 3, 2048, device=gpu) - 0.5, torch.rand(4, 3, 2048, device=gpu) * 2 - 1], dim=1)
+    starts = torch.stack([torch.randint(0, n, (4,), device=gpu) for n in (2048, 512)])
+    with torch.no_grad():
+        out, l3 = net(x, fps_starts=starts)
+        assert out.shape == (4, 7) and l3.shape == (4, 1024, 1)
+        for b in range(4):
+            ob, l3b = net(x[b:b + 1], fps_starts=starts[:, b:b + 1])
+            assert torch.equal(ob[0], out[b]) and torch.equal(l3b[0], l3[b])
+
+
+def _golden_weights(sd, seed):
+    """tools/make_golden.py's MSG recipe: every state_dict tensor in sorted-key order from np.random.default_rng(seed)
+    -> the float32 values and the SHA-256 of their concatenated bytes"""
+    rng = np.random.default_rng(seed)
+    vals = {}
+    for k in sorted(sd):
+        if k.endswith("num_batches_tracked"):
+            continue
+        shape = tuple(sd[k].shape)
+        if k.endswith("running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        elif k.endswith("running_mean"):
+            v = rng.standard_normal(shape) * 0.1
+        elif ".bn_blocks." in k or ".mlp_bns." in k or k.startswith("bn"):
+            v = rng.uniform(0.75, 1.25, shape) if k.endswith("weight") else rng.standard_normal(shape) * 0.1
+        elif k.endswith("weight"):  # conv and fully connected weights
+            v = rng.standard_normal(shape) * 1.2 / np.sqrt(int(np.prod(shape[1:])))
+        else:  # conv and fully connected biases
+            v = rng.standard_normal(shape) * 0.1
+        vals[k] = v.astype(np.float32)
+    blob = b"".join(vals[k].tobytes() for k in sorted(vals))
+    return vals, hashlib.sha256(blob).digest()
+
+
+def _golden_net(g):
+    from mrcc_amd.model.pointnet2 import PointNet2MSGEncoder
+
+    net = PointNet2MSGEncoder(7)
+    sd = net.state_dict()
+    vals, digest = _golden_weights(sd, int(g["seed"]))
+    assert digest == g["weights_sha256"].tobytes()
+    net.load_state_dict({k: torch.from_numpy(vals[k]) if k in vals else sd[k] for k in sd})
+    return net
+
+
+def test_msg_encoder_matches_the_reference(gpu):
+    """The reference's PointNet2MSGEncoder(7) (eval, CPU) with regenerated weights (hash checked) and the recorded FPS
+    starts: FPS indices of sa1 and sa2 exact; the pooled features of the first centroids of sa1 / sa2, x and l3_points
+    within rtol = atol = 1e-4."""
+    from mrcc_amd.model import pointnet2_utils as P2
+
+    g = np.load(GOLDEN)
+    net = _golden_net(g).to(gpu).eval()
+    for i in range(int(g["n_cases"])):
+        x = torch.from_numpy(g[f"x{i}"]).to(gpu)
+        starts = torch.from_numpy(g[f"starts{i}"]).to(gpu)
+        with torch.no_grad():
+            xyz = x[:, :3].permute(0, 2, 1).contiguous()
+            fps1 = P2.farthest_point_sample(xyz, 512, start=starts[0])
+            assert np.array_equal(fps1.cpu().numpy(), g[f"fps1_{i}"].astype(np.int64))
+            l1_xyz, l1 = net.sa1(x[:, :3], x[:, 3:], fps_start=starts[0])
+            fps2 = P2.farthest_point_sample(l1_xyz.permute(0, 2, 1), 128, start=starts[1])
+            assert np.array_equal(fps2.cpu().numpy(), g[f"fps2_{i}"].astype(np.int64))
+            _, l2 = net.sa2(l1_xyz, l1, fps_start=starts[1])
+            out, l3 = net(x, fps_starts=starts)
+        np.testing.assert_allclose(l1[:, :, :8].cpu().numpy(), g[f"l1_head{i}"], rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(l2[:, :, :8].cpu().numpy(), g[f"l2_head{i}"], rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(l3.cpu().numpy(), g[f"l3_{i}"], rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(out.cpu().numpy(), g[f"out{i}"], rtol=1e-4, atol=1e-4)
+    assert np.abs(g["out1"][0] - g["out1"][1]).max() > 1e-2  # the outputs depend on the cloud: 1e-4 pins the signal
+
+
+def test_msg_encoder_loads_a_reference_state_dict(gpu):
+    """a state_dict with the reference's keys (the fixture's list, in the reference's order) loads with strict=True,
+    and the loaded encoder gives the same results as the one the tensors came from"""
+    from mrcc_amd.model.pointnet2 import PointNet2MSGEncoder
+
+    g = np.load(GOLDEN)
+    keys = g["state_dict_keys"].tobytes().decode().split("\n")
+    src = _golden_net(g)
+    sd = src.state_dict()
+    assert sorted(keys) == sorted(sd)
+    dst = PointNet2MSGEncoder(7)
+    dst.load_state_dict({k: sd[k].clone() for k in keys}, strict=True)
+    src, dst = src.to(gpu).eval(), dst.to(gpu).eval()
+    x = torch.from_numpy(g["x0"]).to(gpu)
+    starts = torch.from_numpy(g["starts0"]).to(gpu)
+    with torch.no_grad():
+        a, b = src(x, fps_starts=starts), dst(x, fps_starts=starts)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])

@@ -9,6 +9,7 @@ MinkowskiEngine is not installable here, so this build's own ME-shaped namespace
 get_pred_center and get_key_point_predictions, are pure torch/numpy and never touch ME.
 
     python tools/make_golden.py          # rewrites tests/golden/{kabsch,quat_avg,add,fps,ball_query,preprocess}.npz
+    python tools/make_golden.py pointnet2_msg    # only the named fixtures
 """
 import os
 import sys
@@ -358,13 +359,103 @@ def gen_pointnet2(rng):
     return out
 
 
+def _pointnet2_msg_weights(sd, seed):
+    """the MSG fixture's weight recipe (tests/test_gpu_pointnet2_msg.py restates it): _pointnet2_weights' distributions
+    with BatchNorm keys told apart by module ("bn_blocks" / "mlp_bns" / bn1, bn2) and every conv / fc weight
+    N(0, 1.44/fan_in); float32.  Returns (values, SHA-256 of the concatenated float32 bytes)."""
+    import hashlib
+
+    rng = np.random.default_rng(seed)
+    vals = {}
+    for k in sorted(sd):
+        if k.endswith("num_batches_tracked"):
+            continue
+        shape = tuple(sd[k].shape)
+        if k.endswith("running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        elif k.endswith("running_mean"):
+            v = rng.standard_normal(shape) * 0.1
+        elif ".bn_blocks." in k or ".mlp_bns." in k or k.startswith("bn"):
+            v = rng.uniform(0.75, 1.25, shape) if k.endswith("weight") else rng.standard_normal(shape) * 0.1
+        elif k.endswith("weight"):
+            v = rng.standard_normal(shape) * 1.2 / np.sqrt(int(np.prod(shape[1:])))
+        else:
+            v = rng.standard_normal(shape) * 0.1
+        vals[k] = v.astype(np.float32)
+    blob = b"".join(vals[k].tobytes() for k in sorted(vals))
+    return vals, hashlib.sha256(blob).hexdigest()
+
+
+def gen_pointnet2_msg(rng):
+    """model/pointnet2.py:46-77 PointNet2MSGEncoder(7) (normal_channel True), eval, CPU, with the seeded weights of
+    _pointnet2_msg_weights (not stored: the test regenerates them and checks the hash) on two seeded inputs [B, 6, 2048]
+    (B = 1, 2); every FPS start the reference draws (torch.randint, model/pointnet2_utils.py:77) recorded as starts
+    [2, B], the FPS indices of sa1 / sa2 (int16), the reference's state_dict keys, outputs x [B, 7] and l3_points [B, 1024, 1], and the pooled features of
+    the first 8 centroids of sa1 / sa2 (l1_head [B, 320, 8], l2_head [B, 640, 8]) to localise a difference.  Coordinates
+    span a 1 x 0.6 x 1.2 box, so the 0.1-radius balls hold a few points (first-hit padding) and the 0.4 / 0.8 ones are
+    full at 128."""
+    from model.pointnet2 import PointNet2MSGEncoder as RefMSG
+
+    def cloud(B):
+        xyz = rng.uniform(-0.5, 0.5, size=(B, 3, 2048)) * [[[1.0], [0.6], [1.2]]]
+        feat = rng.uniform(-1.0, 1.0, size=(B, 3, 2048))
+        return np.concatenate([xyz, feat], axis=1).astype(np.float32)
+
+    seed = 2025
+    net = RefMSG(7)
+    sd = net.state_dict()
+    vals, digest = _pointnet2_msg_weights(sd, seed)
+    net.load_state_dict({k: torch.from_numpy(vals[k]) if k in vals else sd[k] for k in sd})
+    net.eval()
+    # numbers only: the digest as its 32 bytes, the state_dict keys (in order) as the UTF-8 bytes of their "\n" join
+    out = dict(seed=np.int64(seed), weights_sha256=np.frombuffer(bytes.fromhex(digest), np.uint8), n_cases=np.int64(2),
+               state_dict_keys=np.frombuffer("\n".join(sd.keys()).encode(), np.uint8))
+    real_randint, real_fps = torch.randint, P2.farthest_point_sample
+    seen = {}
+    hooks = [net.sa1.register_forward_hook(lambda m, i, o: seen.__setitem__("l1", o[1])),
+             net.sa2.register_forward_hook(lambda m, i, o: seen.__setitem__("l2", o[1]))]
+    for i, B in enumerate((1, 2)):
+        x = cloud(B)
+        drawn, fps = [], []
+
+        def recording_randint(*args, **kwargs):
+            t = real_randint(*args, **kwargs)
+            drawn.append(t.clone())
+            return t
+
+        def recording_fps(*args, **kwargs):
+            t = real_fps(*args, **kwargs)
+            fps.append(t.clone())
+            return t
+
+        torch.manual_seed(600 + i)
+        torch.randint, P2.farthest_point_sample = recording_randint, recording_fps
+        try:
+            with torch.no_grad():
+                logits, l3 = net(torch.from_numpy(x))
+        finally:
+            torch.randint, P2.farthest_point_sample = real_randint, real_fps
+        assert len(drawn) == 2 and all(d.shape == (B,) for d in drawn) and len(fps) == 2
+        out[f"x{i}"] = x
+        out[f"starts{i}"] = torch.stack(drawn).numpy().astype(np.int64)
+        out[f"fps1_{i}"] = fps[0].numpy().astype(np.int16)
+        out[f"fps2_{i}"] = fps[1].numpy().astype(np.int16)
+        out[f"out{i}"] = logits.numpy().astype(np.float32)
+        out[f"l3_{i}"] = l3.numpy().astype(np.float32)
+        out[f"l1_head{i}"] = seen["l1"][:, :, :8].numpy().astype(np.float32)
+        out[f"l2_head{i}"] = seen["l2"][:, :, :8].numpy().astype(np.float32)
+    for h in hooks:
+        h.remove()
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
                            ("fps", gen_fps, 103), ("ball_query", gen_ball_query, 104),
                            ("preprocess", gen_preprocess, 105), ("metrics", gen_metrics, 106),
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
-                           ("pointnet2_ssg", gen_pointnet2, 109)]:
+                           ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))

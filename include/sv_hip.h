@@ -65,7 +65,7 @@ const char* sv_last_error(void);
  *    sv_conv_last_instance and sv_conv_fwd_acc (offset-range passes of one layer) added
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
- *    sv_key_point_predictions_batched */
+ *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -264,6 +264,28 @@ int sv_conv_fwd_bf16(const float* in, int64_t V_in, int64_t in_ld, int Cin, cons
                      const int32_t* perm, const int32_t* nbr_s, const uint32_t* submask, const int32_t* tile_order, int64_t V_out,
                      int64_t Vpad, const float* acc_init, int64_t acc_ld, const float* scale, const float* shift,
                      const float* residual, int64_t res_ld, int act, float slope, float* out, int64_t out_ld, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A3/A5 backward: the weight gradient of sv_conv_fwd's layers (training: the reference's train_segmentation.py,
+ *   train_vote.py, train.py and train_key_points.py call loss.backward() through ME.MinkowskiConvolution /
+ *   ConvolutionTranspose / Linear)
+ *
+ *   dW[k][c][n] (+)= sum over plan rows r with o = perm[r] >= 0 and i = nbr_s[k][r] >= 0 of  in[i][c] * dY[o][n]
+ * for the K offsets of the plan (the FORWARD's plan: perm / nbr_s / submask / Vpad exactly as sv_conv_fwd takes them; NULL
+ * = dense rows, i = o = r < V_out, K = 1).  `in` rows have stride in_ld, dY rows dy_ld (column slices of a cat buffer).
+ * submask lets a workgroup skip the 16-row sub-tiles without a pair at its offset.  The input gradient needs no entry of
+ * its own: it is sv_conv_fwd on dY with mirrored weights (offset 26 - k, transposed) on the same 3x3x3 plan, with W[k]^T
+ * on the up plan (down conv) or the down plan (transposed conv).
+ * Matrix op: v_mfma_f32_16x16x4_f32 (A = in^T, B = dY, reduction over pairs).  Every (chunk of plan tiles) writes its
+ * partial dW into the workspace (sv_conv_wgrad_workspace_bytes, monotone in Vpad); a second pass sums the partials in
+ * ascending chunk order and writes dW (accumulate = 0) or dW + that sum (accumulate != 0: the batch ranges of
+ * ConvPlan.chunks and the offset ranges of a split layer): no float atomics, the same bits on every run.
+ * V_out = 0 gives dW = 0 (unchanged when accumulating).  Plan arrays 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_conv_wgrad_workspace_bytes(int64_t Vpad, int K, int Cin, int Cout);
+int sv_conv_wgrad(const float* in, int64_t V_in, int64_t in_ld, int Cin, const float* dy, int64_t V_out, int64_t dy_ld,
+                  int Cout, int K, const int32_t* perm, const int32_t* nbr_s, const uint32_t* submask, int64_t Vpad,
+                  int accumulate, void* workspace, size_t workspace_bytes, float* dW, sv_stream_t stream);
 
 /* Stand-alone BN(eval)/bias + residual + activation on feature rows, same arithmetic as the conv epilogue:
  *   out[v][c] = act( fmaf(in[v][c], scale[c], shift[c]) + residual[v][c] )

@@ -40,6 +40,8 @@ class _PoseHeadMixin:
         )
 
     def _regress(self, feats, joint_angles):
+        if self.training:
+            return self._regress_train(feats, joint_angles)
         scale, shift = self.output_layer[0].folded()
         feats = feats.new(svnn.affine_act(feats.F, scale, shift, act=SV_ACT_RELU))
         pooled = self.global_pool(feats).features
@@ -51,6 +53,17 @@ class _PoseHeadMixin:
         if not self.training:
             out[:, 3:7] = F.normalize(out[:, 3:7], p=2, dim=1)
         return out
+
+
+    def _regress_train(self, feats, joint_angles):
+        """_regress as differentiable ops (train()): BN + ReLU, torch segment pooling, the MLP on the autograd dense path"""
+        feats = self.relu(self.output_layer[0](feats))
+        pooled = self.global_pool(feats).features
+        if self.use_joint_angles:
+            pooled = torch.cat((pooled, joint_angles.to(pooled)), dim=1)
+        h = svnn.linear_train(self.pose_regression[0], pooled, SV_ACT_LEAKY_RELU, self.pose_regression[1].negative_slope)
+        out = svnn.linear_train(self.pose_regression[2], h)
+        return torch.cat((out[:, :7], torch.sigmoid(out[:, 7:])), dim=1)  # confidences
 
 
 def make_robotnet(backbone=None):

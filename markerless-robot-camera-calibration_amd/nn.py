@@ -1,5 +1,9 @@
 """nn.Module layers with MinkowskiEngine's names, parameters and state_dict layout, running on
-libsvhip.so.  Inference only: the forward pass needs eval() BatchNorm (running statistics), there is no backward.
+libsvhip.so.  The path is chosen by each module's own `training` flag: in eval() a conv -> BN -> residual -> activation
+chain is ONE fused launch with detached weights (no graph, the bits of the oracle); in train() the conv / linear layers
+run as a torch.autograd.Function (SparseConvFunction: forward sv_conv_fwd, backward sv_conv_fwd on mirrored weights for
+the input gradient and sv_conv_wgrad for the weight gradient) and BN (batch statistics), residual, activation and cat
+follow as differentiable torch ops.
 
 state_dict keys match ME 0.5.4 so utils/utils.py:87-126 checkpoint_restore-style loading works unchanged:
   MinkowskiConvolution(.Transpose): `kernel` [K, Cin, Cout] ([Cin, Cout] when K == 1), `bias` [1, Cout]
@@ -9,7 +13,7 @@ Kernel-offset order inside `kernel` is this build's definition (include/sv_hip.h
 single hook for adapting a real ME checkpoint if its order turns out to differ.
 """
 import math
-from ctypes import c_float, c_int, c_int64
+from ctypes import c_float, c_int, c_int64, c_size_t
 
 import numpy as np
 import torch
@@ -161,6 +165,105 @@ def _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, 
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# backward: weight gradient (sv_conv_wgrad) and the autograd Function of a conv / linear layer
+# ------------------------------------------------------------------------------------------------------------------
+def _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, accumulate):
+    Vpad = (plan.Vpad if plan is not None
+            else (max(V_out, 1) + _lib.SV_TILE_ROWS - 1) // _lib.SV_TILE_ROWS * _lib.SV_TILE_ROWS)
+    nbytes = _lib.load().sv_conv_wgrad_workspace_bytes(c_int64(Vpad), c_int(K), c_int(Cin), c_int(Cout))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dy.device)
+    call("sv_conv_wgrad", ptr(feats), c_int64(feats.shape[0]), c_int64(feats.stride(0)), c_int(Cin), ptr(dy),
+         c_int64(V_out), c_int64(dy.stride(0)), c_int(Cout), c_int(K), ptr(plan.perm if plan else None),
+         ptr(plan.nbr_s if plan else None), ptr(plan.submask if plan else None), c_int64(Vpad), c_int(1 if accumulate else 0),
+         ptr(ws), c_size_t(nbytes), ptr(dW), stream_ptr())
+
+
+def conv_wgrad(feats, dy, plan, K, Cin, Cout):
+    """dW[k][c][n] = sum over the plan's (in i, out o) pairs at offset k of feats[i][c] * dy[o][n] (sv_conv_wgrad), the
+    forward's plan: a SplitPlan writes each offset range's block, batch ranges (ConvPlan.chunks) accumulate."""
+    if feats.stride(1) != 1:
+        feats = feats.contiguous()
+    if dy.stride(1) != 1:
+        dy = dy.contiguous()
+    V_out = dy.shape[0]
+    dW = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dy.device)
+    if isinstance(plan, SplitPlan):
+        for k0, k1, sub in plan.parts:
+            _wgrad_plan(feats, dy, sub, k1 - k0, Cin, Cout, V_out, dW[k0:k1])
+    else:
+        _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW)
+    return dW
+
+
+def _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW):
+    parts = plan.chunks(4 * feats.stride(0), 4 * dy.stride(0)) if plan is not None else None
+    if parts is None:
+        _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, False)
+        return
+    for j, (sub, i0, i1, o0, o1) in enumerate(parts):  # batch ranges: partial sums of the same offsets
+        _wgrad_one(feats[i0:i1], dy[o0:o1], sub, K, Cin, Cout, o1 - o0, dW, j > 0)
+
+
+class SparseConvFunction(torch.autograd.Function):
+    """out = conv(feats, W) + bias on `plan` (sv_conv_fwd, no epilogue).  Backward, all fp32:
+      dX = sv_conv_fwd(dY, W', grad_plan)   W'[k] = W[26 - k]^T on the 3x3x3 plan itself (offset 26 - k is the negation of
+               offset k), W[k]^T on the up plan of a down conv / the down plan of a transposed conv / dense rows;
+      dW = sv_conv_wgrad(feats, dY, plan);   d bias = column sum of dY.
+    grad_plan: a callable giving the input-gradient plan (built only when the input needs a gradient)."""
+
+    @staticmethod
+    def forward(ctx, feats, weight3, bias, plan, V_out, grad_plan, mirror):
+        w = weight3.detach()
+        if not w.is_contiguous():
+            w = w.contiguous()
+        shift = bias.detach().reshape(-1) if bias is not None else None
+        out = conv_forward(feats.detach(), w, plan, V_out, None, shift)
+        ctx.save_for_backward(feats, w)
+        ctx.plan, ctx.grad_plan, ctx.mirror = plan, grad_plan, mirror
+        ctx.bias_shape = bias.shape if bias is not None else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        feats, w = ctx.saved_tensors
+        K, Cin, Cout = w.shape
+        if dy.stride(1) != 1:
+            dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wt = (w.flip(0) if ctx.mirror else w).transpose(1, 2).contiguous()
+            dx = conv_forward(dy, wt, ctx.grad_plan(), feats.shape[0])
+        if ctx.needs_input_grad[1]:
+            dw = conv_wgrad(feats.detach(), dy, ctx.plan, K, Cin, Cout)
+        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
+            db = dy.sum(0).reshape(ctx.bias_shape)
+        return dx, dw, db, None, None, None, None
+
+
+def sparse_conv(feats, weight3, bias, plan, V_out, grad_plan, mirror=False):
+    """differentiable sparse conv / linear layer (SparseConvFunction); weight3 [K, Cin, Cout] may be a view of the
+    parameter (Linear: weight^T), its gradient flows back through the view"""
+    return SparseConvFunction.apply(feats, weight3, bias, plan, V_out, grad_plan, mirror)
+
+
+def _act_torch(x, act, slope):
+    if act == SV_ACT_RELU:
+        return torch.relu(x)
+    if act == SV_ACT_LEAKY_RELU:
+        return torch.nn.functional.leaky_relu(x, slope)
+    return x
+
+
+def linear_train(linear, x, act=SV_ACT_NONE, slope=0.01):
+    """nn.Linear(x) (+ activation) on the autograd dense path: the weight gradient in sv_conv_wgrad, the input gradient
+    in sv_conv_fwd - no torch GEMM"""
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    out = sparse_conv(x, linear.weight.t().unsqueeze(0), linear.bias, None, x.shape[0], lambda: None)
+    return _act_torch(out, act, slope)
+
+
 def affine_act(feats, scale=None, shift=None, residual=None, act=SV_ACT_NONE, slope=0.01):
     V, C = feats.shape
     if feats.stride(1) != 1:
@@ -186,6 +289,25 @@ def global_pool(x, mode):
     call("sv_global_pool", ptr(F), c_int64(F.stride(0)), c_int(C), ptr(bs), c_int(B), c_int(mode), ptr(out),
          stream_ptr())
     return out
+
+
+def global_pool_train(x, mode):
+    """global_pool as differentiable torch segment reductions over the batch ranges (training): amax (NaN propagates, a
+    tie shares the gradient) / mean; an empty batch gives 0 as the kernel does"""
+    cm = x.coordinate_manager
+    if cm.num_batches is None:
+        m = x.coordinate_map
+        cm.num_batches = int(m.coords[:, 0].max().item()) + 1 if m.V else 1
+    bounds = cm.batch_bounds(x.tensor_stride)
+    F = x.F
+    rows = []
+    for b in range(len(bounds) - 1):
+        seg = F[bounds[b]:bounds[b + 1]]
+        if seg.shape[0] == 0:
+            rows.append(F.new_zeros(F.shape[1]))
+        else:
+            rows.append(seg.amax(0) if mode == _lib.SV_POOL_MAX else seg.mean(0))
+    return torch.stack(rows)
 
 
 def fold_bn(bn):
@@ -336,10 +458,39 @@ class _ConvBase(_Bf16Weights, nn.Module):
         raise NotImplementedError(
             f"kernel_size={ks} stride={st} transposed={self.transposed}: not used by the reference's U-Nets")
 
+    def _grad_plan(self, x, plan):
+        """plan of the input gradient (a forward conv from the output map back to the input map): the 3x3x3 map is its
+        own mirror, a down conv's is the up map of the coarse level, a transposed conv's the down map of the fine one"""
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        if self.kernel_size == 2 and self.stride == 2:
+            return lambda: cm.plan_down(ts // 2) if self.transposed else cm.plan_up(ts * 2)
+        return lambda: plan
+
+    def forward_train(self, x, bn=None, residual=None, act=SV_ACT_NONE, slope=0.01, cat_with=None):
+        """forward_fused's graph as differentiable ops: the autograd conv, then BN (batch statistics in train(),
+        running statistics in eval()), + residual, activation, ME.cat"""
+        plan, out_stride = self._plan(x)
+        V_out = x.coordinate_manager.stride_map(out_stride).V
+        mirror = self.kernel_size == 3
+        out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, self._grad_plan(x, plan), mirror)
+        if bn is not None:
+            out = bn.bn(out)
+        if residual is not None:
+            out = out + (residual.F if isinstance(residual, SparseTensor) else residual)
+        out = _act_torch(out, act, slope)
+        if cat_with is not None:
+            if cat_with.coordinate_manager is not x.coordinate_manager or cat_with.tensor_stride != out_stride:
+                raise ValueError("ME.cat needs tensors on the same coordinate map")
+            out = torch.cat([out, cat_with.F], dim=1)
+        return x.new(out, tensor_stride=out_stride)
+
     def forward_fused(self, x, bn=None, residual=None, act=SV_ACT_NONE, slope=0.01, cat_with=None):
         """conv (+ folded BN / bias) (+ residual) (+ activation) in one launch.  cat_with: a SparseTensor on the
         output's coordinate map - the result is ME.cat(conv(x), cat_with) (model/backbone/minkunet.py:152-156), with
-        the conv writing straight into the left columns of the concatenated buffer instead of being copied there."""
+        the conv writing straight into the left columns of the concatenated buffer instead of being copied there.
+        In train() (this module's or its BN's) the same graph runs as differentiable ops (forward_train)."""
+        if self.training or (bn is not None and bn.training):
+            return self.forward_train(x, bn, residual, act, slope, cat_with)
         plan, out_stride = self._plan(x)
         V_out = x.coordinate_manager.stride_map(out_stride).V
         scale = shift = None
@@ -409,6 +560,10 @@ class MinkowskiBatchNorm(nn.Module):
         return self._folded
 
     def forward(self, x):
+        # ME's BN: nn.BatchNorm1d on the features - batch statistics and running-stat update in train(); frozen (eval)
+        # statistics on features that carry a graph stay differentiable (F.batch_norm with the running statistics)
+        if self.training or (x.F.requires_grad and torch.is_grad_enabled()):
+            return x.new(self.bn(x.F))
         scale, shift = self.folded()
         return x.new(affine_act(x.F, scale, shift))
 
@@ -418,6 +573,8 @@ class MinkowskiReLU(nn.Module):
         super().__init__()
 
     def forward(self, x):
+        if self.training:
+            return x.new(torch.relu(x.F)) if isinstance(x, SparseTensor) else torch.relu(x)
         if isinstance(x, SparseTensor):
             return x.new(affine_act(x.F, act=SV_ACT_RELU))
         return affine_act(x, act=SV_ACT_RELU)
@@ -429,6 +586,9 @@ class MinkowskiLeakyReLU(nn.Module):
         self.negative_slope = negative_slope
 
     def forward(self, x):
+        if self.training:
+            f = torch.nn.functional.leaky_relu
+            return (x.new(f(x.F, self.negative_slope)) if isinstance(x, SparseTensor) else f(x, self.negative_slope))
         if isinstance(x, SparseTensor):
             return x.new(affine_act(x.F, act=SV_ACT_LEAKY_RELU, slope=self.negative_slope))
         return affine_act(x, act=SV_ACT_LEAKY_RELU, slope=self.negative_slope)
@@ -461,6 +621,9 @@ class MinkowskiLinear(_Bf16Weights, nn.Module):
 
     def forward_fused(self, x, act=SV_ACT_NONE, slope=0.01):
         F = x.F if isinstance(x, SparseTensor) else x
+        if self.training:
+            out = linear_train(self.linear, F, act, slope)
+            return x.new(out) if isinstance(x, SparseTensor) else out
         shift = self.linear.bias.detach() if self.linear.bias is not None else None
         wp = self._weight_bf16()
         bf16 = {} if wp is None else {"weight_bf16": wp}  # fp32 layers: the call conv_forward always got
@@ -473,11 +636,15 @@ class MinkowskiLinear(_Bf16Weights, nn.Module):
 
 class MinkowskiGlobalMaxPooling(nn.Module):
     def forward(self, x):
+        if self.training:
+            return PooledTensor(global_pool_train(x, _lib.SV_POOL_MAX))
         return PooledTensor(global_pool(x, _lib.SV_POOL_MAX))
 
 
 class MinkowskiGlobalAvgPooling(nn.Module):
     def forward(self, x):
+        if self.training:
+            return PooledTensor(global_pool_train(x, _lib.SV_POOL_AVG))
         return PooledTensor(global_pool(x, _lib.SV_POOL_AVG))
 
 

@@ -556,6 +556,8 @@ class SparseTensor:
             if coordinate_manager is None:
                 raise ValueError("either coordinates or a coordinate_manager is required")
             self._F = features.to(device=device, dtype=torch.float32).contiguous()
+            if requires_grad and self._F.is_leaf:
+                self._F.requires_grad_(True)
             self.coordinate_manager = coordinate_manager
             self.tensor_stride = tensor_stride
             self.inverse_mapping = None
@@ -571,6 +573,8 @@ class SparseTensor:
         mode = (_lib.SV_REDUCE_MEAN if quantization_mode == SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE
                 else _lib.SV_REDUCE_FIRST)
         self._F = _voxel_reduce(feats, order, seg_start, cmap.V, mode)
+        if requires_grad:  # ME: the voxel features are a leaf of the graph; .F.grad holds dX after backward()
+            self._F.requires_grad_(True)
         self.coordinate_manager = cm
         self.tensor_stride = 1
         self.inverse_mapping = inverse

@@ -65,7 +65,8 @@ const char* sv_last_error(void);
  *    sv_conv_last_instance and sv_conv_fwd_acc (offset-range passes of one layer) added
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
- *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad */
+ *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
+ *    sv_conv_wgrad_bf16 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -286,6 +287,20 @@ size_t sv_conv_wgrad_workspace_bytes(int64_t Vpad, int K, int Cin, int Cout);
 int sv_conv_wgrad(const float* in, int64_t V_in, int64_t in_ld, int Cin, const float* dy, int64_t V_out, int64_t dy_ld,
                   int Cout, int K, const int32_t* perm, const int32_t* nbr_s, const uint32_t* submask, int64_t Vpad,
                   int accumulate, void* workspace, size_t workspace_bytes, float* dW, sv_stream_t stream);
+
+/* sv_conv_wgrad at reduced precision (the opt-in bf16 training mode: nn.set_training_precision):
+ *   dW[k][c][n] (+)= sum over plan rows r with o = perm[r] >= 0 and i = nbr_s[k][r] >= 0 of  bf16(in[i][c]) * bf16(dY[o][n])
+ * operands rounded to bf16 (round to nearest even, NaN stays NaN) when they are staged, products summed in fp32 by
+ * v_mfma_f32_16x16x32_bf16 (32 pairs = two 16-row sub-tiles of the plan per matrix op; the live sub-tiles are paired in plan
+ * order, a lone last one with zeros).  Same arguments, plans, accumulate, V_out = 0 and determinism as sv_conv_wgrad (per-chunk
+ * partials summed in ascending chunk order, no float atomics; an absent pair zeroes both operands), with a workspace of its
+ * own (sv_conv_wgrad_bf16_workspace_bytes, monotone in Vpad).  Returns SV_ERR_UNSUPPORTED, before looking at any pointer,
+ * unless Cin % 16 == 0, Cout % 16 == 0 and K <= 27, and (after the argument checks) unless in and dy are 16-byte aligned
+ * with in_ld % 4 == 0 and dy_ld % 4 == 0: the caller then uses sv_conv_wgrad. */
+size_t sv_conv_wgrad_bf16_workspace_bytes(int64_t Vpad, int K, int Cin, int Cout);
+int sv_conv_wgrad_bf16(const float* in, int64_t V_in, int64_t in_ld, int Cin, const float* dy, int64_t V_out, int64_t dy_ld,
+                       int Cout, int K, const int32_t* perm, const int32_t* nbr_s, const uint32_t* submask, int64_t Vpad,
+                       int accumulate, void* workspace, size_t workspace_bytes, float* dW, sv_stream_t stream);
 
 /* Stand-alone BN(eval)/bias + residual + activation on feature rows, same arithmetic as the conv epilogue:
  *   out[v][c] = act( fmaf(in[v][c], scale[c], shift[c]) + residual[v][c] )

@@ -70,6 +70,11 @@ SIGNATURES = {
         c_int,
         [_P, c_int64, c_int64, c_int, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, c_int64, c_int, _P, c_size_t, _P, _P],
     ),
+    "sv_conv_wgrad_bf16_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "sv_conv_wgrad_bf16": (
+        c_int,
+        [_P, c_int64, c_int64, c_int, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, c_int64, c_int, _P, c_size_t, _P, _P],
+    ),
     "sv_conv_last_instance": (c_char_p, []),
     "sv_conv_set_dispatch": (c_int, [c_double, c_double]),
     "sv_frame_maps_arena_bytes": (c_size_t, [c_int64, c_int]),

@@ -103,7 +103,7 @@ def _conv_forward_split(feats, weight3, plan, V_out, scale, shift, residual, act
         kname = profiling.conv_kernel_config(Cout, plan.Vpad, Cin, plan.parts[-1][1] - plan.parts[-1][0])
         if timer.want(kname):
             t0 = timer.start()
-    if not weight3.is_contiguous():
+    if weight_bf16 is None and not weight3.is_contiguous():
         weight3 = weight3.contiguous()  # a pass takes the block W[k0:k1] by pointer
     acc = None
     for i, (k0, k1, sub) in enumerate(plan.parts):  # timed=False: the passes are ONE layer for the per-kernel table
@@ -168,59 +168,90 @@ def _conv_forward_one(feats, weight3, plan, V_out, scale, shift, residual, act, 
 # ------------------------------------------------------------------------------------------------------------------
 # backward: weight gradient (sv_conv_wgrad) and the autograd Function of a conv / linear layer
 # ------------------------------------------------------------------------------------------------------------------
-def _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, accumulate):
+def _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, accumulate, bf16=False):
+    """one sv_conv_wgrad (bf16: sv_conv_wgrad_bf16, or sv_conv_wgrad where it returns SV_ERR_UNSUPPORTED) launch;
+    returns the entry point that ran"""
     Vpad = (plan.Vpad if plan is not None
             else (max(V_out, 1) + _lib.SV_TILE_ROWS - 1) // _lib.SV_TILE_ROWS * _lib.SV_TILE_ROWS)
-    nbytes = _lib.load().sv_conv_wgrad_workspace_bytes(c_int64(Vpad), c_int(K), c_int(Cin), c_int(Cout))
+    lib = _lib.load()
+    fn = "sv_conv_wgrad_bf16" if bf16 else "sv_conv_wgrad"
+    nbytes = getattr(lib, fn + "_workspace_bytes")(c_int64(Vpad), c_int(K), c_int(Cin), c_int(Cout))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dy.device)
-    call("sv_conv_wgrad", ptr(feats), c_int64(feats.shape[0]), c_int64(feats.stride(0)), c_int(Cin), ptr(dy),
-         c_int64(V_out), c_int64(dy.stride(0)), c_int(Cout), c_int(K), ptr(plan.perm if plan else None),
-         ptr(plan.nbr_s if plan else None), ptr(plan.submask if plan else None), c_int64(Vpad), c_int(1 if accumulate else 0),
-         ptr(ws), c_size_t(nbytes), ptr(dW), stream_ptr())
+    rc = getattr(lib, fn)(ptr(feats), c_int64(feats.shape[0]), c_int64(feats.stride(0)), c_int(Cin), ptr(dy),
+                          c_int64(V_out), c_int64(dy.stride(0)), c_int(Cout), c_int(K), ptr(plan.perm if plan else None),
+                          ptr(plan.nbr_s if plan else None), ptr(plan.submask if plan else None), c_int64(Vpad),
+                          c_int(1 if accumulate else 0), ptr(ws), c_size_t(nbytes), ptr(dW), stream_ptr())
+    if bf16 and rc == _lib.SV_ERR_UNSUPPORTED:  # channel counts / row alignment the bf16 kernel does not cover
+        return _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, accumulate)
+    _lib._check(rc, fn)
+    return fn
 
 
-def conv_wgrad(feats, dy, plan, K, Cin, Cout):
+def conv_wgrad(feats, dy, plan, K, Cin, Cout, bf16=False, used=None):
     """dW[k][c][n] = sum over the plan's (in i, out o) pairs at offset k of feats[i][c] * dy[o][n] (sv_conv_wgrad), the
-    forward's plan: a SplitPlan writes each offset range's block, batch ranges (ConvPlan.chunks) accumulate."""
+    forward's plan: a SplitPlan writes each offset range's block, batch ranges (ConvPlan.chunks) accumulate.
+    bf16: operands rounded to bf16, products summed in fp32 (sv_conv_wgrad_bf16; sv_conv_wgrad where it does not cover
+    the shape).  used: a set that receives the entry points that ran."""
     if feats.stride(1) != 1:
         feats = feats.contiguous()
     if dy.stride(1) != 1:
         dy = dy.contiguous()
     V_out = dy.shape[0]
     dW = torch.empty((K, Cin, Cout), dtype=torch.float32, device=dy.device)
+    used = set() if used is None else used
     if isinstance(plan, SplitPlan):
         for k0, k1, sub in plan.parts:
-            _wgrad_plan(feats, dy, sub, k1 - k0, Cin, Cout, V_out, dW[k0:k1])
+            _wgrad_plan(feats, dy, sub, k1 - k0, Cin, Cout, V_out, dW[k0:k1], bf16, used)
     else:
-        _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW)
+        _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW, bf16, used)
     return dW
 
 
-def _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW):
+def _wgrad_plan(feats, dy, plan, K, Cin, Cout, V_out, dW, bf16=False, used=None):
+    used = set() if used is None else used
     parts = plan.chunks(4 * feats.stride(0), 4 * dy.stride(0)) if plan is not None else None
     if parts is None:
-        _wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, False)
+        used.add(_wgrad_one(feats, dy, plan, K, Cin, Cout, V_out, dW, False, bf16))
         return
     for j, (sub, i0, i1, o0, o1) in enumerate(parts):  # batch ranges: partial sums of the same offsets
-        _wgrad_one(feats[i0:i1], dy[o0:o1], sub, K, Cin, Cout, o1 - o0, dW, j > 0)
+        used.add(_wgrad_one(feats[i0:i1], dy[o0:o1], sub, K, Cin, Cout, o1 - o0, dW, j > 0, bf16))
+
+
+def _bf16_fwd_ok(rows, Cin, Cout, K):
+    """what sv_conv_fwd_bf16 covers: bf16_eligible's channel rule, input rows 16-byte aligned"""
+    return (Cin % 32 == 0 and Cin >= 64 and Cout % 16 == 0 and Cout >= 64 and K <= 27
+            and rows.data_ptr() % 16 == 0 and rows.stride(0) % 4 == 0)
+
+
+def _train_log(layer, op, fn):
+    log = profiling.TRAIN_LOG
+    if log is not None:
+        log.append((layer, op, fn))
 
 
 class SparseConvFunction(torch.autograd.Function):
-    """out = conv(feats, W) + bias on `plan` (sv_conv_fwd, no epilogue).  Backward, all fp32:
+    """out = conv(feats, W) + bias on `plan` (sv_conv_fwd, no epilogue).  Backward, fp32:
       dX = sv_conv_fwd(dY, W', grad_plan)   W'[k] = W[26 - k]^T on the 3x3x3 plan itself (offset 26 - k is the negation of
                offset k), W[k]^T on the up plan of a down conv / the down plan of a transposed conv / dense rows;
       dW = sv_conv_wgrad(feats, dY, plan);   d bias = column sum of dY.
-    grad_plan: a callable giving the input-gradient plan (built only when the input needs a gradient)."""
+    grad_plan: a callable giving the input-gradient plan (built only when the input needs a gradient).
+    layer: the conv / linear module (None: a plain nn.Linear).  When its training_precision is "bf16" the forward runs on
+    sv_conv_fwd_bf16 (bias as the fp32 shift), dX on sv_conv_fwd_bf16 with W' packed (where the swapped shape Cin' = Cout,
+    Cout' = Cin is one sv_conv_fwd_bf16 covers) and dW on sv_conv_wgrad_bf16 (sv_conv_wgrad where it returns
+    SV_ERR_UNSUPPORTED); activations and gradients stay fp32 in memory, d bias stays the fp32 column sum."""
 
     @staticmethod
-    def forward(ctx, feats, weight3, bias, plan, V_out, grad_plan, mirror):
+    def forward(ctx, feats, weight3, bias, plan, V_out, grad_plan, mirror, layer=None):
         w = weight3.detach()
         if not w.is_contiguous():
             w = w.contiguous()
+        bf16 = layer is not None and layer._train_bf16()
         shift = bias.detach().reshape(-1) if bias is not None else None
-        out = conv_forward(feats.detach(), w, plan, V_out, None, shift)
+        wp = layer.packed_weights_bf16() if bf16 and _bf16_fwd_ok(feats, w.shape[1], w.shape[2], w.shape[0]) else None
+        out = conv_forward(feats.detach(), w, plan, V_out, None, shift, weight_bf16=wp)
+        _train_log(layer, "fwd", "sv_conv_fwd_acc" if wp is None else "sv_conv_fwd_bf16")
         ctx.save_for_backward(feats, w)
-        ctx.plan, ctx.grad_plan, ctx.mirror = plan, grad_plan, mirror
+        ctx.plan, ctx.grad_plan, ctx.mirror, ctx.layer, ctx.bf16 = plan, grad_plan, mirror, layer, bf16
         ctx.bias_shape = bias.shape if bias is not None else None
         return out
 
@@ -232,19 +263,30 @@ class SparseConvFunction(torch.autograd.Function):
             dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            wt = (w.flip(0) if ctx.mirror else w).transpose(1, 2).contiguous()
-            dx = conv_forward(dy, wt, ctx.grad_plan(), feats.shape[0])
+            # bf16 only where sv_conv_fwd_bf16 gets a column block of >= 128 channels (Cin % 128 or % 192 == 0): the
+            # 416 / 448-wide decoder inputs split into 32 / 64-wide blocks that gather dY 13 / 7 times
+            if ctx.bf16 and _bf16_fwd_ok(dy, Cout, Cin, K) and (Cin % 128 == 0 or Cin % 192 == 0):
+                dx = conv_forward(dy, w.transpose(1, 2), ctx.grad_plan(), feats.shape[0],
+                                  weight_bf16=ctx.layer.packed_grad_weights_bf16(ctx.mirror))
+                _train_log(ctx.layer, "dx", "sv_conv_fwd_bf16")
+            else:
+                wt = (w.flip(0) if ctx.mirror else w).transpose(1, 2).contiguous()
+                dx = conv_forward(dy, wt, ctx.grad_plan(), feats.shape[0])
+                _train_log(ctx.layer, "dx", "sv_conv_fwd_acc")
         if ctx.needs_input_grad[1]:
-            dw = conv_wgrad(feats.detach(), dy, ctx.plan, K, Cin, Cout)
+            used = set()
+            dw = conv_wgrad(feats.detach(), dy, ctx.plan, K, Cin, Cout, bf16=ctx.bf16, used=used)
+            _train_log(ctx.layer, "dw", "+".join(sorted(used)))
         if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
             db = dy.sum(0).reshape(ctx.bias_shape)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
-def sparse_conv(feats, weight3, bias, plan, V_out, grad_plan, mirror=False):
+def sparse_conv(feats, weight3, bias, plan, V_out, grad_plan, mirror=False, layer=None):
     """differentiable sparse conv / linear layer (SparseConvFunction); weight3 [K, Cin, Cout] may be a view of the
-    parameter (Linear: weight^T), its gradient flows back through the view"""
-    return SparseConvFunction.apply(feats, weight3, bias, plan, V_out, grad_plan, mirror)
+    parameter (Linear: weight^T), its gradient flows back through the view.  layer: the module whose training_precision
+    selects the kernels (None = fp32)"""
+    return SparseConvFunction.apply(feats, weight3, bias, plan, V_out, grad_plan, mirror, layer)
 
 
 def _act_torch(x, act, slope):
@@ -255,12 +297,13 @@ def _act_torch(x, act, slope):
     return x
 
 
-def linear_train(linear, x, act=SV_ACT_NONE, slope=0.01):
+def linear_train(linear, x, act=SV_ACT_NONE, slope=0.01, layer=None):
     """nn.Linear(x) (+ activation) on the autograd dense path: the weight gradient in sv_conv_wgrad, the input gradient
-    in sv_conv_fwd - no torch GEMM"""
+    in sv_conv_fwd - no torch GEMM.  layer: the MinkowskiLinear that owns `linear` (its training_precision applies);
+    None for a plain nn.Linear, which trains fp32"""
     if x.stride(1) != 1:
         x = x.contiguous()
-    out = sparse_conv(x, linear.weight.t().unsqueeze(0), linear.bias, None, x.shape[0], lambda: None)
+    out = sparse_conv(x, linear.weight.t().unsqueeze(0), linear.bias, None, x.shape[0], lambda: None, layer=layer)
     return _act_torch(out, act, slope)
 
 
@@ -347,20 +390,33 @@ def bf16_eligible(m):
     return cin % 32 == 0 and cin >= 64 and cout % 16 == 0 and cout >= 64 and kv <= 27
 
 
-def set_compute_precision(module, precision):
-    """Mark the conv / linear layers of `module` (itself included) for `precision`: "bf16" marks exactly the layers
-    bf16_eligible() accepts (the rest stay fp32), "fp32" marks every layer fp32 (the default).  Returns the qualified
-    names of the layers that now run at `precision`.  Parameters and state_dict are untouched."""
+def _mark_precision(module, precision, attr, what):
     if precision not in PRECISIONS:
-        raise ValueError(f"compute precision must be one of {PRECISIONS}, got {precision!r}")
+        raise ValueError(f"{what} precision must be one of {PRECISIONS}, got {precision!r}")
     marked = []
     for name, m in module.named_modules():
         if isinstance(m, (_ConvBase, MinkowskiLinear)):
             p = precision if precision == "fp32" or bf16_eligible(m) else "fp32"
-            m.compute_precision = p
+            setattr(m, attr, p)
             if p == precision:
                 marked.append(name)
     return marked
+
+
+def set_training_precision(module, precision):
+    """set_compute_precision's twin for train(): "bf16" marks exactly the layers bf16_eligible() accepts for the bf16
+    training path (forward and input gradient on sv_conv_fwd_bf16, weight gradient on sv_conv_wgrad_bf16; activations,
+    gradients, BN, residual adds, activations, cat and pooling stay fp32), "fp32" marks every layer fp32 (the default).
+    Returns the qualified names of the layers that now train at `precision`.  Independent of set_compute_precision (which
+    affects eval() alone); parameters and state_dict are untouched."""
+    return _mark_precision(module, precision, "training_precision", "training")
+
+
+def set_compute_precision(module, precision):
+    """Mark the conv / linear layers of `module` (itself included) for `precision`: "bf16" marks exactly the layers
+    bf16_eligible() accepts (the rest stay fp32), "fp32" marks every layer fp32 (the default).  Returns the qualified
+    names of the layers that now run at `precision`.  Parameters and state_dict are untouched."""
+    return _mark_precision(module, precision, "compute_precision", "compute")
 
 
 class _Bf16Weights:
@@ -381,6 +437,24 @@ class _Bf16Weights:
         if self.compute_precision != "bf16":
             raise ValueError(f"compute precision must be one of {PRECISIONS}, got {self.compute_precision!r}")
         return self.packed_weights_bf16()
+
+    def _train_bf16(self):
+        """whether this layer trains on the bf16 kernels (set_training_precision)"""
+        p = self.__dict__.get("training_precision", "fp32")
+        if p not in PRECISIONS:
+            raise ValueError(f"training precision must be one of {PRECISIONS}, got {p!r}")
+        return p == "bf16" and bf16_eligible(self)
+
+    def packed_grad_weights_bf16(self, mirror):
+        """W' of the input gradient, (W flipped over the offsets if mirror)^T packed for sv_conv_fwd_bf16, cached and
+        re-packed when the weight changes (an optimizer steps it in place)"""
+        weight = self.kernel if isinstance(self, _ConvBase) else self.linear.weight
+        ver = (_tensor_versions(weight), mirror)
+        if self.__dict__.get("_wpt") is None or self.__dict__.get("_wpt_ver") != ver:
+            w = self.weight3().detach()
+            self._wpt = pack_weights_bf16((w.flip(0) if mirror else w).transpose(1, 2).contiguous())
+            self._wpt_ver = ver
+        return self._wpt
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -403,6 +477,7 @@ class _ConvBase(_Bf16Weights, nn.Module):
             self.kernel = nn.Parameter(torch.empty(in_channels, out_channels))
         self.bias = nn.Parameter(torch.empty(1, out_channels)) if bias else None
         self.compute_precision = "fp32"  # "bf16": sv_conv_fwd_bf16 (set_compute_precision)
+        self.training_precision = "fp32"  # "bf16": the bf16 kernels in train() (set_training_precision)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -472,7 +547,7 @@ class _ConvBase(_Bf16Weights, nn.Module):
         plan, out_stride = self._plan(x)
         V_out = x.coordinate_manager.stride_map(out_stride).V
         mirror = self.kernel_size == 3
-        out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, self._grad_plan(x, plan), mirror)
+        out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, self._grad_plan(x, plan), mirror, layer=self)
         if bn is not None:
             out = bn.bn(out)
         if residual is not None:
@@ -607,6 +682,7 @@ class MinkowskiLinear(_Bf16Weights, nn.Module):
         self._wt = None
         self._wt_ver = None
         self.compute_precision = "fp32"  # "bf16": sv_conv_fwd_bf16 (set_compute_precision)
+        self.training_precision = "fp32"  # "bf16": the bf16 kernels in train() (set_training_precision)
 
     def weight3(self):
         """[1, Cin, Cout] view of linear.weight^T, cached (the kernel wants W[k][c][n])."""
@@ -622,7 +698,7 @@ class MinkowskiLinear(_Bf16Weights, nn.Module):
     def forward_fused(self, x, act=SV_ACT_NONE, slope=0.01):
         F = x.F if isinstance(x, SparseTensor) else x
         if self.training:
-            out = linear_train(self.linear, F, act, slope)
+            out = linear_train(self.linear, F, act, slope, layer=self)
             return x.new(out) if isinstance(x, SparseTensor) else out
         shift = self.linear.bias.detach() if self.linear.bias is not None else None
         wp = self._weight_bf16()

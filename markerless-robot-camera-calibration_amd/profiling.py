@@ -12,6 +12,11 @@ TIMER = None  # set by bench.py
 # Optional list: nn.conv_forward appends (instance name, {"fast", "ring", "full"}, K, Cin, Cout, rows) per launch, as
 # reported by the library itself (sv_conv_last_instance) - tests check which instances a configuration really ran on.
 INSTANCE_LOG = None
+# Optional list: every op of a training step's conv / linear layers (nn.SparseConvFunction) appends (layer, op, entry
+# point): layer = the module (None for a plain nn.Linear through nn.linear_train), op "fwd" / "dx" / "dw", entry point the
+# library function that ran it ("sv_conv_fwd_acc" / "sv_conv_fwd_bf16" for fwd and dx, "sv_conv_wgrad" / "sv_conv_wgrad_bf16"
+# for dw) - tests check which layers a training precision really put on the bf16 kernels.
+TRAIN_LOG = None
 
 _CANDIDATES = {
     "wide3": [(64, 4, 3, 2500), (32, 4, 3, 1500), (32, 2, 3, 0)],

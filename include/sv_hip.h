@@ -66,7 +66,7 @@ const char* sv_last_error(void);
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
- *    sv_conv_wgrad_bf16 */
+ *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -482,6 +482,48 @@ int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, 
 int sv_pointnet_sa_msg(const float* xyz, const float* points, const float* new_xyz, int B, int N, int D, int S, int R,
                        const int* nsamples, const int64_t* const* group_idx, const float* const* params,
                        const int* widths, const int* nlayers, float* out, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A9  PointNet++ training (set_training_path "hip"): the gather, pooling and interpolation around the shared-MLP GEMMs
+ *     and their backward.  No float atomics: every result is bit-reproducible.
+ * ------------------------------------------------------------------------------------------- */
+/* The grouped rows of a set abstraction, row (b, s, k) = (b * S + s) * nsample + k of out float32[B*S*nsample][ld], with
+ * i = idx[b][s][k]: order SV_GROUP_SSG [xyz[b][i] - new_xyz[b][s], points[b][i]] (model/pointnet2_utils.py:131-137),
+ * SV_GROUP_MSG [points[b][i], xyz[b][i] - new_xyz[b][s]] (:245-250).  Columns 3 + D .. ld - 1 are written 0.  idx NULL is
+ * sample_and_group_all (:143-160): S = 1, nsample = N, row k = [xyz[b][k], points[b][k]], no subtraction, SSG order,
+ * new_xyz unused.  points NULL when D = 0.  The bits of torch's index_points and subtraction. */
+#define SV_GROUP_SSG 0
+#define SV_GROUP_MSG 1
+int sv_group_rows(const float* xyz, const float* points, const float* new_xyz, const int64_t* idx, int B, int N, int D,
+                  int S, int nsample, int order, int ld, float* out, sv_stream_t stream);
+/* Inverse of an index table idx[B][M] (int32 or int64 by idx_bytes) with values in [0, N): target t = b * N + idx[b][m]
+ * is referenced by the positions pos[offsets[t] .. offsets[t + 1]) (position p = b * M + m), ascending per target.
+ * offsets int32[B*N + 1], pos int32[B*M]; entries outside [0, N) are dropped (they sort behind every target).  The
+ * stable radix sort of sv_sort.hip on key = target, value = position.  workspace: sv_index_transpose_workspace_bytes. */
+size_t sv_index_transpose_workspace_bytes(int B, int64_t M, int N);
+int sv_index_transpose(const void* idx, int idx_bytes, int B, int64_t M, int N, void* workspace, size_t workspace_bytes,
+                       int32_t* offsets, int32_t* pos, sv_stream_t stream);
+/* out[t][c] = sum over p in pos[offsets[t] .. offsets[t + 1]) ascending of w[p] * rows[p / per_row][col0 + c] (w NULL:
+ * 1), for t < T and c < C; every target is written (0 where nothing references it).  rows row stride ld_rows, out
+ * [T][ld_out].  The backward of sv_group_rows over the point-feature columns (per_row 1) and of sv_three_nn_gather with
+ * the 3-NN weights (per_row 3); it replaces the atomic scatter of index_points' backward. */
+int sv_gather_transpose(const int32_t* offsets, const int32_t* pos, const float* w, const float* rows, int64_t ld_rows,
+                        int col0, int C, int per_row, int64_t T, float* out, int64_t ld_out, sv_stream_t stream);
+/* Max over every group of nsample consecutive rows (torch.max(t, 2) of the set abstraction, :203 / :258):
+ * out[g][c] = max over k of rows[g * nsample + k][c], arg[g][c] = its k; torch's max(dim) rule: the first NaN wins, a tie
+ * goes to the lowest k.  rows row stride ld; out float32[G][C], arg int32[G][C].  group_all is G = B, nsample = N. */
+int sv_group_max(const float* rows, int64_t ld, int64_t G, int nsample, int C, float* out, int32_t* arg,
+                 sv_stream_t stream);
+/* drows float32[G*nsample][C] = dpooled[g][c] at k = arg[g][c], 0 elsewhere: every element written in one pass. */
+int sv_group_max_backward(const float* dpooled, const int32_t* arg, int64_t G, int nsample, int C, float* drows,
+                          sv_stream_t stream);
+/* The search and weights of sv_three_nn_interpolate written out (:298-305): idx int32[B][N][3] nearest first, w float32
+ * [B][N][3] normalised 1 / (d + 1e-8); same float32 distance, tie rule and weight arithmetic, S >= 3. */
+int sv_three_nn(const float* xyz1, const float* xyz2, int B, int N, int S, int32_t* idx, float* w, sv_stream_t stream);
+/* out[b][n][c] = (points2[b][i0][c] * w0 + points2[b][i1][c] * w1) + points2[b][i2][c] * w2 with sv_three_nn's idx / w:
+ * the bits of sv_three_nn_interpolate.  points2 [B][S][C], out [B][N][C]. */
+int sv_three_nn_gather(const float* points2, const int32_t* idx, const float* w, int B, int N, int S, int C, float* out,
+                       sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  largest single-linkage cluster of the end-effector points

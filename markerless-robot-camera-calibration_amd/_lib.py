@@ -21,6 +21,7 @@ SV_ERR_UNSUPPORTED = -5
 SV_PN_MAX_LAYERS = 4
 SV_PN_MAX_SCALES = 4
 SV_BQ_MAX_RADII = 4
+SV_GROUP_SSG, SV_GROUP_MSG = 0, 1
 SV_COORD_BIAS = 1 << 17
 SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
@@ -111,6 +112,14 @@ SIGNATURES = {
     "sv_pointnet_sa": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P]),
     "sv_ball_query_multi": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "sv_pointnet_sa_msg": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_group_rows": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "sv_index_transpose_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    "sv_index_transpose": (c_int, [_P, c_int, c_int, c_int64, c_int, _P, c_size_t, _P, _P, _P]),
+    "sv_gather_transpose": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int64, _P, c_int64, _P]),
+    "sv_group_max": (c_int, [_P, c_int64, c_int64, c_int, c_int, _P, _P, _P]),
+    "sv_group_max_backward": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),
+    "sv_three_nn": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "sv_three_nn_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 _lib = None

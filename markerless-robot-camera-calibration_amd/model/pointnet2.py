@@ -3,17 +3,21 @@ config/override_inference_test.yaml:97).  SA 1024/256/64/16 centroids (radii .1/
 propagation stages, 1x1 conv head.
 PointNet2MSGEncoder: the pose regressor of STRUCTURE.backbone = pointnet2 with encode_only (model/pointnet2.py:46-77,
 train.py:259-263): two multi-scale set abstractions (512 / 128 centroids, three radii each), a group-all one, three
-fully connected layers.  Same attribute names as the reference -> same state_dict keys."""
+fully connected layers.  Same attribute names as the reference -> same state_dict keys.
+set_training_path(model, "hip") (re-exported from pointnet2_utils): train() on the HIP kernels."""
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import nn as svnn
 from .._lib import SV_ACT_NONE, SV_ACT_RELU
-from .pointnet2_utils import (FoldCache, PointNetFeaturePropagation, PointNetSetAbstraction,
-                              PointNetSetAbstractionMsg, _fold_conv_bn)
+from .pointnet2_utils import (FoldCache, PointNetFeaturePropagation, PointNetSetAbstraction,  # noqa: F401
+                              PointNetSetAbstractionMsg, _fold_conv_bn, _hip_train, bn_rows_train, conv_rows_train,
+                              set_training_path)
 
 
 class PointNet2SSG(FoldCache):
+    _hip_trainable = True  # set_training_path: the conv1 / bn1 / conv2 head
+
     def __init__(self, num_classes=10, in_channels=3):
         super().__init__()
         self.sa1 = PointNetSetAbstraction(1024, 0.1, 32, in_channels + 3, [32, 32, 64], False)
@@ -45,6 +49,13 @@ class PointNet2SSG(FoldCache):
         x = svnn.conv_forward(x, w2, None, B * N, None, b2, None, SV_ACT_NONE)
         return x.view(B, N, -1)
 
+    def _head_train(self, l0_points):
+        """train() head on the HIP path, rows [B*N, C]: conv1 / conv2 on sv_conv_fwd, bn1 as F.batch_norm -> [B, N, classes]"""
+        B, C, N = l0_points.shape
+        rows = l0_points.permute(0, 2, 1).reshape(B * N, C)
+        x = self.drop1(F.relu(bn_rows_train(self.bn1, conv_rows_train(rows, self.conv1))))
+        return conv_rows_train(x, self.conv2).view(B, N, -1)
+
     def forward(self, xyz, fps_starts=None):
         """xyz [B, in_channels, N] with the coordinates in the first three channels -> ([B, N, classes], l4 features).
         fps_starts int64 [4, B]: the first farthest-point centroid of every set abstraction (None: drawn as the reference
@@ -61,12 +72,16 @@ class PointNet2SSG(FoldCache):
         l0_points = self.fp1(l0_xyz, l1_xyz, None, l1_points)
         if not self.training and l0_points.is_cuda:
             return self._head(l0_points), l4_points
+        if _hip_train(self):
+            return self._head_train(l0_points), l4_points
         x = self.drop1(F.relu(self.bn1(self.conv1(l0_points))))
         x = self.conv2(x)
         return x.permute(0, 2, 1), l4_points
 
 
 class PointNet2MSGEncoder(FoldCache):
+    _hip_trainable = True  # set_training_path: the fc1 / fc2 / fc3 head
+
     def __init__(self, num_class, normal_channel=True):
         super().__init__()
         in_channel = 3 if normal_channel else 0
@@ -99,6 +114,12 @@ class PointNet2MSGEncoder(FoldCache):
         x = svnn.conv_forward(x, w2, None, B, s2, h2, None, SV_ACT_RELU)
         return svnn.conv_forward(x, w3, None, B, None, b3, None, SV_ACT_NONE)
 
+    def _head_train(self, x):
+        """train() head on the HIP path: fc1 / fc2 / fc3 on sv_conv_fwd, bn1 / bn2 as F.batch_norm -> [B, num_class]"""
+        x = self.drop1(F.relu(bn_rows_train(self.bn1, conv_rows_train(x, self.fc1))))
+        x = self.drop2(F.relu(bn_rows_train(self.bn2, conv_rows_train(x, self.fc2))))
+        return conv_rows_train(x, self.fc3)
+
     def forward(self, xyz, fps_starts=None):
         """xyz [B, 6, N] (coordinates, then normals; [B, 3, N] with normal_channel False) -> (x [B, num_class],
         l3_points [B, 1024, 1]).  fps_starts int64 [2, B]: the first farthest-point centroid of sa1 and sa2 (None: drawn
@@ -117,6 +138,8 @@ class PointNet2MSGEncoder(FoldCache):
         x = l3_points.reshape(B, 1024)
         if not self.training and x.is_cuda:
             return self._head(x), l3_points
+        if _hip_train(self):
+            return self._head_train(x), l3_points
         x = self.drop1(F.relu(self.bn1(self.fc1(x))))
         x = self.drop2(F.relu(self.bn2(self.fc2(x))))
         return self.fc3(x), l3_points

@@ -4,8 +4,10 @@ farthest_point_sample(xyz [B,N,3], npoint) -> int64 [B,npoint]     reference :65
 query_ball_point(radius, nsample, xyz, new_xyz) -> int64 [B,S,nsample]   reference :89-109 ([B,S,N] matrix + sort)
 query_ball_point_multi(radii, nsamples, xyz, new_xyz) -> R of those      one scan for a multi-scale layer's radii
 index_points, square_distance: thin torch helpers with the reference's semantics (:21-62).
+set_training_path(model, "torch" | "hip"): which kernels the set abstraction / feature propagation layers and the
+PointNet++ heads train on (default "torch": the reference's torch expressions).
 """
-from ctypes import c_double, c_int
+from ctypes import c_double, c_int, c_int64
 
 import torch
 
@@ -101,7 +103,7 @@ import torch.nn as nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from .. import nn as svnn  # noqa: E402
-from .._lib import SV_ACT_RELU  # noqa: E402
+from .._lib import SV_ACT_RELU, SV_GROUP_MSG, SV_GROUP_SSG  # noqa: E402
 
 
 def _fold_conv_bn(conv, bn):
@@ -159,6 +161,228 @@ class FoldCache(nn.Module):
         return super()._load_from_state_dict(*args, **kwargs)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# training on libsvhip (set_training_path(model, "hip")): the grouped rows, the max over a group and the
+# 3-NN interpolation are HIP kernels with fixed-order backwards (no atomics: bit-reproducible gradients); the shared
+# MLPs stay rows [B*S*nsample, C] from the gather to the max, every 1x1 conv / linear layer on sv_conv_fwd /
+# sv_conv_wgrad (nn.sparse_conv dense rows), BatchNorm as F.batch_norm on the rows, ReLU / Dropout torch ops.
+# Coordinates are not differentiated: a call whose coordinates require grad runs the torch path (recorded).
+# ----------------------------------------------------------------------------------------------------------------------
+TRAINING_PATHS = ("torch", "hip")
+
+
+def set_training_path(model, path):
+    """Mark every PointNetSetAbstraction(Msg) / PointNetFeaturePropagation of `model` (itself included) and the heads of
+    PointNet2SSG / PointNet2MSGEncoder to train on `path`: "torch" (the default, the reference's torch expressions) or
+    "hip".  Affects train() alone (eval() keeps the fused kernels); a plain attribute, not in state_dict, kept by .to(),
+    load_state_dict and train() / eval().  Returns the qualified names of the modules it switched."""
+    if path not in TRAINING_PATHS:
+        raise ValueError(f"training path must be one of {TRAINING_PATHS}, got {path!r}")
+    names = []
+    for name, m in model.named_modules():
+        if getattr(type(m), "_hip_trainable", False):
+            m.training_path = path
+            names.append(name)
+    return names
+
+
+def _hip_train(module, *coords):
+    """whether this call of `module` trains on the HIP path; coordinates that require grad take the torch path for the
+    call, counted in module.train_fallbacks and recorded in profiling.TRAIN_LOG as (module, "fallback", "torch")"""
+    if not module.training or module.__dict__.get("training_path", "torch") != "hip":
+        return False
+    if any(c is not None and c.requires_grad for c in coords):
+        module.__dict__["train_fallbacks"] = module.__dict__.get("train_fallbacks", 0) + 1
+        svnn._train_log(module, "fallback", "torch")
+        return False
+    return True
+
+
+def _csr(idx, N, module):
+    """sv_index_transpose: (offsets int32 [B*N + 1], pos int32 [B*M]) of the index table idx [B, ...] (values in [0, N))"""
+    from .. import _lib
+
+    B = idx.shape[0]
+    M = idx.numel() // max(B, 1)
+    lib = _lib.load()
+    nbytes = lib.sv_index_transpose_workspace_bytes(B, M, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=idx.device)
+    offsets = torch.empty(B * N + 1, dtype=torch.int32, device=idx.device)
+    pos = torch.empty(max(B * M, 1), dtype=torch.int32, device=idx.device)
+    _lib._check(lib.sv_index_transpose(ptr(idx), idx.element_size(), B, M, N, ptr(ws), nbytes, ptr(offsets), ptr(pos),
+                                       stream_ptr()), "sv_index_transpose")
+    svnn._train_log(module, "index_transpose", "sv_index_transpose")
+    return offsets, pos
+
+
+def _gather_transpose(csr, w, rows, col0, C, per_row, T, module):
+    """out [T, C]: out[t] = sum over the CSR positions p of target t (ascending) of w[p] * rows[p / per_row, col0:col0+C]"""
+    offsets, pos = csr
+    out = torch.empty((T, C), dtype=torch.float32, device=rows.device)
+    call("sv_gather_transpose", ptr(offsets), ptr(pos), ptr(w), ptr(rows), c_int64(rows.stride(0)), c_int(col0), c_int(C),
+         c_int(per_row), c_int64(T), ptr(out), c_int64(C), stream_ptr())
+    svnn._train_log(module, "gather_transpose", "sv_gather_transpose")
+    return out
+
+
+class GroupRowsFunction(torch.autograd.Function):
+    """rows [B*S*nsample, 3 + D] = sv_group_rows (order SV_GROUP_SSG / SV_GROUP_MSG; idx None: group_all).  Backward to
+    the point features only: the CSR of idx (sv_index_transpose, built once) and sv_gather_transpose over the feature
+    columns; group_all's rows hold every point once, so its gradient is the column slice."""
+
+    @staticmethod
+    def forward(ctx, points, xyz, new_xyz, idx, order, module):
+        from .._lib import SV_GROUP_SSG
+
+        B, N, _ = xyz.shape
+        S, K = (1, N) if idx is None else (idx.shape[1], idx.shape[2])
+        D = 0 if points is None else points.shape[2]
+        x = xyz.detach().to(torch.float32).contiguous()
+        p = points.detach().contiguous() if points is not None else None
+        q = new_xyz.detach().to(torch.float32).contiguous() if idx is not None else None
+        out = torch.empty((B * S * K, 3 + D), dtype=torch.float32, device=xyz.device)
+        call("sv_group_rows", ptr(x), ptr(p), ptr(q), ptr(idx), c_int(B), c_int(N), c_int(D), c_int(S), c_int(K),
+             c_int(order), c_int(3 + D), ptr(out), stream_ptr())
+        svnn._train_log(module, "group_rows", "sv_group_rows")
+        ctx.save_for_backward(idx)
+        ctx.shape, ctx.col0, ctx.module = (B, N, D), (3 if order == SV_GROUP_SSG else 0), module
+        return out
+
+    @staticmethod
+    def backward(ctx, drows):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        (idx,) = ctx.saved_tensors
+        B, N, D = ctx.shape
+        if drows.stride(1) != 1:
+            drows = drows.contiguous()
+        if idx is None:  # group_all: row (b, k) = [xyz[b][k], points[b][k]]
+            dp = drows.view(B, N, 3 + D)[:, :, 3:]
+        else:
+            dp = _gather_transpose(_csr(idx, N, ctx.module), None, drows, ctx.col0, D, 1, B * N, ctx.module).view(B, N, D)
+        return dp, None, None, None, None, None
+
+
+class GroupMaxFunction(torch.autograd.Function):
+    """pooled [G, C] = max over every group of nsample consecutive rows (sv_group_max: the first NaN wins, a tie goes to
+    the lowest row); backward: the dense row gradient, dPooled at the argmax, in one pass (sv_group_max_backward)"""
+
+    @staticmethod
+    def forward(ctx, rows, nsample, module):
+        R, C = rows.shape
+        if rows.stride(1) != 1:
+            rows = rows.contiguous()
+        G = R // nsample
+        out = torch.empty((G, C), dtype=torch.float32, device=rows.device)
+        arg = torch.empty((G, C), dtype=torch.int32, device=rows.device)
+        call("sv_group_max", ptr(rows), c_int64(rows.stride(0)), c_int64(G), c_int(nsample), c_int(C), ptr(out), ptr(arg),
+             stream_ptr())
+        svnn._train_log(module, "group_max", "sv_group_max")
+        ctx.save_for_backward(arg)
+        ctx.nsample, ctx.module = nsample, module
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dpooled, _darg):
+        (arg,) = ctx.saved_tensors
+        G, C = arg.shape
+        dp = dpooled.contiguous()
+        drows = torch.empty((G * ctx.nsample, C), dtype=torch.float32, device=dp.device)
+        call("sv_group_max_backward", ptr(dp), ptr(arg), c_int64(G), c_int(ctx.nsample), c_int(C), ptr(drows),
+             stream_ptr())
+        svnn._train_log(ctx.module, "group_max_backward", "sv_group_max_backward")
+        return drows, None, None
+
+
+class ThreeNNGatherFunction(torch.autograd.Function):
+    """out [B, N, C] = (p2[i0] * w0 + p2[i1] * w1) + p2[i2] * w2 (sv_three_nn_gather: sv_three_nn_interpolate's bits);
+    backward to points2: the CSR of idx (sv_index_transpose) and sv_gather_transpose with the weights"""
+
+    @staticmethod
+    def forward(ctx, points2, idx, w, module):
+        B, N, _ = idx.shape
+        S, C = points2.shape[1], points2.shape[2]
+        p2 = points2.detach().contiguous()
+        out = torch.empty((B, N, C), dtype=torch.float32, device=p2.device)
+        call("sv_three_nn_gather", ptr(p2), ptr(idx), ptr(w), c_int(B), c_int(N), c_int(S), c_int(C), ptr(out),
+             stream_ptr())
+        svnn._train_log(module, "three_nn_gather", "sv_three_nn_gather")
+        ctx.save_for_backward(idx, w)
+        ctx.S, ctx.module = S, module
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        idx, w = ctx.saved_tensors
+        B, N, _ = idx.shape
+        d = dout.contiguous().view(B * N, -1)
+        dp2 = _gather_transpose(_csr(idx, ctx.S, ctx.module), w, d, 0, d.shape[1], 3, B * ctx.S, ctx.module)
+        return dp2.view(B, ctx.S, -1), None, None, None
+
+
+def group_rows(xyz, points, new_xyz, idx, order, module=None):
+    """differentiable sv_group_rows (gradient to `points` only) -> rows [B*S*nsample, 3 + D]"""
+    if points is not None and points.dtype != torch.float32:
+        points = points.to(torch.float32)
+    return GroupRowsFunction.apply(points, xyz, new_xyz, idx, order, module)
+
+
+def group_max(rows, nsample, module=None):
+    """differentiable sv_group_max -> [R / nsample, C] (the argmax indices are kept for the backward)"""
+    return GroupMaxFunction.apply(rows, nsample, module)[0]
+
+
+def three_nn(xyz1, xyz2, module=None):
+    """sv_three_nn: (idx int32 [B, N, 3], w float32 [B, N, 3]) of the 3-NN interpolation of xyz2 onto xyz1"""
+    B, N, _ = xyz1.shape
+    S = xyz2.shape[1]
+    x1, x2 = (t.detach().to(torch.float32).contiguous() for t in (xyz1, xyz2))
+    idx = torch.empty((B, N, 3), dtype=torch.int32, device=x1.device)
+    w = torch.empty((B, N, 3), dtype=torch.float32, device=x1.device)
+    call("sv_three_nn", ptr(x1), ptr(x2), c_int(B), c_int(N), c_int(S), ptr(idx), ptr(w), stream_ptr())
+    svnn._train_log(module, "three_nn", "sv_three_nn")
+    return idx, w
+
+
+def three_nn_gather(points2, idx, w, module=None):
+    """differentiable sv_three_nn_gather (gradient to points2)"""
+    if points2.dtype != torch.float32:
+        points2 = points2.to(torch.float32)
+    return ThreeNNGatherFunction.apply(points2, idx, w, module)
+
+
+def conv_rows_train(rows, layer):
+    """1x1 Conv1d / Conv2d or Linear on rows [R, Cin] -> [R, Cout]: nn.sparse_conv dense rows (forward sv_conv_fwd, dX
+    sv_conv_fwd with W^T, dW sv_conv_wgrad, d bias a column sum); the gradient flows back through the weight's view.
+    profiling.TRAIN_LOG records its ops as (layer, "fwd" / "dx" / "dw", entry point)."""
+    if rows.stride(1) != 1:
+        rows = rows.contiguous()
+    w = layer.weight.view(layer.weight.shape[0], -1).t().unsqueeze(0)
+    return svnn.sparse_conv(rows, w, layer.bias, None, rows.shape[0], lambda: None, layer=layer)
+
+
+def bn_rows_train(bn, rows):
+    """BatchNorm1d / BatchNorm2d.forward on rows [R, C] (what the module computes on [B, C, ...] with R = the product of
+    the other dimensions): the same num_batches_tracked / momentum=None bookkeeping, F.batch_norm with its parameters"""
+    eaf = 0.0 if bn.momentum is None else bn.momentum
+    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+        eaf = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+    batch_stats = bn.training or (bn.running_mean is None and bn.running_var is None)
+    keep = not bn.training or bn.track_running_stats
+    return F.batch_norm(rows, bn.running_mean if keep else None, bn.running_var if keep else None, bn.weight, bn.bias,
+                        batch_stats, eaf, bn.eps)
+
+
+def _mlp_rows_train(rows, convs, bns):
+    for conv, bn in zip(convs, bns):
+        rows = F.relu(bn_rows_train(bn, conv_rows_train(rows, conv)))
+    return rows
+
+
 def sample_and_group_all(xyz, points):
     B, N, C = xyz.shape
     new_xyz = torch.zeros(B, 1, C, device=xyz.device)
@@ -168,6 +392,8 @@ def sample_and_group_all(xyz, points):
 
 
 class PointNetSetAbstraction(FoldCache):
+    _hip_trainable = True  # set_training_path
+
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
         super().__init__()
         self.npoint, self.radius, self.nsample, self.group_all = npoint, radius, nsample, group_all
@@ -215,6 +441,8 @@ class PointNetSetAbstraction(FoldCache):
     def forward(self, xyz, points, fps_start=None):
         """xyz [B,3,N], points [B,D,N] -> new_xyz [B,3,S], new_points [B,D',S].  fps_start int64 [B] pins the first
         farthest-point centroids (None: drawn as the reference draws them, torch.randint on the device)."""
+        if _hip_train(self, xyz):
+            return self._train_hip(xyz, points, fps_start)
         xyz = xyz.permute(0, 2, 1)
         if points is not None:
             points = points.permute(0, 2, 1)
@@ -246,6 +474,26 @@ class PointNetSetAbstraction(FoldCache):
             pooled = rows.view(B, S, Kn, -1).max(dim=2)[0]
         return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)  # [B, D', S]
 
+    def _train_hip(self, xyz, points, fps_start):
+        """train() on the HIP path: sv_group_rows -> shared MLP on rows -> sv_group_max (the sampling and ball query of
+        the torch path, so the same groups)"""
+        xyz = xyz.permute(0, 2, 1)
+        if points is not None:
+            points = points.permute(0, 2, 1)
+        B, N, C = xyz.shape
+        if self.group_all:
+            new_xyz = torch.zeros(B, 1, C, device=xyz.device)
+            S, K, idx = 1, N, None
+        else:
+            fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
+            new_xyz = index_points(xyz, fps_idx)
+            S, K = self.npoint, self.nsample
+            idx = query_ball_point(self.radius, K, xyz, new_xyz)
+        rows = group_rows(xyz, points, new_xyz, idx, SV_GROUP_SSG, self)
+        rows = _mlp_rows_train(rows, self.mlp_convs, self.mlp_bns)
+        pooled = group_max(rows, K, self).view(B, S, -1)
+        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)
+
 
 def _group_msg(xyz, points, new_xyz, idx):
     """[points[idx], xyz[idx] - new_xyz] -> [B, S, nsample, D + 3]: the multi-scale grouping's order, features first
@@ -261,6 +509,8 @@ class PointNetSetAbstractionMsg(FoldCache):
     on the GPU: sv_fps, sv_ball_query_multi, then sv_pointnet_sa_msg (all scales in one launch); shapes the fused kernel
     declines, or `fused = False`, run every scale's layers one launch each (sv_conv_fwd dense rows), torch.max and
     torch.cat - the same bits."""
+
+    _hip_trainable = True  # set_training_path
 
     def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
         super().__init__()
@@ -344,8 +594,17 @@ class PointNetSetAbstractionMsg(FoldCache):
         xyz = xyz.permute(0, 2, 1)
         if points is not None:
             points = points.permute(0, 2, 1)
+        hip = _hip_train(self, xyz)
         fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
         new_xyz = index_points(xyz, fps_idx)
+        if hip:  # every scale: sv_group_rows (MSG order) -> shared MLP on rows -> sv_group_max, then torch.cat
+            B, S = new_xyz.shape[0], new_xyz.shape[1]
+            pooled = []
+            for i, idx in enumerate(query_ball_point_multi(self.radius_list, self.nsample_list, xyz, new_xyz)):
+                rows = group_rows(xyz, points, new_xyz, idx, SV_GROUP_MSG, self)
+                rows = _mlp_rows_train(rows, self.conv_blocks[i], self.bn_blocks[i])
+                pooled.append(group_max(rows, self.nsample_list[i], self).view(B, S, -1))
+            return new_xyz.permute(0, 2, 1), torch.cat(pooled, dim=-1).permute(0, 2, 1)
         if self.training:  # the reference's torch path (:238-262)
             pooled = []
             for i, (radius, K) in enumerate(zip(self.radius_list, self.nsample_list)):
@@ -380,6 +639,8 @@ def three_nn_interpolate(xyz1, xyz2, points2):
 
 
 class PointNetFeaturePropagation(FoldCache):
+    _hip_trainable = True  # set_training_path
+
     def __init__(self, in_channel, mlp):
         super().__init__()
         self.mlp_convs = nn.ModuleList()
@@ -392,6 +653,8 @@ class PointNetFeaturePropagation(FoldCache):
 
     def forward(self, xyz1, xyz2, points1, points2):
         """3-NN inverse-distance interpolation of points2 (at xyz2) onto xyz1, concat points1, shared MLP."""
+        if _hip_train(self, xyz1, xyz2):
+            return self._train_hip(xyz1, xyz2, points1, points2)
         xyz1 = xyz1.permute(0, 2, 1)
         xyz2 = xyz2.permute(0, 2, 1)
         points2 = points2.permute(0, 2, 1)
@@ -414,4 +677,20 @@ class PointNetFeaturePropagation(FoldCache):
             return t
         folds = self._fold_get(lambda: [_fold_conv_bn(conv, bn) for conv, bn in zip(self.mlp_convs, self.mlp_bns)])
         rows = _mlp_rows(new_points.reshape(B * N, -1).contiguous(), self.mlp_convs, self.mlp_bns, folds)
+        return rows.view(B, N, -1).permute(0, 2, 1)
+
+    def _train_hip(self, xyz1, xyz2, points1, points2):
+        """train() on the HIP path: sv_three_nn + sv_three_nn_gather (one source point: the torch broadcast), concat
+        points1, shared MLP on rows"""
+        xyz1 = xyz1.permute(0, 2, 1)
+        xyz2 = xyz2.permute(0, 2, 1)
+        points2 = points2.permute(0, 2, 1)
+        B, N, _ = xyz1.shape
+        if xyz2.shape[1] == 1:
+            interpolated = points2.repeat(1, N, 1)
+        else:
+            idx, w = three_nn(xyz1, xyz2, self)
+            interpolated = three_nn_gather(points2, idx, w, self)
+        new_points = interpolated if points1 is None else torch.cat([points1.permute(0, 2, 1), interpolated], dim=-1)
+        rows = _mlp_rows_train(new_points.reshape(B * N, -1), self.mlp_convs, self.mlp_bns)
         return rows.view(B, N, -1).permute(0, 2, 1)

@@ -235,7 +235,9 @@ class SparseConvFunction(torch.autograd.Function):
                offset k), W[k]^T on the up plan of a down conv / the down plan of a transposed conv / dense rows;
       dW = sv_conv_wgrad(feats, dY, plan);   d bias = column sum of dY.
     grad_plan: a callable giving the input-gradient plan (built only when the input needs a gradient).
-    layer: the conv / linear module (None: a plain nn.Linear).  When its training_precision is "bf16" the forward runs on
+    layer: the conv / linear module (None: a plain nn.Linear; a module without training precisions, such as the
+    PointNet++ nn.Conv1d / nn.Conv2d, trains fp32 and only names the layer in TRAIN_LOG).  When its training_precision is
+    "bf16" the forward runs on
     sv_conv_fwd_bf16 (bias as the fp32 shift), dX on sv_conv_fwd_bf16 with W' packed (where the swapped shape Cin' = Cout,
     Cout' = Cin is one sv_conv_fwd_bf16 covers) and dW on sv_conv_wgrad_bf16 (sv_conv_wgrad where it returns
     SV_ERR_UNSUPPORTED); activations and gradients stay fp32 in memory, d bias stays the fp32 column sum."""
@@ -245,7 +247,7 @@ class SparseConvFunction(torch.autograd.Function):
         w = weight3.detach()
         if not w.is_contiguous():
             w = w.contiguous()
-        bf16 = layer is not None and layer._train_bf16()
+        bf16 = layer is not None and hasattr(layer, "_train_bf16") and layer._train_bf16()
         shift = bias.detach().reshape(-1) if bias is not None else None
         wp = layer.packed_weights_bf16() if bf16 and _bf16_fwd_ok(feats, w.shape[1], w.shape[2], w.shape[0]) else None
         out = conv_forward(feats.detach(), w, plan, V_out, None, shift, weight_bf16=wp)

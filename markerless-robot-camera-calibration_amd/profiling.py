@@ -52,7 +52,7 @@ def conv_kernel_config(Cout, Vpad, Cin=None, K=1):
     if K == 1 and Cout <= 4 and Cin is not None and Cin >= 64 and Cin % 4 == 0:
         return f"linear_narrow_kernel<{Cout}>"  # dense rows only; every K = 1 layer of the path is dense
     if K > 1 and Cin == 3 and Cout == 32:
-        return "conv_first_mfma_kernel<3, 32>"  # (SV_CONV_FIRST_VALU: the thread-per-voxel VALU kernel it replaced)
+        return "conv_first_mfma_kernel<3, 32>"  # (conv_first_layer_kernel, thread per voxel, beyond the 2 GB buffer extent)
     if K > 1 and Cin == 32 and Cout == 32:
         # conv_thin_lds_kernel (weights resident in LDS, one 16-wave workgroup per CU) under sv_conv_set_dispatch(>= 1): one
         # frame alone on the GPU; the recorded name is the library's (sv_conv_last_instance), this one only gates timing

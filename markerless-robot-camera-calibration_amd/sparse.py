@@ -65,7 +65,7 @@ class CoordinateMap:
         return self._hash
 
 
-BUF_LIMIT = 0x7fff0000 - 4096  # extent (bytes) the buffer-addressed conv instances take (csrc/sv_conv.hip BUF_LIMIT)
+BUF_LIMIT = 0x7fff0000 - 4096  # extent (bytes) the buffer-addressed conv instances take (csrc/sv_conv_params.h BUF_LIMIT)
 
 
 class ConvPlan:

@@ -418,6 +418,44 @@ int sv_icp_point2point(const float* src, int64_t S, const float* tgt, int64_t T,
                        size_t workspace_bytes, double* out_T, double* out_stats, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3b  point-to-plane ICP refinement with device-side normal estimation (the registration the reference prepares but
+ *      never runs: utils/icp.py:46-48 estimates normals on the crop with KDTreeSearchParamHybrid(radius=0.02,
+ *      max_nn=30), :63 then passes the point-to-point estimator, which does not read them).  Opt-in; the definitions
+ *      below follow Open3D's published algorithm, parity with Open3D binaries is by construction and unverified.
+ *
+ *   sv_estimate_normals: xyz float32[N][3] -> normals float32[N][3], counts int32[N] (or NULL).
+ *   Neighbour set of point i: the points j (i included) whose float32 squared distance (dx*dx + dy*dy) + dz*dz (no fma,
+ *   as sv_fps) is strictly below (float)(radius*radius); when more than max_nn qualify, the max_nn nearest, ties going
+ *   to the lower index.  counts[i] = size of the set.  A point with a NaN or inf coordinate is nobody's neighbour, has
+ *   an empty set and gets a NaN normal.  Fewer than 3 neighbours: normal (0, 0, 1).  Otherwise the covariance of the
+ *   neighbours about their mean in float64 and the unit eigenvector of its smallest eigenvalue (float64 cyclic Jacobi),
+ *   rounded to float32; sign: the stored component of largest magnitude is positive, the first on ties (as
+ *   sv_quat_avg_batched; Open3D leaves the sign to its solver and point-to-plane does not depend on it).  Collinear or
+ *   coincident neighbours: a unit vector orthogonal to the largest eigenvector.  The same cloud gives the same bits
+ *   whatever the kernel's tiling.  N in [1, 2^20], radius > 0, max_nn in [3, 64];
+ *   workspace: sv_normals_workspace_bytes(N, max_nn) - a fixed 256 bytes that the kernel currently does not use (its
+ *   candidates stay in LDS); the size is still checked.
+ *
+ *   sv_icp_point2plane: arguments, nearest-neighbour rule, inlier rule, fitness, rmse (over point distances), stop rule,
+ *   max_iterations, out_T and out_stats exactly as sv_icp_point2point; tgt_normals float32[T][3].  Update: for each
+ *   inlier with p the source point under the current T (float64), q its target point and n that point's normal,
+ *   r = (p - q).n, J = [p x n, n]; A = sum J J^T, b = sum J r (fixed summation order: repeated runs give the same bits);
+ *   A x = -b by Cholesky in float64, x = (alpha, beta, gamma, t); T <- [Rz(gamma) Ry(beta) Rx(alpha) | t] T.
+ *   An inlier whose normal is not finite counts towards fitness and rmse but adds nothing to A and b.  Fewer than 6
+ *   contributing inliers, or a Cholesky pivot that is not positive and finite (e.g. all normals parallel), stop the
+ *   iteration with no update (0 inliers: out_T = init_T bit for bit).  A non-finite x makes T NaN.
+ *   workspace: sv_icp_point2plane_workspace_bytes(S).
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_normals_workspace_bytes(int64_t N, int max_nn);
+int sv_estimate_normals(const float* xyz, int64_t N, double radius, int max_nn, void* workspace, size_t workspace_bytes,
+                        float* normals, int32_t* counts, sv_stream_t stream);
+size_t sv_icp_point2plane_workspace_bytes(int64_t S);
+int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const float* tgt_normals, int64_t T,
+                       const double* init_T, double max_distance, int max_iterations, double rel_fitness,
+                       double rel_rmse, void* workspace, size_t workspace_bytes, double* out_T, double* out_stats,
+                       sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,
  *      :89-109 query_ball_point, :178-204 the set abstraction's shared MLP + max, utils/data.py:13-34 numpy FPS)
  * ------------------------------------------------------------------------------------------- */

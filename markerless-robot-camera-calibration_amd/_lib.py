@@ -102,6 +102,11 @@ SIGNATURES = {
     "sv_icp_workspace_bytes": (c_size_t, [c_int64]),
     "sv_icp_point2point": (c_int, [_P, c_int64, _P, c_int64, _P, c_double, c_int, c_double, c_double, _P, c_size_t, _P, _P,
                                    _P]),
+    "sv_normals_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "sv_estimate_normals": (c_int, [_P, c_int64, c_double, c_int, _P, c_size_t, _P, _P, _P]),
+    "sv_icp_point2plane_workspace_bytes": (c_size_t, [c_int64]),
+    "sv_icp_point2plane": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_double, c_int, c_double, c_double, _P, c_size_t, _P,
+                                   _P, _P]),
     "sv_fps": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_interpolate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "sv_cluster_workspace_bytes": (c_size_t, [c_int64]),

@@ -7,7 +7,8 @@ the Kabsch / averaging solves run through libsvhip.  Differences that are delibe
     `pred_enabled` when a checkpoint is missing so the pipeline can be exercised with seeded random weights;
     with the reference's behaviour (False) a missing checkpoint disables prediction (all-zero segmentation, :281-283).
   * ICP refinement (utils/icp.py) runs on libsvhip (sv_icp_point2point); the CAD model points are passed in
-    (`cad_points=`) because the reference's mesh asset does not ship with this build.
+    (`cad_points=`) because the reference's mesh asset does not ship with this build.  `icp_method="point2plane"`
+    is an opt-in beyond the reference: normals of the crop (sv_estimate_normals) and sv_icp_point2plane.
   * check_sanity: the reference derives ground-truth key points from the EE crop with utils/data.py:141-335
     get_6_key_points (label synthesis, out of scope); here the expected key points are the six constant
     reference_key_points moved by the predicted EE pose — the same quantity the reference compares against.
@@ -55,10 +56,15 @@ def checkpoint_restore(model, f=None, device="cuda"):
     return ckpt.get("epoch", 0) + 1
 
 
+ICP_METHODS = ("point2point", "point2plane")
+
+
 class InferenceEngine:
     def __init__(self, calibration_only=False, device="cuda", allow_random_init=False, seed=1, cad_points=None,
-                 seg_precision=None):
-        """seg_precision: "fp32" or "bf16" compute precision of the segmentation network's wide conv / linear layers
+                 seg_precision=None, icp_method="point2point"):
+        """icp_method: the objective of the ICP refinement when INFERENCE.icp_enabled: "point2point" (the reference's) or
+        "point2plane" (normals estimated on the crop once per frame, utils/icp.py get_point2plane_matcher).
+        seg_precision: "fp32" or "bf16" compute precision of the segmentation network's wide conv / linear layers
         (nn.set_compute_precision; None = INFERENCE.SEGMENTATION.precision when the config has it, else fp32).  The pose
         networks always run fp32."""
         self._config = config.Config()
@@ -69,15 +75,19 @@ class InferenceEngine:
             raise ValueError(f"seg_precision must be one of {svnn.PRECISIONS}, got {seg_precision!r}")
         self.seg_precision = seg_precision
         self.device = torch.device(device)
+        if icp_method not in ICP_METHODS:
+            raise ValueError(f"icp_method must be one of {ICP_METHODS}, got {icp_method!r}")
+        self.icp_method = icp_method
         # CAD-to-crop ICP (utils/icp.py): the reference samples its CAD points from app/hand_files/hand_notblender.obj,
         # which does not ship with this build -> the caller supplies the model points
         self.match_icp = None
         if cfg.INFERENCE.icp_enabled:
             if cad_points is None:
                 raise ValueError("INFERENCE.icp_enabled needs cad_points (the CAD model of the end effector, [P,3])")
-            from ..utils.icp import get_point2point_matcher
+            from ..utils.icp import get_point2plane_matcher, get_point2point_matcher
 
-            self.match_icp = get_point2point_matcher(cad_points, device=self.device)
+            get_matcher = get_point2plane_matcher if icp_method == "point2plane" else get_point2point_matcher
+            self.match_icp = get_matcher(cad_points, device=self.device)
         self.reference_key_points = REFERENCE_KEY_POINTS.copy()
         self.ee_min_width = abs(self.reference_key_points[0][1] - self.reference_key_points[1][1]) - 0.02
         self.ee_min_height = abs(self.reference_key_points[0][2] - self.reference_key_points[2][2]) - 0.01
@@ -636,7 +646,13 @@ class InferenceEngine:
                 _, t, q = next(sol)
                 result.key_points_pose = np.concatenate((t, q))
             result.is_confident = self.check_sanity(data, result)
-            if self.match_icp is not None:  # app/inference_engine.py:358-362
+            if self.match_icp is not None and self.icp_method == "point2plane":
+                if result.ee_pose is not None or result.key_points_pose is not None:
+                    crop = torch.as_tensor(np.ascontiguousarray(ee_pts, dtype=np.float32)).to(self.device)
+                    normals = self.match_icp.crop_normals(crop)  # once per frame, shared by both refinements
+                    result.ee_pose = self.match_icp(crop, result.ee_pose, normals)
+                    result.key_points_pose = self.match_icp(crop, result.key_points_pose, normals)
+            elif self.match_icp is not None:  # app/inference_engine.py:358-362
                 result.ee_pose = self.match_icp(ee_pts, result.ee_pose)
                 result.key_points_pose = self.match_icp(ee_pts, result.key_points_pose)
         # ---- solve 2: the base poses' quaternions (get_base2cam_pose -> get_q_from_matrix), all frames at once

@@ -41,6 +41,49 @@ __device__ __forceinline__ void jacobi_svd3(double G[3][3], double V[3][3]) {
   }
 }
 
+// Cyclic two-sided Jacobi eigen-solve of a symmetric 3x3 matrix (only the upper triangle of A is read): on exit
+// lam[k] are the eigenvalues (unsorted) and the columns of V the matching unit eigenvectors.  Every rotation is exact
+// to rounding, so V stays orthonormal and small eigenvalues keep their relative accuracy (no trigonometric closed form).
+__device__ __forceinline__ void jacobi_eig3(const double A[3][3], double lam[3], double V[3][3]) {
+  double a[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      a[i][j] = (i <= j) ? A[i][j] : A[j][i];
+      V[i][j] = (i == j) ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 12; ++sweep) {
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = (pq == 2) ? 1 : 0;
+      const int q = (pq == 0) ? 1 : 2;
+      const int r = 3 - p - q;
+      const double apq = a[p][q];
+      if (fabs(apq) > 1e-300 && fabs(apq) > 1e-17 * sqrt(fabs(a[p][p] * a[q][q]))) {
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
+        const double c = 1.0 / sqrt(1.0 + t * t);
+        const double s = c * t;
+        a[p][p] -= t * apq;
+        a[q][q] += t * apq;
+        a[p][q] = a[q][p] = 0.0;
+        const double arp = a[r][p], arq = a[r][q];
+        a[r][p] = a[p][r] = c * arp - s * arq;
+        a[r][q] = a[q][r] = s * arp + c * arq;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const double vp = V[i][p], vq = V[i][q];
+          V[i][p] = c * vp - s * vq;
+          V[i][q] = s * vp + c * vq;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) lam[k] = a[k][k];
+}
+
 __device__ __forceinline__ void swap_cols(double M[3][3], int a, int b) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {

@@ -8,6 +8,10 @@
 // cross-covariance in fp64 and solves the Kabsch problem with the same one-sided Jacobi SVD as sv_kabsch_batched.
 // The iteration loop runs on the device side of the stream: a `state` record carries the current transform, the
 // previous fitness / rmse and a converged flag that turns the remaining launches into no-ops (no host read-backs).
+//
+// sv_icp_point2plane shares the search, the state record and the loop; only step (2) differs (icp_plane_update_kernel:
+// the 6x6 normal equations of the linearised point-to-plane residual, Cholesky, T <- U T).  The target normals come from
+// sv_estimate_normals (sv_normals.hip) or from the caller.
 #include "sv_common.h"
 #include "sv_dense_math.h"
 
@@ -166,6 +170,154 @@ __global__ void icp_finish_kernel(const IcpState* st, double* out_T, double* out
   }
 }
 
+// ---- point-to-plane update (sv_icp_point2plane) -------------------------------------------------------------------
+// Same evaluation as icp_update_kernel (inliers of icp_nn_kernel, fitness, rmse, stop rule); the update linearises the
+// rotation: per inlier r = (p - q).n, J = [p x n, n], A = sum J J^T (upper triangle, 21 values), b = sum J r, solved by
+// a 6x6 Cholesky in float64.  PL_ACC values per thread are summed over the wave by shuffles, then over the 8 waves in
+// ascending order, one thread per sum, through LDS: a fixed order, so repeated runs give the same bits (and thread 0's
+// solve reads the totals from LDS instead of holding 30 of them next to L in registers).
+constexpr int PL_ACC = 30;       // inliers, contributing, err, A (21), b (6)
+constexpr int PL_THREADS = 512;  // 8 waves
+
+__device__ __forceinline__ void nan_transform(double* T) {
+  const double nan = __builtin_nan("");
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = nan;
+  T[12] = T[13] = T[14] = 0.0;
+  T[15] = 1.0;
+}
+
+__global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
+    const float* __restrict__ src, int S, const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
+    const int32_t* __restrict__ nn, const float* __restrict__ d2, IcpState* __restrict__ st, double rel_fitness,
+    double rel_rmse, int last) {
+  __shared__ double red[PL_ACC][PL_THREADS / 64];
+  __shared__ double tot[PL_ACC];
+  if (st->converged) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  double acc[PL_ACC];
+#pragma unroll
+  for (int k = 0; k < PL_ACC; ++k) acc[k] = 0.0;
+  for (int i = threadIdx.x; i < S; i += PL_THREADS) {
+    const int j = nn[i];
+    if (j < 0) continue;
+    acc[0] += 1.0;
+    acc[2] += (double)d2[i];
+    const double n[3] = {tgt_normals[j * 3], tgt_normals[j * 3 + 1], tgt_normals[j * 3 + 2]};
+    if (!(isfinite(n[0]) && isfinite(n[1]) && isfinite(n[2]))) continue;  // counts as an inlier, adds no equation
+    const double x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    const double p[3] = {Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3], Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7],
+                         Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11]};
+    const double q[3] = {tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2]};
+    const double r = (p[0] - q[0]) * n[0] + (p[1] - q[1]) * n[1] + (p[2] - q[2]) * n[2];
+    const double J[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0],
+                         n[0], n[1], n[2]};
+    acc[1] += 1.0;
+    int e = 3;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) acc[e++] += J[a] * J[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) acc[24 + a] += J[a] * r;
+  }
+#pragma unroll
+  for (int k = 0; k < PL_ACC; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < PL_ACC) {
+    double t = 0;
+    for (int w = 0; w < PL_THREADS / 64; ++w) t += red[threadIdx.x][w];  // fixed order -> reproducible
+    tot[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double n = tot[0];
+  const double fitness = n / (double)S;
+  const double rmse = n > 0 ? sqrt(tot[2] / n) : 0.0;
+  const bool stop = (st->iterations > 0 || st->fitness >= 0) &&
+                    fabs(st->fitness - fitness) < rel_fitness && fabs(st->rmse - rmse) < rel_rmse;
+  st->fitness = fitness;
+  st->rmse = rmse;
+  if (stop || tot[1] < 6 || last) {
+    st->converged = 1;
+    return;
+  }
+  // A = L L^T (lower triangle of L), then L y = -b, L^T x = y.  A pivot that is not a positive finite number (parallel
+  // normals, NaN sums) ends the iteration without an update.
+  double L[6][6], x[6];
+  {
+    int e = 3;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) L[b][a] = tot[e++];
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double d = L[c][c];
+#pragma unroll
+    for (int k = 0; k < c; ++k) d -= L[c][k] * L[c][k];
+    if (!(d > 0.0) || !isfinite(d)) {
+      st->converged = 1;
+      return;
+    }
+    d = sqrt(d);
+    L[c][c] = d;
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      double v = L[r][c];
+#pragma unroll
+      for (int k = 0; k < c; ++k) v -= L[r][k] * L[c][k];
+      L[r][c] = v / d;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double v = -tot[24 + r];
+#pragma unroll
+    for (int k = 0; k < r; ++k) v -= L[r][k] * x[k];
+    x[r] = v / L[r][r];
+  }
+#pragma unroll
+  for (int r = 5; r >= 0; --r) {
+    double v = x[r];
+#pragma unroll
+    for (int k = r + 1; k < 6; ++k) v -= L[k][r] * x[k];
+    x[r] = v / L[r][r];
+  }
+  double Tn[16];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) finite = finite && isfinite(x[k]);
+  if (!finite) {
+    nan_transform(Tn);
+  } else {
+    // U = [Rz(gamma) Ry(beta) Rx(alpha) | t], T <- U * T
+    const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sg = sin(x[2]), cg = cos(x[2]);
+    const double R[3][3] = {{cb * cg, sa * sb * cg - ca * sg, ca * sb * cg + sa * sg},
+                            {cb * sg, sa * sb * sg + ca * cg, ca * sb * sg - sa * cg},
+                            {-sb, sa * cb, ca * cb}};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        Tn[r * 4 + c] =
+            R[r][0] * Tm[0 * 4 + c] + R[r][1] * Tm[1 * 4 + c] + R[r][2] * Tm[2 * 4 + c] + (c == 3 ? x[3 + r] : 0.0);
+    Tn[12] = Tn[13] = Tn[14] = 0.0;
+    Tn[15] = 1.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 16; ++k) st->T[k] = Tn[k];
+  st->iterations += 1;
+}
+
 }  // namespace sv
 
 using namespace sv;
@@ -197,6 +349,37 @@ int sv_icp_point2point(const float* src, int64_t S, const float* tgt, int64_t T,
     hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(256), 0, stream, src, (int)S, tgt, (int)T, st, max_d2, nn, d2);
     hipLaunchKernelGGL(icp_update_kernel, dim3(1), dim3(1024), 0, stream, src, (int)S, tgt, nn, d2, st, rel_fitness,
                        rel_rmse, it == max_iterations ? 1 : 0);
+  }
+  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, stream, st, out_T, out_stats);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+size_t sv_icp_point2plane_workspace_bytes(int64_t S) { return sv_icp_workspace_bytes(S); }
+
+int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const float* tgt_normals, int64_t T,
+                       const double* init_T, double max_distance, int max_iterations, double rel_fitness,
+                       double rel_rmse, void* workspace, size_t workspace_bytes, double* out_T, double* out_stats,
+                       sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(S >= 3 && T >= 1 && S < (1 << 24) && T < (1 << 24), "need at least 3 source points and 1 target point");
+  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0, "bad parameters");
+  SV_CHECK_ARG(src && tgt && tgt_normals && out_T && workspace, "null pointer");
+  Workspace ws(workspace, workspace_bytes);
+  IcpState* st = ws.take<IcpState>(1);
+  int32_t* nn = ws.take<int32_t>(S);
+  float* d2 = ws.take<float>(S);
+  if (!ws.ok) {
+    set_error("sv_icp_point2plane: workspace too small");
+    return SV_ERR_WORKSPACE;
+  }
+  hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, stream, st, init_T);
+  const float max_d2 = (float)(max_distance * max_distance);
+  const unsigned nb = (unsigned)((S + 255) / 256);
+  for (int it = 0; it <= max_iterations; ++it) {
+    hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(256), 0, stream, src, (int)S, tgt, (int)T, st, max_d2, nn, d2);
+    hipLaunchKernelGGL(icp_plane_update_kernel, dim3(1), dim3(PL_THREADS), 0, stream, src, (int)S, tgt, tgt_normals, nn, d2, st,
+                       rel_fitness, rel_rmse, it == max_iterations ? 1 : 0);
   }
   hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, stream, st, out_T, out_stats);
   SV_LAUNCH_CHECK();

@@ -464,13 +464,17 @@ int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const floa
 int sv_fps(const float* xyz, int B, int N, int S, const int64_t* start, int64_t* out, sv_stream_t stream);
 /* out int64[B][S][nsample]: the first nsample indices n (ascending) with ||xyz[n]-new_xyz[s]||^2 <= r^2,
  * padded with the first hit (r^2 = (float)(radius*radius), as torch compares a float32 tensor with the python
- * scalar radius**2); the distance uses the reference's expanded form (-2ab + a^2 + b^2) in float32. */
+ * scalar radius**2); the distance uses the reference's expanded form (-2ab + a^2 + b^2) in float32.  A point is a hit
+ * when NOT (d > r^2), so a NaN distance is a hit.  An empty ball (no hit at all) yields the index N in all nsample
+ * entries, as the reference does: an index outside the cloud, which sv_pointnet_sa[_msg] and sv_group_rows turn into a NaN
+ * row (never pass it to a plain gather). */
 int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, double radius, int nsample,
                   int64_t* out, sv_stream_t stream);
 /* The R ball queries of one PointNetSetAbstractionMsg layer (model/pointnet2_utils.py:242-244, query_ball_point per radius
  * over the same centroids) in one scan over the cloud: out[r] int64[B][S][nsamples[r]] is exactly sv_ball_query with
  * (radii[r], nsamples[r]) - the same float32 distance, r^2 = (float)(radius*radius), ascending order and first-hit
- * padding.  radii, nsamples and out are HOST arrays of R entries (out: device pointers); the radii need not be sorted.
+ * padding, and the index N in every entry of an empty ball.  radii, nsamples and out are HOST arrays of R entries (out:
+ * device pointers); the radii need not be sorted.
  * Returns SV_ERR_UNSUPPORTED (nothing launched) when R is outside 1..SV_BQ_MAX_RADII. */
 #define SV_BQ_MAX_RADII 4
 int sv_ball_query_multi(const float* xyz, const float* new_xyz, int B, int N, int S, int R, const double* radii,
@@ -498,9 +502,11 @@ int sv_fps_segmented(const float* xyz, const int64_t* offsets, const int64_t* ou
  * params: one device buffer, per layer l in order W_l float32[widths[l]][widths[l + 1]], scale_l [widths[l + 1]],
  * shift_l [widths[l + 1]]; widths: HOST int[L + 1], widths[0] = 3 + D.
  * Every output element is one fma chain over the input channels ascending from 0 (as sv_conv_fwd's dense rows): the
- * unfused path's bits.  Returns SV_ERR_UNSUPPORTED (nothing launched) when nsample is not 16 / 32 / 64, L is outside
- * 1..SV_PN_MAX_LAYERS, a layer width is not a multiple of 16 in 16..1024, or the 64-row tile's two LDS buffers exceed
- * 160 KiB. */
+ * unfused path's bits.  A group index outside [0, N) (sv_ball_query's N for an empty ball) reads nothing: its row is NaN
+ * in every column, so that centroid's pooled output is NaN (as sv_group_rows + sv_group_max on the training path); the
+ * other centroids are unaffected.  Returns SV_ERR_UNSUPPORTED (nothing launched) when nsample is not 16 / 32 / 64, L is
+ * outside 1..SV_PN_MAX_LAYERS, a layer width is not a multiple of 16 in 16..1024, or the 64-row tile's two LDS buffers
+ * exceed 160 KiB. */
 #define SV_PN_MAX_LAYERS 4
 int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B, int N,
                    int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
@@ -512,7 +518,8 @@ int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, 
  * (col_r = C_0 + .. + C_{r-1}, C_r its last width: the reference's torch.cat, :262).
  * nsamples, group_idx (device pointers), params (device pointers, sv_pointnet_sa's packing per scale), nlayers: HOST
  * arrays of R entries; widths: HOST, the R scales' width lists concatenated (nlayers[r] + 1 entries each, first 3 + D).
- * Same arithmetic as sv_pointnet_sa: every scale's columns are bit-identical to the unfused eval path on its groups.
+ * Same arithmetic as sv_pointnet_sa: every scale's columns are bit-identical to the unfused eval path on its groups, and
+ * a group index outside [0, N) gives a NaN row (that scale's columns of the centroid are NaN).
  * Returns SV_ERR_UNSUPPORTED (nothing launched) when R is outside 1..SV_PN_MAX_SCALES, a scale's nsample is not
  * 16 / 32 / 64 / 128, its layer count or widths are outside sv_pointnet_sa's limits, or its LDS (two 64-row buffers, plus
  * C_r floats of running maxima when nsample = 128) exceeds 160 KiB. */
@@ -529,7 +536,8 @@ int sv_pointnet_sa_msg(const float* xyz, const float* points, const float* new_x
  * i = idx[b][s][k]: order SV_GROUP_SSG [xyz[b][i] - new_xyz[b][s], points[b][i]] (model/pointnet2_utils.py:131-137),
  * SV_GROUP_MSG [points[b][i], xyz[b][i] - new_xyz[b][s]] (:245-250).  Columns 3 + D .. ld - 1 are written 0.  idx NULL is
  * sample_and_group_all (:143-160): S = 1, nsample = N, row k = [xyz[b][k], points[b][k]], no subtraction, SSG order,
- * new_xyz unused.  points NULL when D = 0.  The bits of torch's index_points and subtraction. */
+ * new_xyz unused.  points NULL when D = 0.  The bits of torch's index_points and subtraction.  An index outside [0, N)
+ * (sv_ball_query's N for an empty ball) reads nothing: columns 0 .. 3 + D - 1 of its row are NaN. */
 #define SV_GROUP_SSG 0
 #define SV_GROUP_MSG 1
 int sv_group_rows(const float* xyz, const float* points, const float* new_xyz, const int64_t* idx, int B, int N, int D,

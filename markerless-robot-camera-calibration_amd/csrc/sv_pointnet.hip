@@ -186,10 +186,11 @@ __global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams 
       float v = 0.f;
       if (q < p.nq && c < c_real) {
         const int64_t b = q / p.S;
-        int64_t j = p.idx[q * ns + r % ns];
-        j = j < 0 ? 0 : (j >= p.N ? p.N - 1 : j);  // ball-query indices are in range; never read outside the cloud
+        const int64_t j = p.idx[q * ns + r % ns];
         const int64_t row = b * p.N + j;
-        if (c < 3)
+        if (j < 0 || j >= p.N)
+          v = NAN;  // an index outside the cloud (an empty ball's N) reads nothing: a NaN row, as sv_group_rows
+        else if (c < 3)
           v = __fsub_rn(p.xyz[row * 3 + c], p.new_xyz[q * 3 + c]);
         else
           v = p.points[row * p.D + (c - 3)];
@@ -275,10 +276,11 @@ __global__ __launch_bounds__(PN_THREADS) void pointnet_sa_msg_kernel(const PnMsg
         float v = 0.f;
         if (q < p.nq && c < c_real) {
           const int64_t b = q / p.S;
-          int64_t j = sc.idx[q * ns + pass * rows_c + rr % rows_c];
-          j = j < 0 ? 0 : (j >= p.N ? p.N - 1 : j);  // ball-query indices are in range; never read outside the cloud
+          const int64_t j = sc.idx[q * ns + pass * rows_c + rr % rows_c];
           const int64_t row = b * p.N + j;
-          if (c < p.D)
+          if (j < 0 || j >= p.N)
+            v = NAN;  // an index outside the cloud (an empty ball's N) reads nothing: a NaN row, as sv_group_rows
+          else if (c < p.D)
             v = p.points[row * p.D + c];
           else
             v = __fsub_rn(p.xyz[row * 3 + (c - p.D)], p.new_xyz[q * 3 + (c - p.D)]);

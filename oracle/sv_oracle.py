@@ -14,6 +14,9 @@ PARITY STATUS
   * dense solves, metrics, FPS, ball query: pinned by tests/golden/*.npz generated from the reference's own
     utils/transformation.py, utils/calibration.py, utils/metrics.py, utils/data.py, model/pointnet2_utils.py
     (tools/make_golden.py).
+  * 3-NN interpolation (three_nn, three_nn_interpolate): the reference's formula (model/pointnet2_utils.py:298-305) in
+    float32 with the operation order sv_three_nn documents; pinned to float64 brute force, like the ball query, by
+    tests/test_oracle_points.py.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
@@ -612,6 +615,67 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
             row[: min(nsample, len(idx))] = idx[:nsample]
             out[b, s] = row
     return out
+
+
+def three_nn(xyz1, xyz2):
+    """model/pointnet2_utils.py:298-303 as sv_three_nn / sv_three_nn_interpolate state it, in float32 with every operation
+    rounded on its own: d = (-2 * ((qx*px + qy*py) + qz*pz) + qq) + pp with qq, pp = (x*x + y*y) + z*z; the three smallest d
+    by strict-less insertion over the sources in ascending order (a tie keeps the lower index, a NaN distance is never
+    selected, an unfilled slot keeps index 0 and distance +inf); w_i = 1 / (d_i + 1e-8), ws = (w0 + w1) + w2, w_i / ws.
+    xyz1 [B,N,3] queries, xyz2 [B,S,3] sources -> (idx int32 [B,N,3] nearest first, w float32 [B,N,3])."""
+    q = np.asarray(xyz1, dtype=np.float32)
+    p = np.asarray(xyz2, dtype=np.float32)
+    B, N, _ = q.shape
+    S = p.shape[1]
+    two, eps, one = np.float32(-2.0), np.float32(1e-8), np.float32(1.0)
+    with np.errstate(all="ignore"):
+        qx, qy, qz = q[..., 0], q[..., 1], q[..., 2]
+        qq = (qx * qx + qy * qy) + qz * qz
+        dd = [np.full((B, N), np.inf, dtype=np.float32) for _ in range(3)]
+        ii = [np.zeros((B, N), dtype=np.int32) for _ in range(3)]
+        for j in range(S):
+            px, py, pz = (p[:, j, k][:, None] for k in range(3))
+            dot = (qx * px + qy * py) + qz * pz
+            pp = (px * px + py * py) + pz * pz
+            d = (two * dot + qq) + pp
+            lt0, lt1, lt2 = d < dd[0], d < dd[1], d < dd[2]
+            jj = np.int32(j)
+            dd[2], ii[2] = np.where(lt1, dd[1], np.where(lt2, d, dd[2])), np.where(lt1, ii[1], np.where(lt2, jj, ii[2]))
+            dd[1], ii[1] = np.where(lt0, dd[0], np.where(lt1, d, dd[1])), np.where(lt0, ii[0], np.where(lt1, jj, ii[1]))
+            dd[0], ii[0] = np.where(lt0, d, dd[0]), np.where(lt0, jj, ii[0])
+        w = [one / (d + eps) for d in dd]
+        ws = (w[0] + w[1]) + w[2]
+        wn = np.stack([wi / ws for wi in w], axis=-1).astype(np.float32)
+    return np.stack(ii, axis=-1).astype(np.int32), wn
+
+
+def three_nn_distances(xyz1, xyz2, idx):
+    """the float32 expanded distances of three_nn for given source indices idx [B,N,3] (same operation order)"""
+    q = np.asarray(xyz1, dtype=np.float32)[:, :, None, :]
+    p = np.take_along_axis(np.asarray(xyz2, dtype=np.float32)[:, None, :, :], np.asarray(idx)[..., None].astype(np.int64),
+                           axis=2)
+    with np.errstate(all="ignore"):
+        qq = (q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1]) + q[..., 2] * q[..., 2]
+        pp = (p[..., 0] * p[..., 0] + p[..., 1] * p[..., 1]) + p[..., 2] * p[..., 2]
+        dot = (q[..., 0] * p[..., 0] + q[..., 1] * p[..., 1]) + q[..., 2] * p[..., 2]
+        return ((np.float32(-2.0) * dot + qq) + pp).astype(np.float32)
+
+
+def three_nn_interpolate(xyz1, xyz2, points2):
+    """model/pointnet2_utils.py:298-305: out[b][n][c] = (p0*w0 + p1*w1) + p2*w2 over three_nn's sources, float32, every
+    operation rounded on its own.  points2 [B,S,C] -> float32 [B,N,C]."""
+    idx, w = three_nn(xyz1, xyz2)
+    return three_nn_gather(points2, idx, w)
+
+
+def three_nn_gather(points2, idx, w):
+    """(p0*w0 + p1*w1) + p2*w2 for given idx [B,N,3] / w [B,N,3] (sv_three_nn_gather's arithmetic)"""
+    p2 = np.asarray(points2, dtype=np.float32)
+    idx = np.asarray(idx).astype(np.int64)
+    w = np.asarray(w, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        g = [np.take_along_axis(p2, idx[..., k][..., None], axis=1) * w[..., k][..., None] for k in range(3)]
+        return ((g[0] + g[1]) + g[2]).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -39,6 +39,22 @@ def test_pointnet_sa_argument_checks_without_gpu():
                               None) == 0
 
 
+def test_fps_argument_checks_without_gpu():
+    """sv_fps beyond the LDS-resident distance array (N = 38401): an argument error before any pointer is looked at or
+    anything is launched; N = 38400 passes that check (only the pointers are missing)."""
+    import mrcc_amd
+
+    lib = mrcc_amd._lib.load()
+    # (xyz, B, N, S, start, out, stream)
+    rc = lib.sv_fps(None, 2, 38401, 16, None, None, None)
+    assert rc == -1 and b"too large" in lib.sv_last_error()
+    rc = lib.sv_fps(None, 2, 38400, 16, None, None, None)
+    assert rc == -1 and b"null pointer" in lib.sv_last_error()
+    rc = lib.sv_fps(None, 2, 0, 16, None, None, None)
+    assert rc == -1 and b"bad shape" in lib.sv_last_error()
+    assert lib.sv_fps(None, 0, 38400, 16, None, None, None) == 0
+
+
 def test_fps_segmented_argument_checks_without_gpu():
     import mrcc_amd
 

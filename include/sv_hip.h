@@ -78,6 +78,9 @@ int sv_abi_version(void);
  * coords4: float32[N,4] rows (batch, x, y, z) already multiplied by `scale` by the caller, exactly what
  *          ME.utils.batched_coordinates hands to TensorField.  voxel = floor(coord) per axis.
  *          With coords_are_int != 0 the buffer is int32[N,4] (already quantised coordinates).
+ *          Key range: a voxel coordinate lies in [-2^17, 2^17 - 1] per axis and the batch index in [0, 1023] (the 18 + 18 +
+ *          18 + 10 bits of the key); a float row is in range iff -2^17 <= coord < 2^17 and 0 <= batch < 1024 (the batch is
+ *          truncated), so NaN, +-inf and a negative batch fraction are out of range, as is every int32 outside those intervals.
  * keys:    uint64[N]    first V entries = canonical sorted unique keys
  * vcoords: int32[N,4]   first V rows   = (batch,x,y,z) of each voxel
  * inverse: int64[N]     voxel row of every input point  (TensorField -> SparseTensor inverse map)
@@ -100,7 +103,9 @@ int sv_voxel_reduce(const float* feats, int C, const int32_t* order, const int32
  * Coordinate manager pieces (replace ME's coordinate_map_gpu / kernel_map; implicit in every
  * ME.MinkowskiConvolution call of model/backbone/minkunet.py:55-121)
  * ------------------------------------------------------------------------------------------- */
-/* open-addressing hash  key -> row ;  capacity must be a power of two >= 2*V. */
+/* open-addressing hash  key -> row ;  capacity must be a power of two >= 2*V.  An empty slot holds the key ~0, which is
+ * also the key of the voxel (1023, 2^17-1, 2^17-1, 2^17-1): that key is not stored; sv_kernel_map_k3 finds the voxel as the
+ * last row of its (canonical) vcoords instead. */
 int sv_hash_build(const uint64_t* keys, int64_t V, uint64_t* table_keys, int32_t* table_vals, int64_t capacity,
                   sv_stream_t stream);
 

@@ -72,9 +72,11 @@ __host__ __device__ __forceinline__ uint64_t compact1by2(uint64_t v) {
   v = (v ^ (v >> 32)) & 0x3ffffull;
   return v;
 }
+// valid voxel: batch in [0, SV_MAX_BATCH), every axis in [-2^17, 2^17 - 1] (include/sv_hip.h).  The bias is added in unsigned
+// arithmetic: any int32 is a defined input (INT32_MAX + 2^17 as a signed sum is not) and wraps to a value >= 2^18.
 __host__ __device__ __forceinline__ bool coord_in_range(int b, int x, int y, int z) {
-  return (unsigned)b < SV_MAX_BATCH && (unsigned)(x + SV_COORD_BIAS) < (1u << SV_COORD_BITS) &&
-         (unsigned)(y + SV_COORD_BIAS) < (1u << SV_COORD_BITS) && (unsigned)(z + SV_COORD_BIAS) < (1u << SV_COORD_BITS);
+  return (unsigned)b < SV_MAX_BATCH && (unsigned)x + (unsigned)SV_COORD_BIAS < (1u << SV_COORD_BITS) &&
+         (unsigned)y + (unsigned)SV_COORD_BIAS < (1u << SV_COORD_BITS) && (unsigned)z + (unsigned)SV_COORD_BIAS < (1u << SV_COORD_BITS);
 }
 __host__ __device__ __forceinline__ uint64_t make_key(int b, int x, int y, int z) {
   return ((uint64_t)b << 54) | part1by2((uint64_t)(x + SV_COORD_BIAS)) | (part1by2((uint64_t)(y + SV_COORD_BIAS)) << 1) |
@@ -86,6 +88,10 @@ __host__ __device__ __forceinline__ void decode_key(uint64_t key, int& b, int& x
   y = (int)compact1by2(key >> 1) - SV_COORD_BIAS;
   z = (int)compact1by2(key >> 2) - SV_COORD_BIAS;
 }
+// Marker of an empty hash slot.  All 64 bits of a key are in use, so this value is also the key of ONE valid voxel: batch
+// 1023 at x = y = z = 2^17 - 1.  The table never stores that key (hash_insert_kernel skips it) and hash_find must not be asked
+// for it: being the largest key, the voxel can only be the LAST row of a canonical map, which is how kmap_k3_probe_kernel
+// resolves it.
 #define SV_EMPTY_KEY 0xffffffffffffffffull
 
 __host__ __device__ __forceinline__ uint64_t hash64(uint64_t k) {
@@ -100,7 +106,7 @@ __host__ __device__ __forceinline__ uint64_t hash64(uint64_t k) {
 __device__ __forceinline__ int hash_find(const uint64_t* __restrict__ tkeys, const int32_t* __restrict__ tvals,
                                          uint64_t cap_mask, uint64_t key) {
   uint64_t slot = hash64(key) & cap_mask;
-  // the table is at most half full, so a probe sequence always terminates at an empty slot
+  // the table is at most half full, so a probe sequence always terminates at an empty slot; key != SV_EMPTY_KEY
   for (;;) {
     uint64_t k = tkeys[slot];
     if (k == key) return tvals[slot];

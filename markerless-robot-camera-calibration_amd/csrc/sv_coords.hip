@@ -126,9 +126,10 @@ __global__ __launch_bounds__(256) void quantize_kernel(const void* __restrict__ 
     b = c.x; x = c.y; y = c.z; z = c.w;
   } else {
     const float4 c = ((const float4*)coords4)[i];
+    // voxel = floor(c) lies in [-2^17, 2^17 - 1] iff -2^17 <= c < 2^17; every comparison is false for NaN
     const float lim = (float)SV_COORD_BIAS;
-    ok = (c.x >= 0.0f) && (c.x < (float)SV_MAX_BATCH) && (fabsf(c.y) < lim) && (fabsf(c.z) < lim) &&
-         (fabsf(c.w) < lim);  // also false for NaN
+    ok = (c.x >= 0.0f) && (c.x < (float)SV_MAX_BATCH) && (c.y >= -lim) && (c.y < lim) && (c.z >= -lim) && (c.z < lim) &&
+         (c.w >= -lim) && (c.w < lim);
     b = ok ? (int)c.x : 0;
     x = ok ? (int)floorf(c.y) : 0;
     y = ok ? (int)floorf(c.z) : 0;
@@ -195,6 +196,7 @@ __global__ __launch_bounds__(256) void hash_insert_kernel(const uint64_t* __rest
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= V) return;
   uint64_t key = keys[i];
+  if (key == SV_EMPTY_KEY) return;  // the one voxel whose key is the empty marker (sv_common.h): resolved without the table
   uint64_t slot = hash64(key) & cap_mask;
   for (;;) {
     unsigned long long prev = atomicCAS((unsigned long long*)&tkeys[slot], (unsigned long long)SV_EMPTY_KEY,
@@ -253,7 +255,17 @@ __global__ __launch_bounds__(256) void kmap_k3_probe_kernel(const int32_t* __res
   } else {
     const int4 c = ((const int4*)vcoords)[o];
     const int x = c.y + dx * step, y = c.z + dy * step, z = c.w + dz * step;
-    r = coord_in_range(c.x, x, y, z) ? hash_find(tkeys, tvals, cap_mask, make_key(c.x, x, y, z)) : -1;
+    if (!coord_in_range(c.x, x, y, z)) {
+      r = -1;  // outside the key range: make_key would wrap it onto the opposite face
+    } else {
+      const uint64_t key = make_key(c.x, x, y, z);
+      if (key != SV_EMPTY_KEY) {
+        r = hash_find(tkeys, tvals, cap_mask, key);
+      } else {  // the largest key there is: present iff it is the last row of the (key-sorted) map
+        const int4 l = ((const int4*)vcoords)[V - 1];
+        r = (l.x == c.x && l.y == x && l.z == y && l.w == z) ? (int)(V - 1) : -1;
+      }
+    }
   }
   nbr[(int64_t)k * ld + o] = r;
 }

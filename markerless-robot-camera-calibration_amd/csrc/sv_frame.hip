@@ -106,7 +106,7 @@ int sv_frame_maps(const void* coords4, int coords_are_int, int64_t N, int levels
   L[6] = counters_host[1];  // points outside the key range
   L[7] = 0;
   if (counters_host[1] != 0) {
-    set_error("sv_frame_maps: %d points have coordinates outside the key range (|coord| < 2^17 voxels, 0 <= batch < 1024)",
+    set_error("sv_frame_maps: %d points have coordinates outside the key range (-2^17 <= voxel < 2^17 per axis, 0 <= batch < 1024)",
               counters_host[1]);
     return SV_ERR_RANGE;
   }

@@ -421,7 +421,7 @@ def _voxelize(coords, device, coords_are_int):
     V, bad = cnt[0], cnt[1]
     if bad:
         raise _lib.SvHipError(
-            f"{bad} points have coordinates outside the key range (|coord| < 2^17 voxels, 0 <= batch < 1024)")
+            f"{bad} points have coordinates outside the key range (-2^17 <= voxel < 2^17 per axis, 0 <= batch < 1024)")
     return CoordinateMap(keys[:V], vcoords[:V], V, 1), inverse[:N], order[:N], seg_start[: V + 1]
 
 

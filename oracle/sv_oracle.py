@@ -33,6 +33,7 @@ _lib = None
 
 COORD_BIAS = 1 << 17
 COORD_BITS = 18
+MAX_BATCH = 1024
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 
@@ -66,11 +67,16 @@ def _part1by2(v):
     return out
 
 
+def _in_range(xyz):
+    """voxel coordinates inside the key range [-2^17, 2^17 - 1] (include/sv_hip.h)"""
+    return (xyz >= -COORD_BIAS) & (xyz < COORD_BIAS)
+
+
 def make_keys(bxyz):
     """uint64 key = batch << 54 | morton3(x + 2^17, y + 2^17, z + 2^17), x in bit 3j (include/sv_hip.h)."""
     bxyz = np.asarray(bxyz, dtype=np.int64)
     b, x, y, z = (bxyz[:, i] for i in range(4))
-    if ((b < 0) | (b >= 1024)).any() or (np.abs(bxyz[:, 1:]) >= COORD_BIAS).any():
+    if ((b < 0) | (b >= MAX_BATCH)).any() or not _in_range(bxyz[:, 1:]).all():
         raise ValueError("coordinate outside the key range")
     return ((b.astype(np.uint64) << np.uint64(54)) | _part1by2(x + COORD_BIAS) | (_part1by2(y + COORD_BIAS) << np.uint64(1))
             | (_part1by2(z + COORD_BIAS) << np.uint64(2)))
@@ -84,6 +90,10 @@ def voxelize(coords4, coords_are_int=False):
         q = c.astype(np.int64)
     else:
         c = c.astype(np.float32)
+        # a float row is in range iff -2^17 <= coord < 2^17 and 0 <= batch < 1024: NaN and +-inf fail every comparison, and
+        # a batch value in (-1, 0) must not be truncated to batch 0
+        if not (_in_range(c[:, 1:]).all() and ((c[:, 0] >= 0) & (c[:, 0] < MAX_BATCH)).all()):
+            raise ValueError("coordinate outside the key range")
         q = np.empty(c.shape, dtype=np.int64)
         q[:, 0] = c[:, 0].astype(np.int64)
         q[:, 1:] = np.floor(c[:, 1:]).astype(np.int64)
@@ -175,7 +185,7 @@ def kernel_map_k3(coords, tensor_stride, dilation=1):
                 q[:, 1] += dx * step
                 q[:, 2] += dy * step
                 q[:, 3] += dz * step
-                valid = (np.abs(q[:, 1:]) < COORD_BIAS).all(axis=1)
+                valid = _in_range(q[:, 1:]).all(axis=1)
                 q[~valid, 1:] = 0
                 nbr[k] = _lookup(keys, make_keys(q), valid)
                 k += 1

@@ -30,10 +30,15 @@ def _same_plan(a, b):
 @pytest.mark.parametrize("n,batch,levels,rules", [(3000, 1, 4, "200:9,18"), (9000, 2, 4, "1000:14;300:9,18"),
                                                    (700, 1, 6, ""), (20000, 1, 4, "2000:7,14,20")])
 def test_frame_composites_equal_the_piecewise_calls(gpu, n, batch, levels, rules):
+    c, f = _frame(n, 3, batch)
+    check_composites_equal_piecewise(gpu, c, f, levels, rules)
+
+
+def check_composites_equal_piecewise(gpu, c, f, levels, rules):
+    """coordinates c [N, 4] and features f of one input (also used by test_gpu_coords_edges.py on its range-edge cloud)"""
     from mrcc_amd import MinkowskiEngine as ME
     from mrcc_amd import nn as svnn
 
-    c, f = _frame(n, 3, batch)
     parsed = svnn._parse_split_rules(rules)
     fa = ME.TensorField(f, c, device=gpu)
     xa = fa.sparse(pyramid_levels=levels)

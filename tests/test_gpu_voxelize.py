@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 import torch
+from coords_helpers import check_plan_order, unsort
 
 pytestmark = pytest.mark.gpu
 
@@ -105,26 +106,6 @@ def test_stride_and_kernel_maps_match_oracle(gpu, oracle, n, L, scale):
         cs = child_start.cpu().numpy()
         assert cs[0] == 0 and cs[-1] == len(frame.maps[ts]) and np.all(np.diff(cs) >= 1)
 
-    def unsort(plan):
-        """Undo the mask sort: nbr in canonical output-row order."""
-        perm = plan.perm.cpu().numpy()
-        nbr_s = plan.nbr_s.cpu().numpy()
-        valid = perm >= 0
-        assert valid.sum() == plan.V_out and np.array_equal(np.sort(perm[valid]), np.arange(plan.V_out))
-        out = np.full((plan.K, plan.V_out), -2, np.int32)
-        out[:, perm[valid]] = nbr_s[:, valid]
-        assert np.all(nbr_s[:, ~valid] == -1)
-        # submask bit s of tile t for offset k <=> some row of that 16-row sub-tile has a neighbour at k
-        sub = (nbr_s >= 0).reshape(plan.K, plan.Vpad // 128, 8, 16).any(axis=3)  # [K, tiles, 8]
-        bits = (sub * (1 << np.arange(8))).sum(axis=2).T  # [tiles, K]
-        assert np.array_equal(plan.submask.cpu().numpy().astype(np.int64), bits)
-        # tile_order: a permutation of the plan tiles, work (active sub-tile slots) non-increasing
-        order = plan.tile_order.cpu().numpy()
-        assert np.array_equal(np.sort(order), np.arange(plan.Vpad // 128))
-        work = sub.sum(axis=(0, 2))[order]
-        assert np.all(np.diff(work) <= 0)
-        return out
-
     for ts in (1, 2, 4):
         assert np.array_equal(unsort(cm.plan_k3(ts)), frame.k3(ts))
         assert np.array_equal(unsort(cm.plan_down(ts)), frame.kdown(ts))
@@ -191,26 +172,6 @@ def test_sparse_quantize_matches_oracle(gpu, oracle, cols, as_torch):
     assert np.array_equal(m_idx, widx) and np.array_equal(m_inv, winv)
 
 
-def _gray_key(mask, K):
-    """sort key of sv_plan_build (csrc/sv_coords.hip iota_key_kernel): rarest offsets (corners, edges, faces, centre) as
-    the most significant bits, then the rank in reflected-Gray order."""
-    m = mask.astype(np.int64)
-    if K == 27:
-        pos, rank = {}, 0
-        for cls in (3, 2, 1, 0):
-            for k in range(27):
-                if abs(k % 3 - 1) + abs((k // 3) % 3 - 1) + abs(k // 9 - 1) == cls:
-                    pos[k] = 26 - rank
-                    rank += 1
-        m2 = np.zeros_like(m)
-        for k in range(27):
-            m2 |= ((m >> k) & 1) << pos[k]
-        m = m2
-    for s in (1, 2, 4, 8, 16):
-        m ^= m >> s
-    return m
-
-
 @pytest.mark.parametrize("n,L", [(200_000, 2.4), (9_000, 0.6), (300, 0.2)])
 def test_plan_order_is_the_stable_sort_of_its_key(gpu, n, L):
     """The hand-written radix sort (csrc/sv_sort.hip) behind the conv plans: multi-workgroup passes at the big levels,
@@ -225,17 +186,14 @@ def test_plan_order_is_the_stable_sort_of_its_key(gpu, n, L):
     cm = x.coordinate_manager
     plans = [(cm.plan_k3(1 << l), 27) for l in range(4)] + [(cm.plan_down(1), 8), (cm.plan_up(2), 8), (cm.plan_down(4), 8)]
     for plan, K in plans:
-        V = plan.V_out
-        perm = plan.perm.cpu().numpy()
-        nbr_s = plan.nbr_s.cpu().numpy()
-        assert np.array_equal(np.sort(perm[:V]), np.arange(V)) and (perm[V:] == -1).all()
-        mask_sorted = np.zeros(plan.Vpad, np.int64)
-        for k in range(K):
-            mask_sorted |= (nbr_s[k] >= 0).astype(np.int64) << k
-        mask = np.zeros(V, np.int64)
-        mask[perm[:V]] = mask_sorted[:V]
-        want = np.argsort(_gray_key(mask, K), kind="stable")
-        assert np.array_equal(perm[:V], want)
-        sub = plan.submask.cpu().numpy().astype(np.uint32)
-        cost = np.array([[bin(int(v)).count("1") for v in row] for row in sub]).sum(axis=1)
-        assert np.array_equal(plan.tile_order.cpu().numpy(), np.argsort(255 - np.minimum(cost, 255), kind="stable"))
+        check_plan_order(plan, K)
+    # the offset-range plans (K = 14 + 13, 9 + 9 + 9, 7 + 7 + 6 + 7): each range sorts by the Gray key of its own sub-mask
+    for cuts in (14, (9, 18), (7, 14, 20)):
+        split = cm.plan_k3_split(1, cuts)
+        bounds = (0,) + ((cuts,) if isinstance(cuts, int) else cuts) + (27,)
+        assert [(k0, k1) for k0, k1, _ in split.parts] == list(zip(bounds[:-1], bounds[1:]))
+        whole = unsort(split.whole)
+        for k0, k1, part in split.parts:
+            assert part.K == k1 - k0
+            check_plan_order(part, k1 - k0)
+            assert np.array_equal(unsort(part), whole[k0:k1])

@@ -1,6 +1,7 @@
 """Self-consistency of the sparse oracle (its parity with MinkowskiEngine is unpinned): the sparse
 convolution must equal a dense torch conv3d on the active sites; BN fold vs torch BatchNorm1d; voxelisation laws."""
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -114,3 +115,101 @@ def test_voxelize_laws(oracle):
     perm = np.random.default_rng(0).permutation(len(pts))
     v3 = oracle.voxelize(c4[perm])
     assert np.array_equal(v3["keys"], v["keys"]) and np.array_equal(v3["inverse"], v["inverse"][perm])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# key range and key packing (include/sv_hip.h: voxel coordinates in [-2^17, 2^17 - 1] per axis, batch in [0, 1023])
+# ------------------------------------------------------------------------------------------------------------------
+LO, HI = -(1 << 17), (1 << 17) - 1
+
+
+def _key_by_bits(b, x, y, z):
+    """the key definition of include/sv_hip.h, bit by bit on Python ints (shares no code with the oracle)"""
+    k = 0
+    for j in range(18):
+        k |= (((x + (1 << 17)) >> j) & 1) << (3 * j)
+        k |= (((y + (1 << 17)) >> j) & 1) << (3 * j + 1)
+        k |= (((z + (1 << 17)) >> j) & 1) << (3 * j + 2)
+    return k | (b << 54)
+
+
+def _full_range_voxels(rng, n):
+    return np.concatenate([rng.choice([0, 1, 511, 1022, 1023], size=(n, 1)), rng.integers(LO, HI + 1, size=(n, 3))], axis=1)
+
+
+def test_make_keys_equals_the_bitwise_definition(oracle):
+    corners = [(b, x, y, z) for b in (0, 1023) for x in (LO, HI) for y in (LO, HI) for z in (LO, HI)]
+    vox = np.concatenate([np.array(corners), _full_range_voxels(np.random.default_rng(0), 300)])
+    got = oracle.make_keys(vox)
+    assert got.dtype == np.uint64
+    assert [int(k) for k in got] == [_key_by_bits(*map(int, v)) for v in vox]
+    assert int(oracle.make_keys(np.array([[1023, HI, HI, HI]]))[0]) == (1 << 64) - 1  # every key bit is in use
+    assert int(oracle.make_keys(np.array([[0, LO, LO, LO]]))[0]) == 0
+
+
+def test_key_order_is_batch_then_morton(oracle):
+    vox = np.unique(_full_range_voxels(np.random.default_rng(1), 400), axis=0)
+    vox = vox[np.random.default_rng(2).permutation(len(vox))]
+    morton = [_key_by_bits(0, *map(int, v[1:])) for v in vox]
+    want = sorted(range(len(vox)), key=lambda i: (int(vox[i, 0]), morton[i]))
+    assert np.argsort(oracle.make_keys(vox), kind="stable").tolist() == want
+    assert np.array_equal(oracle.voxelize(vox, coords_are_int=True)["coords"], vox[want])
+
+
+def test_key_range_edges_are_accepted(oracle):
+    edge = np.array([[0, LO, HI, 0], [1023, HI, LO, LO]])
+    assert np.array_equal(oracle.voxelize(edge, coords_are_int=True)["coords"], edge)
+    f = np.array([[-0.0, -131072.0, -131071.5, np.nextafter(np.float32(131072), np.float32(0))],
+                  [1023.0, -0.0, -1e-7, 0.99999994]], np.float32)
+    assert np.array_equal(oracle.voxelize(f)["coords"], [[0, LO, LO, HI], [1023, 0, -1, 0]])
+
+
+@pytest.mark.parametrize("row", [(0, HI + 1, 0, 0), (0, 0, LO - 1, 0), (0, 0, 0, HI + 1), (-1, 0, 0, 0), (1024, 0, 0, 0)])
+def test_out_of_range_int_rows_raise(oracle, row):
+    vox = np.array([[0, 1, 2, 3], row])
+    with pytest.raises(ValueError):
+        oracle.make_keys(vox)
+    with pytest.raises(ValueError):
+        oracle.voxelize(vox, coords_are_int=True)
+
+
+@pytest.mark.parametrize("row", [(0, 131072.0, 0, 0), (0, 0, -131072.5, 0), (0, 0, 0, -131073.0), (-0.5, 0, 0, 0), (-1, 0, 0, 0),
+                                 (1024, 0, 0, 0), (np.nan, 0, 0, 0), (0, np.nan, 0, 0), (0, 0, np.inf, 0), (0, 0, 0, -np.inf),
+                                 (0, 1e30, 0, 0)])
+def test_out_of_range_float_rows_raise(oracle, row):
+    with pytest.raises(ValueError):
+        oracle.voxelize(np.array([[0, 1.5, 2.5, 3.5], row], np.float32))
+
+
+def test_kernel_map_does_not_wrap_at_the_range_edge(oracle):
+    """the key holds 18 bits per axis: x = 131071 + 1 would alias x = -131072 if the range check were missing"""
+    coords = oracle.voxelize(np.array([[3, HI, 7, -9], [3, LO, 7, -9], [3, HI - 1, 7, -9], [3, LO + 1, 7, -9]]),
+                             coords_are_int=True)["coords"]
+    nbr = oracle.kernel_map_k3(coords, 1)
+    row = {tuple(c): i for i, c in enumerate(coords.tolist())}
+    hi, lo = row[(3, HI, 7, -9)], row[(3, LO, 7, -9)]
+    assert nbr[14, hi] == -1 and nbr[12, lo] == -1          # +x of the last voxel, -x of the first
+    assert nbr[12, hi] == row[(3, HI - 1, 7, -9)] and nbr[14, lo] == row[(3, LO + 1, 7, -9)]
+    assert (nbr[13] == np.arange(4)).all() and (nbr >= 0).sum() == 4 + 4
+
+
+def _kernel_map_by_dict(coords, step):
+    row = {tuple(c): i for i, c in enumerate(coords.tolist())}
+    nbr = np.full((27, len(coords)), -1, np.int32)
+    for o, (b, x, y, z) in enumerate(coords.tolist()):
+        for k in range(27):
+            nbr[k, o] = row.get((b, x + (k % 3 - 1) * step, y + (k // 3 % 3 - 1) * step, z + (k // 9 - 1) * step), -1)
+    return nbr
+
+
+@pytest.mark.parametrize("ts,dilation", [(1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (2, 3)])
+def test_kernel_map_dilation_and_tensor_stride_equal_a_dictionary_lookup(oracle, ts, dilation):
+    rng = np.random.default_rng(10 * ts + dilation)
+    coords = _random_sparse(rng, n=900, extent=7)
+    coords[:, 1:] *= ts
+    coords = oracle.voxelize(coords, coords_are_int=True)["coords"]
+    got = oracle.kernel_map_k3(coords, ts, dilation)
+    assert np.array_equal(got, _kernel_map_by_dict(coords, ts * dilation))
+    assert (got >= 0).sum() > 3 * len(coords)  # the lookup is not vacuous
+    if dilation > 1:
+        assert not np.array_equal(got, oracle.kernel_map_k3(coords, ts, 1))

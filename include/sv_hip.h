@@ -66,7 +66,7 @@ const char* sv_last_error(void);
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
- *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9 */
+ *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -459,6 +459,49 @@ int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const floa
                        const double* init_T, double max_distance, int max_iterations, double rel_fitness,
                        double rel_rmse, void* workspace, size_t workspace_bytes, double* out_T, double* out_stats,
                        sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188
+ *      compute_pose_loss, :190-209 compute_shape_match_loss, :211-227 compute_pose_match_loss, :229-249
+ *      compute_kp_pose_match_loss; call sites train.py:89,189 and train_kp_to_pose.py:297).  Additions of ABI 4.
+ *
+ *   points float32[M][3]; instance b owns rows offsets[b] .. offsets[b+1]-1 (offsets int32[B+1], as sv_batch_offsets
+ *   writes it: non-decreasing, inside [0, M]; anything else is clamped into [0, M] so that no access leaves the arrays,
+ *   with unspecified results).  weights float32[M] or NULL (= 1); mask uint8[M] or NULL (= all rows): a row whose mask
+ *   byte is 0 contributes nothing, whatever its point and weight hold, and is nobody's match.  R, R_pred float32[B][9]
+ *   row-major (target, prediction); t, t_pred float32[B][3], both given or both NULL (= no translation).
+ *   With n_b the number of unmasked rows of instance b, p_j such a row, a_j = R_pred[b] p_j (+ t_pred[b]) and
+ *   b_j = R[b] p_j (+ t[b]):
+ *     SV_LOSS_POSE           r_j = a_j - b_j                                  loss[b] = sum_j w_j^2 |r_j|^2 / (2 n_b)
+ *     SV_LOSS_SHAPE_MATCH    r_j = a_j - b_k*, k* = argmin_k |a_j - b_k|^2 over the instance's unmasked rows, ties to
+ *                            the lowest k                                     loss[b] = sum_j w_j^2 |r_j|^2 / (2 n_b)
+ *     SV_LOSS_POSE_MATCH     r_j = a_j - b_j                                  loss[b] = sum_j |r_j|_1 / n_b
+ *     SV_LOSS_KP_POSE_MATCH  r_j = a_j - b_j                                  loss[b] = sum_j w_j^2 |r_j|^2 / (2 n_b)
+ *   (the reference calls POSE and SHAPE_MATCH without a translation and without weights, POSE_MATCH and KP_POSE_MATCH
+ *   with the translation, KP_POSE_MATCH with weights; POSE_MATCH with weights is refused.)
+ *   grad_R float32[B][9] = d loss[b] / d R_pred[b] = sum_j g_j p_j^T / n_b and grad_t float32[B][3] =
+ *   d loss[b] / d t_pred[b] = sum_j g_j / n_b, with g_j = w_j^2 r_j for the squared terms and sign(r_j), sign(0) = 0,
+ *   for the L1 term; k* is a constant of the differentiation; either may be NULL, grad_t must be NULL when t is.
+ *   match int32[M] or NULL, SHAPE_MATCH only: k* of every row of an instance, relative to the instance's first row
+ *   (-1 for a masked-out row and for a row whose distances are all NaN).
+ *   Arithmetic: the float32 inputs are promoted to float64; transforms ((R0 x + R1 y) + R2 z, then + t), distances
+ *   ((dx^2 + dy^2) + dz^2, the search included), terms and sums are float64 without fma; loss, grad_R and grad_t are
+ *   the float64 results rounded once to float32.  Sums run in a fixed order without atomics: the same inputs give the
+ *   same bits, and identical poses (R_pred = R, t_pred = t bit for bit) give exactly 0 everywhere.
+ *   n_b = 0 gives NaN for that instance's loss and gradients (the reference's 0 / 0).  A NaN or inf among an instance's
+ *   unmasked inputs makes that instance's outputs non-finite and changes no bit of any other instance.
+ *   B in [1, SV_MAX_BATCH], M in [0, 2^24); a bad mode, a null pointer, t without t_pred or a short workspace is refused
+ *   on the host before any HIP call.  workspace: sv_pose_loss_workspace_bytes(M, B).  No host read-back.
+ * ------------------------------------------------------------------------------------------- */
+#define SV_LOSS_POSE 0
+#define SV_LOSS_SHAPE_MATCH 1
+#define SV_LOSS_POSE_MATCH 2
+#define SV_LOSS_KP_POSE_MATCH 3
+size_t sv_pose_loss_workspace_bytes(int64_t M, int B);
+int sv_pose_match_loss(const float* points, const int32_t* offsets, int64_t M, int B, const float* weights,
+                       const uint8_t* mask, const float* R, const float* t, const float* R_pred, const float* t_pred,
+                       int mode, void* workspace, size_t workspace_bytes, float* loss, float* grad_R, float* grad_t,
+                       int32_t* match, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,

@@ -22,6 +22,7 @@ SV_PN_MAX_LAYERS = 4
 SV_PN_MAX_SCALES = 4
 SV_BQ_MAX_RADII = 4
 SV_GROUP_SSG, SV_GROUP_MSG = 0, 1
+SV_LOSS_POSE, SV_LOSS_SHAPE_MATCH, SV_LOSS_POSE_MATCH, SV_LOSS_KP_POSE_MATCH = 0, 1, 2, 3
 SV_COORD_BIAS = 1 << 17
 SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
@@ -107,6 +108,8 @@ SIGNATURES = {
     "sv_icp_point2plane_workspace_bytes": (c_size_t, [c_int64]),
     "sv_icp_point2plane": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_double, c_int, c_double, c_double, _P, c_size_t, _P,
                                    _P, _P]),
+    "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_fps": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_interpolate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "sv_cluster_workspace_bytes": (c_size_t, [c_int64]),

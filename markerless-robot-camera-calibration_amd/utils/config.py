@@ -20,6 +20,8 @@ _DEFAULTS = {
     "STRUCTURE": {
         "m": 32, "block_reps": 2, "use_joint_angles": False, "bottleneck": True, "backbone": "minkunet",
         "encode_only": False, "compute_confidence": False,
+        "position_threshold": 0.03, "position_ignore_threshold": 0.05, "angle_diff_threshold": 0.24,
+        "angle_diff_ignore_threshold": 0.4, "disable_position": False, "disable_orientation": False,
     },
     "INFERENCE": {
         "ee_point_counts_threshold": 512, "icp_enabled": False, "num_of_dense_input_points": 2048,

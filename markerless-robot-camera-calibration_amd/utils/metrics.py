@@ -2,6 +2,7 @@
 
 compute_ADD_np            utils/metrics.py:139-150   (the reported pose accuracy)
 compute_rotational_diff   :153-165, compute_translational_diff :168-176
+compute_pose_dist         :18-48     (the training loops' distances; the cos2 criterion's confidence targets)
 compute_segmentation_metrics  :51-107 (accuracy / precision / recall per class, balanced accuracy) + mIoU, which the
                           reference never computes on this path (BASELINE.json asks for it).
 """
@@ -52,6 +53,24 @@ def compute_rotational_diff(q1, q2, degree=True):
 def compute_translational_diff(t1, t2, cm=True, method="euclidean"):
     dist = np.linalg.norm(np.asarray(t1) - np.asarray(t2)) if method == "euclidean" else -1
     return dist * 100 if cm else dist
+
+
+def compute_pose_dist(gt, pred, position_voxelization=1):
+    """utils/metrics.py:18-48 on [B, >=7] torch poses: (pose distance, position distance, quaternion distance up to sign,
+    rotation angle acos(2 dot^2 - 1)), positions scaled by position_voxelization first.  Unlike the reference, which
+    scales `gt` and `pred` in place, the arguments are left as they were."""
+    with torch.no_grad():
+        position = gt[:, :3] * position_voxelization
+        position_pred = pred[:, :3] * position_voxelization
+        orientation, orientation_pred = gt[:, 3:7], pred[:, 3:7]
+        gt_n = torch.nn.functional.normalize(orientation, p=2, dim=1)
+        pred_n = torch.nn.functional.normalize(orientation_pred, p=2, dim=1)
+        dist = torch.norm(torch.cat((position, gt[:, 3:]), dim=1) - torch.cat((position_pred, pred[:, 3:7]), dim=1), dim=1)
+        dist_position = torch.norm(position - position_pred, dim=1)
+        dist_orientation = torch.min(torch.norm(orientation - orientation_pred, dim=1),
+                                     torch.norm(orientation + orientation_pred, dim=1))
+        angle_diff = torch.acos(2 * (torch.sum(gt_n * pred_n, dim=1) ** 2) - 1)
+        return dist, dist_position, dist_orientation, angle_diff
 
 
 def _qmul(q, r):

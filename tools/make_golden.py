@@ -10,6 +10,9 @@ get_pred_center and get_key_point_predictions, are pure torch/numpy and never to
 
     python tools/make_golden.py          # rewrites tests/golden/{kabsch,quat_avg,add,fps,ball_query,preprocess}.npz
     python tools/make_golden.py pointnet2_msg    # only the named fixtures
+
+`pose_losses` imports the reference's utils/loss.py with `utils.config` replaced by a stub (_StubConfig) that carries the
+keys the criteria read: the real module parses sys.argv and creates directories when it is imported.
 """
 import os
 import sys
@@ -449,13 +452,115 @@ def gen_pointnet2_msg(rng):
     return out
 
 
+class _StubConfig:
+    """What the reference's utils/loss.py reads of utils.config.Config (the real module parses sys.argv and creates
+    directories on import): `cfg()` -> dict, `cfg.STRUCTURE.x` / `cfg.DATA.x` -> attributes; one shared instance."""
+    _d = {"STRUCTURE": {"compute_confidence": False, "disable_position": False, "disable_orientation": False,
+                        "position_threshold": 0.03, "position_ignore_threshold": 0.05, "angle_diff_threshold": 0.24,
+                        "angle_diff_ignore_threshold": 0.4, "backbone": "minkunet"},
+          "DATA": {"ignore_label": -100, "center_at_origin": False, "voxelize_position": True}}
+
+    def __call__(self):
+        return self._d
+
+    def __getattr__(self, name):
+        return types.SimpleNamespace(**self._d[name])
+
+
+def _ellipsoid_voxels(rng, n, radii):
+    """n distinct integer voxel coordinates on an ellipsoid shell"""
+    d = rng.normal(size=(4 * n, 3))
+    c = np.unique(np.rint(d / np.linalg.norm(d, axis=1, keepdims=True) * radii).astype(np.int32), axis=0)
+    return c[rng.permutation(len(c))[:n]]
+
+
+def gen_pose_losses(rng):
+    """The reference's ten criteria (utils/loss.py) and compute_pose_dist on CPU float32: loss and d loss / d y_pred for
+    both reductions; cos2 with and without its confidence terms."""
+    stub = types.ModuleType("utils.config")
+    stub.Config = _StubConfig
+    import utils as ref_utils
+
+    saved = sys.modules.get("utils.config"), getattr(ref_utils, "config", None)
+    sys.modules["utils.config"] = ref_utils.config = stub
+    try:
+        from utils import loss as L
+    finally:
+        if saved[0] is not None:
+            sys.modules["utils.config"] = saved[0]
+        if saved[1] is not None:
+            ref_utils.config = saved[1]
+    cfg = L._config
+    B = 3
+    # instance 0 close to its target (inside both confidence thresholds), 1 far (outside both ignore thresholds), 2 between
+    q = np.stack([rand_quat(rng) for _ in range(B)])
+    dq = rng.normal(size=(B, 4)) * np.array([0.02, 0.4, 0.12])[:, None]
+    y = np.concatenate([rng.uniform(-0.3, 0.3, (B, 3)), q * rng.uniform(0.7, 1.4, (B, 1))], axis=1).astype(np.float32)
+    dp = rng.normal(size=(B, 3))
+    dp = dp / np.linalg.norm(dp, axis=1, keepdims=True) * np.array([0.01, 0.2, 0.04])[:, None]
+    y_pred = np.concatenate([y[:, :3] + dp, (q + dq) * rng.uniform(0.7, 1.4, (B, 1))], axis=1).astype(np.float32)
+    y_pred10 = np.concatenate([y_pred, rng.uniform(0.1, 0.9, (B, 3))], axis=1).astype(np.float32)
+    coords = [_ellipsoid_voxels(rng, n, np.array([9.0, 6.0, 4.0])) for n in (300, 1, 157)]
+    N = 64
+    pn = rng.normal(size=(B, 7, N)).astype(np.float32)
+    kp = np.concatenate([rng.uniform(-0.2, 0.2, (B, 40, 3)), rng.normal(size=(B, 40, 1)),
+                         rng.uniform(0.05, 1.0, (B, 40, 1))], axis=2).astype(np.float32)
+    kp_labels = rng.integers(0, 6, size=(B, 40)).astype(np.int64)
+    kp_labels[rng.uniform(size=(B, 40)) < 0.3] = -100
+    kp_labels[1, :3], kp_labels[1, -2:] = -100, -100
+    out = {"y": y, "y_pred": y_pred, "y_pred10": y_pred10, "pointnet_x": pn, "kp_x": kp, "kp_labels": kp_labels,
+           "coords_offsets": np.cumsum([0] + [len(c) for c in coords]).astype(np.int32),
+           "coords": np.concatenate(coords).astype(np.int32)}
+    sparse_x = types.SimpleNamespace(decomposed_coordinates=[torch.from_numpy(c) for c in coords])
+    yt = torch.from_numpy(y)
+
+    def run(name, loss_type, pred, **kw):
+        for reduction in ("mean", "sum"):
+            crit = L.get_criterion(device="cpu", loss_type=L.LossType(loss_type), reduction=reduction)
+            p = torch.from_numpy(pred.copy()).requires_grad_(True)
+            loss = crit(yt.clone(), p, **kw)
+            loss.backward()
+            out[f"{name}_{reduction}_loss"] = np.float32(loss.item())
+            out[f"{name}_{reduction}_grad"] = p.grad.numpy().astype(np.float32)
+
+    for lt in ("mse", "cos", "angle", "cos2", "wgeodesic", "smoothl1"):
+        run(lt, lt, y_pred)
+    # cos2 with confidence: the reference's compute_pose_dist scales its arguments in place (`position *= 1`), which
+    # bumps the version of tensors the graph has saved, so its backward raises.  The forward value is taken as it is; for
+    # the gradient the same criterion runs with compute_pose_dist handed clones (same value, asserted).
+    cfg._d["STRUCTURE"]["compute_confidence"] = True
+    as_is = {r: L.get_criterion(device="cpu", loss_type=L.LossType.COS2, reduction=r)(
+        yt.clone(), torch.from_numpy(y_pred10.copy())).item() for r in ("mean", "sum")}
+    ref_dist = L.compute_pose_dist
+    L.compute_pose_dist = lambda gt, pred, **kw: ref_dist(gt.clone(), pred.clone(), **kw)
+    try:
+        run("cos2_confidence", "cos2", y_pred10)
+    finally:
+        L.compute_pose_dist = ref_dist
+    assert all(np.float32(as_is[r]) == out[f"cos2_confidence_{r}_loss"] for r in as_is)
+    cfg._d["STRUCTURE"]["compute_confidence"] = False
+    for lt in ("pose", "shape_match", "pose_match"):
+        run(lt, lt, y_pred, x=sparse_x)
+    cfg._d["STRUCTURE"]["backbone"] = "pointnet2"
+    run("pose_pointnet", "pose", y_pred, x=torch.from_numpy(pn))
+    cfg._d["STRUCTURE"]["backbone"] = "minkunet"
+    run("kp_pose_match", "kp_pose_match", y_pred, x=torch.from_numpy(kp), labels=torch.from_numpy(kp_labels))
+    run("kp_pose_match_nolabels", "kp_pose_match", y_pred, x=torch.from_numpy(kp))
+    for v in (1, 4):
+        d = Mx.compute_pose_dist(yt.clone(), torch.from_numpy(y_pred10.copy()), position_voxelization=v)
+        for k, a in zip(("dist", "dist_position", "dist_orientation", "angle_diff"), d):
+            out[f"pose_dist_v{v}_{k}"] = a.numpy().astype(np.float32)
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
                            ("fps", gen_fps, 103), ("ball_query", gen_ball_query, 104),
                            ("preprocess", gen_preprocess, 105), ("metrics", gen_metrics, 106),
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
-                           ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110)]:
+                           ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110),
+                           ("pose_losses", gen_pose_losses, 111)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))

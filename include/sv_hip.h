@@ -66,7 +66,7 @@ const char* sv_last_error(void);
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
- *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4 */
+ *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -502,6 +502,91 @@ int sv_pose_match_loss(const float* points, const int32_t* offsets, int64_t M, i
                        const uint8_t* mask, const float* R, const float* t, const float* R_pred, const float* t_pred,
                        int mode, void* workspace, size_t workspace_bytes, float* loss, float* grad_R, float* grad_t,
                        int32_t* match, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N5  training-time augmentation and batched quantisation (replace utils/augmentation.py:14-33 distort_elastic, :49-75
+ *      add_noise / transform_random / flip_random / rotate_along_gravity, :108-138 augment_segmentation, called per
+ *      frame at data/alivev2.py:273-279, and the centring + ME.utils.sparse_quantize + collate that follow it,
+ *      data/alivev2.py:199-208,290-296,358-365).  Additions of ABI 4.  The random draws are the caller's: nothing here
+ *      draws a number, so the same arguments give the same bits.
+ *
+ * sv_elastic_field: the blurred displacement fields of distort_elastic:15-26.  raw, out float32: F fields one after the
+ *   other, field f being [3][bx][by][bz] with (bx, by, bz) = dims[3f .. 3f+2]; dims is a HOST array (int32[F][3]), every
+ *   entry in [3, 1024], F in [1, 2 * SV_MAX_BATCH].  Each component goes through six 3-tap box blurs along axes 0, 1, 2,
+ *   0, 1, 2 with zero padding (scipy.ndimage.convolve, mode='constant', cval=0): one pass computes
+ *   (a*w + b*w) + c*w in float64 with w = (double)(float)(1/3) and rounds once to float32, as scipy does, so the second
+ *   blur along an axis sees the first one's rounded, truncated result.  out must not alias raw.
+ *   workspace: sv_elastic_field_workspace_bytes(dims, F) (0 for arguments the call would refuse).
+ *
+ * sv_augment_points: points float32[N][3] (float64[N][3] with points_f64 != 0, for a caller that chains calls: the
+ *   reference's intermediate clouds are float64) of B frames, frame b owning rows offsets[b] .. offsets[b+1]-1 (int32[B+1],
+ *   non-decreasing inside [0, N]; anything else is clamped so that no access leaves the arrays).  table is
+ *   float64[B][SV_AUG_STRIDE] on the device, one row per frame (integers stored as float64):
+ *     SV_AUG_ELASTIC0 / SV_AUG_ELASTIC1 + SV_AUG_E_ON      stage enabled (0 / 1)
+ *                                       + SV_AUG_E_OFFSET  index in `fields` of the stage's field's first float
+ *                                       + SV_AUG_E_BX..BZ  its shape        + SV_AUG_E_GRAN, SV_AUG_E_MAG
+ *     SV_AUG_NOISE_ON, SV_AUG_NOISE_SIGMA, SV_AUG_NOISE_CLIP
+ *     SV_AUG_TRANSFORM_ON, SV_AUG_ROT (9, row-major), SV_AUG_TRANSLATION (3)
+ *     SV_AUG_FLIP_SIGN     0 = off, else the factor of x (+1 / -1)
+ *     SV_AUG_GRAVITY_ON, SV_AUG_GRAVITY_ANGLE (informative), SV_AUG_GRAVITY_COS, SV_AUG_GRAVITY_SIN (host cos / sin)
+ *   fields float32[fields_len]: the output of sv_elastic_field (may be NULL with fields_len = 0 when no stage is on);
+ *   noise float64[N][3] standard normal draws or NULL (then no frame gets noise).  Every step is float64 without fma, in
+ *   the reference's order:
+ *     elastic stage: p += mag * g(p), g = trilinear interpolation of the three components on the axes
+ *       np.linspace(-(b-1)*gran, (b-1)*gran, b) (nodes k * step + start, the last one = stop), cell k with
+ *       node(k) <= v < node(k+1), the upper edge inclusive, weights ((1 * wx) * wy) * wz summed in scipy's corner order;
+ *       a point outside the grid on any axis gets exactly zero displacement, a NaN coordinate makes its row NaN; the
+ *       second stage is evaluated at the positions the first produced.  A table row whose field does not lie inside
+ *       [0, fields_len) makes its frame's rows NaN instead of reading outside the buffer.
+ *     noise: p + clip(sigma * n, -clip, clip)
+ *     transform: (p @ rot + translation) @ rot^T, both products computed
+ *     flip: p @ diag(sign, 1, 1);  gravity: p @ [[c, 0, -s], [0, 1, 0], [s, 0, c]]^T, as full three-term products
+ *   out float64[N][3]; stats float64[B][6] = per-frame (min x, y, z, max x, y, z) of out, NaN if the column holds one
+ *   (numpy's min / max), (+inf, -inf) for a frame without rows.  B in [1, SV_MAX_BATCH], N in [0, 2^29).
+ *   workspace: sv_augment_points_workspace_bytes(N, B).
+ *
+ * sv_quantise_points: points float64[N][3] and offsets as above; stats as sv_augment_points wrote it.  origin selects what
+ *   is subtracted from frame b's rows first: SV_ORIGIN_NONE nothing, SV_ORIGIN_CENTER (max + min) / 2
+ *   (utils/preprocess.py:8-11), SV_ORIGIN_BASE min (:14-17) - read from stats on the device.  coords int32[N][4] =
+ *   (b, floor(p / quantization_size)) with the float64 division and floor of ME.utils.sparse_quantize, 16-byte aligned;
+ *   a NaN, an inf or a quotient outside int32 gives INT32_MIN, which sv_voxelize reports as out of range.
+ *   shifted float32[N][3] or NULL: the shifted points rounded once; shift_out float64[B][3] or NULL: what was subtracted.
+ *
+ * All three validate on the host before any HIP call and never read back.
+ * ------------------------------------------------------------------------------------------- */
+#define SV_AUG_STRIDE 40
+#define SV_AUG_ELASTIC0 0
+#define SV_AUG_ELASTIC1 7
+#define SV_AUG_E_ON 0
+#define SV_AUG_E_OFFSET 1
+#define SV_AUG_E_BX 2
+#define SV_AUG_E_BY 3
+#define SV_AUG_E_BZ 4
+#define SV_AUG_E_GRAN 5
+#define SV_AUG_E_MAG 6
+#define SV_AUG_NOISE_ON 14
+#define SV_AUG_NOISE_SIGMA 15
+#define SV_AUG_NOISE_CLIP 16
+#define SV_AUG_TRANSFORM_ON 17
+#define SV_AUG_ROT 18
+#define SV_AUG_TRANSLATION 27
+#define SV_AUG_FLIP_SIGN 30
+#define SV_AUG_GRAVITY_ON 31
+#define SV_AUG_GRAVITY_ANGLE 32
+#define SV_AUG_GRAVITY_COS 33
+#define SV_AUG_GRAVITY_SIN 34
+#define SV_ORIGIN_NONE 0
+#define SV_ORIGIN_CENTER 1
+#define SV_ORIGIN_BASE 2
+size_t sv_elastic_field_workspace_bytes(const int32_t* dims, int F);
+int sv_elastic_field(const float* raw, const int32_t* dims, int F, void* workspace, size_t workspace_bytes, float* out,
+                     sv_stream_t stream);
+size_t sv_augment_points_workspace_bytes(int64_t N, int B);
+int sv_augment_points(const void* points, int points_f64, const int32_t* offsets, int64_t N, int B, const double* table,
+                      const float* fields, int64_t fields_len, const double* noise, void* workspace,
+                      size_t workspace_bytes, double* out, double* stats, sv_stream_t stream);
+int sv_quantise_points(const double* points, const int32_t* offsets, int64_t N, int B, const double* stats, int origin,
+                       double quantization_size, int32_t* coords, float* shifted, double* shift_out, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,

@@ -1,4 +1,5 @@
-"""ME.utils: batched_coordinates, sparse_quantize, kaiming_normal_ (data/alivev2.py:290-296,363; resnet.py:89)."""
+"""ME.utils: batched_coordinates, sparse_quantize, sparse_collate, kaiming_normal_ (data/alivev2.py:290-296,363,391;
+resnet.py:89)."""
 from ctypes import c_int, c_int64, c_size_t
 
 import numpy as np
@@ -20,6 +21,35 @@ def batched_coordinates(coords, dtype=torch.int32, device=None):
         out.append(torch.cat([bc, c.to(dtype)], dim=1))
     res = torch.cat(out, dim=0) if out else torch.zeros((0, 4), dtype=dtype)
     return res.to(device) if device is not None else res
+
+
+def resolve_voxel_labels(lab, first, inverse, V, ignore_label):
+    """Label of every voxel: its representative point's (lab[first]), or ignore_label where the voxel's points disagree.
+    lab int64 [N], first int64 [V], inverse int64 [N], all on one device."""
+    rep = lab[first]
+    differs = torch.zeros(V, dtype=torch.bool, device=lab.device)
+    differs.index_put_((inverse,), lab != rep[inverse], accumulate=True)
+    return torch.where(differs, torch.full_like(rep, ignore_label), rep)
+
+
+def sparse_collate(coords, feats, labels=None, dtype=torch.int32, device=None):
+    """Lists of per-frame coordinates [N_i, 3], features [N_i, C] and (optionally) labels -> (batched coordinates
+    [sum N_i, 4], concatenated features, concatenated labels), as data/alivev2.py:391 collate_sparse expects; without
+    labels the pair (coordinates, features)."""
+    if len(coords) != len(feats) or (labels is not None and len(labels) != len(coords)):
+        raise ValueError("coords, feats and labels must list the same frames")
+    for i, (c, f) in enumerate(zip(coords, feats)):
+        if len(c) != len(f) or (labels is not None and len(labels[i]) != len(c)):
+            raise ValueError(f"frame {i}: one feature row (and one label) per coordinate row")
+    coords_batch = batched_coordinates(coords, dtype=dtype, device=device)
+
+    def cat(xs):
+        t = torch.cat([torch.as_tensor(x) for x in xs], dim=0)
+        return t.to(device) if device is not None else t
+
+    if labels is None:
+        return coords_batch, cat(feats)
+    return coords_batch, cat(feats), cat(labels)
 
 
 def sparse_quantize(coordinates, features=None, labels=None, ignore_label=-100, return_index=False,
@@ -54,11 +84,7 @@ def sparse_quantize(coordinates, features=None, labels=None, ignore_label=-100, 
         f = torch.as_tensor(features)
         res.append(back(f.to(dev)[first]) if not isinstance(features, np.ndarray) else features[first.cpu().numpy()])
     if labels is not None:
-        lab = torch.as_tensor(labels).to(dev).long()
-        rep = lab[first]
-        differs = torch.zeros(cmap.V, dtype=torch.bool, device=dev)
-        differs.index_put_((inverse,), lab != rep[inverse], accumulate=True)
-        out_lab = torch.where(differs, torch.full_like(rep, ignore_label), rep)
+        out_lab = resolve_voxel_labels(torch.as_tensor(labels).to(dev).long(), first, inverse, cmap.V, ignore_label)
         res.append(back(out_lab.to(torch.as_tensor(labels).dtype)))
     if return_index:
         res.append(back(first))

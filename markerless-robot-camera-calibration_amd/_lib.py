@@ -23,6 +23,11 @@ SV_PN_MAX_SCALES = 4
 SV_BQ_MAX_RADII = 4
 SV_GROUP_SSG, SV_GROUP_MSG = 0, 1
 SV_LOSS_POSE, SV_LOSS_SHAPE_MATCH, SV_LOSS_POSE_MATCH, SV_LOSS_KP_POSE_MATCH = 0, 1, 2, 3
+SV_AUG_STRIDE, SV_AUG_ELASTIC0, SV_AUG_ELASTIC1 = 40, 0, 7
+SV_AUG_E_ON, SV_AUG_E_OFFSET, SV_AUG_E_BX, SV_AUG_E_BY, SV_AUG_E_BZ, SV_AUG_E_GRAN, SV_AUG_E_MAG = range(7)
+SV_AUG_NOISE_ON, SV_AUG_NOISE_SIGMA, SV_AUG_NOISE_CLIP, SV_AUG_TRANSFORM_ON, SV_AUG_ROT, SV_AUG_TRANSLATION = 14, 15, 16, 17, 18, 27
+SV_AUG_FLIP_SIGN, SV_AUG_GRAVITY_ON, SV_AUG_GRAVITY_ANGLE, SV_AUG_GRAVITY_COS, SV_AUG_GRAVITY_SIN = 30, 31, 32, 33, 34
+SV_ORIGIN_NONE, SV_ORIGIN_CENTER, SV_ORIGIN_BASE = 0, 1, 2
 SV_COORD_BIAS = 1 << 17
 SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
@@ -110,6 +115,11 @@ SIGNATURES = {
                                    _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),
+    "sv_elastic_field": (c_int, [_P, _P, c_int, _P, c_size_t, _P, _P]),
+    "sv_augment_points_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "sv_augment_points": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, c_int64, _P, _P, c_size_t, _P, _P, _P]),
+    "sv_quantise_points": (c_int, [_P, _P, c_int64, c_int, _P, c_int, c_double, _P, _P, _P, _P]),
     "sv_fps": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_interpolate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "sv_cluster_workspace_bytes": (c_size_t, [c_int64]),

@@ -1,0 +1,150 @@
+"""Float64 numpy / scipy restatement of the reference's point augmentation (utils/augmentation.py:14-138) with explicit
+draws, for tests.  It shares no code with the package: scipy.ndimage.convolve and RegularGridInterpolator do the
+elastic stage, numpy the rest, in the reference's operation order.
+
+A frame's draws are a plain dict:
+    {"elastic": [(raw float32 [3, bx, by, bz], gran, mag), ...], "normals": float64 [n, 3] or None, "sigma", "clip",
+     "transform": (tr, rot [3, 3]) or None, "flip": +1 / -1 or None, "gravity": angle or None}
+The `seeded_*` functions make the draws from the global np.random state with the reference's calls in the reference's
+order, so that under the same np.random.seed they reproduce what the reference's own functions return.
+"""
+import numpy as np
+import scipy.interpolate
+import scipy.ndimage
+from scipy.stats import special_ortho_group
+
+SIGMA, CLIP = 0.0016, 0.005
+
+
+def rel_err(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    scale = float(np.abs(b).max()) if b.size else 0.0
+    return float(np.abs(a - b).max()) / scale if scale > 0 else float(np.abs(a - b).max() if b.size else 0.0)
+
+
+def no_draws():
+    return {"elastic": [], "normals": None, "sigma": SIGMA, "clip": CLIP, "transform": None, "flip": None, "gravity": None}
+
+
+def grid_shape(x, gran):
+    return tuple(int(v) for v in np.abs(x).max(0).astype(np.int32) // gran + 3)
+
+
+def stages(scale):
+    return (6 * scale // 50, 40 * scale / 50), (20 * scale // 50, 160 * scale / 50)
+
+
+def blur_field(raw):
+    """[3, bx, by, bz] float32 raw noise -> the three blurred float32 grids (six 3-tap box blurs: axes 0 1 2 0 1 2)"""
+    kernels = [np.ones(s).astype("float32") / 3 for s in ((3, 1, 1), (1, 3, 1), (1, 1, 3))]
+    noise = [np.asarray(n, dtype=np.float32) for n in raw]
+    for k in kernels + kernels:
+        noise = [scipy.ndimage.convolve(n, k, mode="constant", cval=0) for n in noise]
+    return noise
+
+
+def axes_of(shape, gran):
+    return [np.linspace(-(b - 1) * gran, (b - 1) * gran, b) for b in shape]
+
+
+def distort_elastic(x, gran, mag, raw, blurred=None):
+    noise = blur_field(raw) if blurred is None else blurred
+    ax = axes_of(noise[0].shape, gran)
+    interp = [scipy.interpolate.RegularGridInterpolator(ax, n, bounds_error=0, fill_value=0) for n in noise]
+    g = np.hstack([i(x)[:, None] for i in interp])
+    return x + g * mag
+
+
+def add_noise(x, normals, sigma=SIGMA, clip=CLIP):
+    return x + np.clip(sigma * normals, -1 * clip, clip)
+
+
+def transform_random(pc, tr, rot):
+    shifted = pc @ rot + np.array([[tr, 0, 0]])  # a shift along x in the rotated frame ...
+    return shifted @ rot.T  # ... and back
+
+
+def flip_random(pc, sign):
+    return np.matmul(pc, np.diag([float(sign), 1.0, 1.0]))
+
+
+def rotate_along_gravity(pc, angle):
+    c, s = np.cos(angle), np.sin(angle)
+    about_y = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+    return (about_y @ pc.T).T
+
+
+def apply_draws(points, d):
+    """A frame through the stages its draws enable, in augment_segmentation's order; float64 out."""
+    p = np.array(points, dtype=np.float64)
+    for raw, gran, mag in d["elastic"]:
+        p = distort_elastic(p, gran, mag, raw)
+    if d["normals"] is not None:
+        p = add_noise(p, d["normals"], d["sigma"], d["clip"])
+    if d["transform"] is not None:
+        p = transform_random(p, *d["transform"])
+    if d["flip"] is not None:
+        p = flip_random(p, d["flip"])
+    if d["gravity"] is not None:
+        p = rotate_along_gravity(p, d["gravity"])
+    return p
+
+
+def _draw_raw(x, gran):
+    bb = grid_shape(x, gran)
+    return np.stack([np.random.randn(*bb).astype("float32") for _ in range(3)])
+
+
+def seeded_single(name, x):
+    """(result, draws) of one of the reference's five functions with its draws taken from np.random"""
+    d = no_draws()
+    if name == "distort_elastic_1_4":
+        d["elastic"] = [(_draw_raw(x, 1), 1, 4)]
+    elif name == "distort_elastic_24_160":
+        d["elastic"] = [(_draw_raw(x, 24), 24, 160.0)]
+    elif name == "add_noise":
+        d["normals"] = np.random.randn(*x.shape)
+    elif name == "transform_random":
+        tr = np.random.rand() * 0.04
+        d["transform"] = (tr, special_ortho_group.rvs(3))
+    elif name == "flip_random":
+        d["flip"] = np.random.randint(0, 2) * 2 - 1
+    elif name == "rotate_along_gravity":
+        d["gravity"] = np.random.rand() * 2 * np.pi
+    else:
+        raise KeyError(name)
+    return apply_draws(x, d), d
+
+
+def seeded_augment(points, stage_list, probability, elastic, noise, transform, flip, gravity):
+    """(result, draws) of augment / augment_segmentation (stage_list = their distort_elastic calls' (gran, mag))"""
+    d = no_draws()
+    p = np.array(points, dtype=np.float64)
+    if elastic and np.random.rand() < probability:
+        for gran, mag in stage_list:
+            raw = _draw_raw(p, gran)
+            d["elastic"].append((raw, gran, mag))
+            p = distort_elastic(p, gran, mag, raw)
+    if noise and np.random.rand() < probability:
+        d["normals"] = np.random.randn(*p.shape)
+        p = add_noise(p, d["normals"])
+    if transform and np.random.rand() < probability:
+        tr = np.random.rand() * 0.04
+        d["transform"] = (tr, special_ortho_group.rvs(3))
+        p = transform_random(p, *d["transform"])
+    if flip and np.random.rand() < probability:
+        d["flip"] = np.random.randint(0, 2) * 2 - 1
+        p = flip_random(p, d["flip"])
+    if gravity and np.random.rand() < probability:
+        d["gravity"] = np.random.rand() * 2 * np.pi
+        p = rotate_along_gravity(p, d["gravity"])
+    return p, d
+
+
+def to_package_draws(d):
+    """the dict above as the package's AugmentationDraws"""
+    from mrcc_amd.utils.augmentation import AugmentationDraws, ElasticStage
+
+    return AugmentationDraws(elastic=[ElasticStage(raw, gran, mag) for raw, gran, mag in d["elastic"]],
+                             noise=d["normals"] is not None, normals=d["normals"], sigma=d["sigma"], clip=d["clip"],
+                             transform=d["transform"], flip=d["flip"], gravity=d["gravity"])

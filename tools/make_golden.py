@@ -12,7 +12,9 @@ get_pred_center and get_key_point_predictions, are pure torch/numpy and never to
     python tools/make_golden.py pointnet2_msg    # only the named fixtures
 
 `pose_losses` imports the reference's utils/loss.py with `utils.config` replaced by a stub (_StubConfig) that carries the
-keys the criteria read: the real module parses sys.argv and creates directories when it is imported.
+keys the criteria read: the real module parses sys.argv and creates directories when it is imported.  `augmentation`
+imports the reference's utils/augmentation.py with an empty `open3d` module beside the `ipdb` one (only
+change_background, which is not recorded, uses it).
 """
 import os
 import sys
@@ -553,6 +555,45 @@ def gen_pose_losses(rng):
     return out
 
 
+AUG_SINGLES = ("distort_elastic_1_4", "distort_elastic_24_160", "add_noise", "transform_random", "flip_random",
+               "rotate_along_gravity")
+AUG_FLAGS = dict(elastic=True, noise=True, transform=True, flip=True, gravity=True)
+
+
+def gen_augmentation(rng):
+    """The reference's utils/augmentation.py under fixed np.random seeds: every function alone, augment, and
+    augment_segmentation with all flags at probability 1.0 and 0.5 with scale=200 on a metre-sized cloud (3^3 grids) and
+    on a voxel-sized one (larger grids).  `open3d` (only change_background uses it) is an empty module."""
+    sys.modules.setdefault("open3d", types.ModuleType("open3d"))
+    from utils import augmentation as A
+
+    cloud_m = rng.uniform(-0.8, 0.8, (600, 3)).astype(np.float32)
+    cloud_v = rng.uniform(-150, 150, (400, 3)).astype(np.float32)
+    cloud_s = rng.uniform(-40, 40, (250, 3)).astype(np.float32)
+    out = {"cloud_m": cloud_m, "cloud_v": cloud_v, "cloud_s": cloud_s, "single_names": np.array(AUG_SINGLES)}
+    calls = {"distort_elastic_1_4": lambda x: A.distort_elastic(x, 1, 4),
+             "distort_elastic_24_160": lambda x: A.distort_elastic(x, 24, 160.0),
+             "add_noise": A.add_noise, "transform_random": A.transform_random, "flip_random": A.flip_random,
+             "rotate_along_gravity": A.rotate_along_gravity}
+    seeds = []
+    for i, name in enumerate(AUG_SINGLES):
+        np.random.seed(1000 + i)
+        seeds.append(1000 + i)
+        out["single_" + name] = np.asarray(calls[name](np.array(cloud_s)), dtype=np.float64)
+    out["single_seeds"] = np.array(seeds, dtype=np.int64)
+    np.random.seed(2000)
+    out["augment_p1"] = np.asarray(A.augment(np.array(cloud_s), probability=1.0, copy=True, **AUG_FLAGS), dtype=np.float64)
+    cases = []
+    for ci, cloud in enumerate((cloud_m, cloud_v)):
+        for prob, seed in ((1.0, 3000), (0.5, 3001), (0.5, 3007)):  # under seed 3007 the elastic stage does not fire
+            np.random.seed(seed)
+            res = A.augment_segmentation(np.array(cloud), scale=200, probability=prob, copy=True, **AUG_FLAGS)
+            out[f"seg_{ci}_{seed}"] = np.asarray(res, dtype=np.float64)
+            cases.append((ci, prob, seed))
+    out["seg_cases"] = np.array(cases, dtype=np.float64)
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
@@ -560,7 +601,7 @@ def main():
                            ("preprocess", gen_preprocess, 105), ("metrics", gen_metrics, 106),
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
                            ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110),
-                           ("pose_losses", gen_pose_losses, 111)]:
+                           ("pose_losses", gen_pose_losses, 111), ("augmentation", gen_augmentation, 112)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))

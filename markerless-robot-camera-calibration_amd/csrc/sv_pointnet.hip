@@ -8,6 +8,8 @@
 //  sv_pointnet_sa_msg <- model/pointnet2_utils.py:207-264 PointNetSetAbstractionMsg.forward: the R scales of one
 //                    multi-scale layer (grouping [points[idx], xyz[idx] - new_xyz], :247-250; nsample up to 128) in one
 //                    launch, every scale's pooled rows written into its columns of the concatenated output (:262).
+// Both entries run one kernel body, pointnet_sa_kernel<MSG>: single-scale is its one-scale, one-pass instance in the
+// SV_GROUP_SSG row layout.  The grouped element itself (pn_group_element, sv_pointnet_dev.h) is sv_group_rows' too.
 //
 // Work decomposition
 //   * a workgroup (4 waves) owns PN_ROWS = 64 rows = 64 / nsample centroids x nsample neighbours;
@@ -24,6 +26,7 @@
 #include <atomic>
 
 #include "sv_common.h"
+#include "sv_pointnet_dev.h"
 
 namespace sv {
 
@@ -46,17 +49,26 @@ struct PnLayer {
   int64_t w, scale, shift;  // offsets into the packed parameter buffer (floats)
 };
 
+// One scale: a ball (group_idx, nsample), its layers and parameters, and where its work and its output sit in the launch.
+struct PnScale {
+  const int64_t* idx;
+  const float* params;
+  int nsample, L, col;  // col: first column of the scale in the [B][S][ctot] output
+  int buf1;  // float offset of the scale's second LDS buffer
+  int run;   // float offset of the running maxima (two-pass balls)
+  int64_t blk0;  // first workgroup of the scale
+  PnLayer layer[SV_PN_MAX_LAYERS];
+};
+
+template <int MAXR>
 struct PnParams {
   const float* xyz;
   const float* points;
   const float* new_xyz;
-  const int64_t* idx;
-  const float* params;
   float* out;
-  int N, S, D, nsample, L;
+  int N, S, D, R, ctot;
   int64_t nq;  // B * S
-  int buf1;    // float offset of the second LDS buffer
-  PnLayer layer[SV_PN_MAX_LAYERS];
+  PnScale sc[MAXR];
 };
 
 template <int MR, int NT>
@@ -168,127 +180,50 @@ __device__ __forceinline__ void pn_layer_any(const float* params, const PnLayer&
   }
 }
 
-__global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* bufs[2] = {lds, lds + p.buf1};
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ns = p.nsample;
-  const int tc = PN_ROWS / ns;  // centroids per workgroup
-  const int64_t q0 = (int64_t)blockIdx.x * tc;
-  // ---- gather: row r = (centroid q0 + r / ns, neighbour r % ns) -> [xyz[idx] - new_xyz, points[idx], 0 ...]
-  {
-    const PnLayer& l0 = p.layer[0];
-    const int c_real = 3 + p.D;
-    float* dst = bufs[0];
-    for (int e = tid; e < PN_ROWS * l0.kpad; e += PN_THREADS) {
-      const int r = e / l0.kpad, c = e - r * l0.kpad;
-      const int64_t q = q0 + r / ns;
-      float v = 0.f;
-      if (q < p.nq && c < c_real) {
-        const int64_t b = q / p.S;
-        const int64_t j = p.idx[q * ns + r % ns];
-        const int64_t row = b * p.N + j;
-        if (j < 0 || j >= p.N)
-          v = NAN;  // an index outside the cloud (an empty ball's N) reads nothing: a NaN row, as sv_group_rows
-        else if (c < 3)
-          v = __fsub_rn(p.xyz[row * 3 + c], p.new_xyz[q * 3 + c]);
-        else
-          v = p.points[row * p.D + (c - 3)];
-      }
-      dst[r * l0.sa_in + c] = v;
-    }
-  }
-  __syncthreads();
-  // ---- layers: layer l reads bufs[l & 1], writes bufs[(l + 1) & 1]
-  for (int l = 0; l < p.L; ++l) {
-    const bool last = l == p.L - 1;
-    pn_layer_any(p.params, p.layer[l], bufs[l & 1], bufs[(l + 1) & 1], last, wave, lane);
-    __syncthreads();
-  }
-  // ---- max over the sub-tiles of each centroid
-  const int cout = p.layer[p.L - 1].cout;
-  const float* part = bufs[p.L & 1];
-  const int nsub = ns / 16;
-  for (int e = tid; e < tc * cout; e += PN_THREADS) {
-    const int cl = e / cout, c = e - cl * cout;
-    const int64_t q = q0 + cl;
-    if (q >= p.nq) continue;
-    float m = part[(cl * nsub) * cout + c];
-    for (int j = 1; j < nsub; ++j) {
-      const float o = part[(cl * nsub + j) * cout + c];
-      m = (o > m || o != o) ? o : m;
-    }
-    p.out[q * cout + c] = m;
-  }
-}
-
-// ---- multi-scale grouping (PointNetSetAbstractionMsg): R scales over the same centroids in ONE launch.  Workgroups
-// blk0[r] .. blk0[r + 1] - 1 serve scale r, each with its own ball (group_idx_r, nsample_r), layers and parameters; LDS is
-// sized for the largest scale.  Differences from pointnet_sa_kernel:
-//   * the gather follows the MSG row layout [points[idx], xyz[idx] - new_xyz, 0 ...] (features first);
-//   * nsample 128: a centroid is two 64-row passes; pass 0's per-channel maxima wait in LDS (`run`, [C_last]) and pass 1
-//     folds its own into them with the same NaN-propagating rule;
-//   * scale r writes its pooled rows into columns col_r .. col_r + C_r of the [B][S][sum C_r] output (no cat).
-struct PnScale {
-  const int64_t* idx;
-  const float* params;
-  int nsample, L, col;
-  int buf1;  // float offset of the scale's second LDS buffer
-  int run;   // float offset of the running maxima (two-pass balls)
-  int64_t blk0;  // first workgroup of the scale
-  PnLayer layer[SV_PN_MAX_LAYERS];
-};
-
-struct PnMsgParams {
-  const float* xyz;
-  const float* points;
-  const float* new_xyz;
-  float* out;
-  int N, S, D, R, ctot;
-  int64_t nq;
-  PnScale sc[SV_PN_MAX_SCALES];
-};
-
-__global__ __launch_bounds__(PN_THREADS) void pointnet_sa_msg_kernel(const PnMsgParams p) {
+// The set abstraction of R scales over the same centroids in ONE launch.  Workgroups blk0[r] .. blk0[r + 1] - 1 serve
+// scale r, each with its own ball (group_idx_r, nsample_r), layers and parameters; LDS is sized for the largest scale.
+// A ball of up to 64 neighbours is one pass of 64 / nsample centroids per workgroup; nsample 128 is one centroid in two
+// 64-row passes: pass 0's per-channel maxima wait in LDS (`run`, [C_last]) and pass 1 folds its own into them with the
+// same NaN-propagating rule.  Scale r writes its pooled rows into columns col_r .. col_r + C_r of the [B][S][sum C_r]
+// output (no cat).
+//   MSG = false (sv_pointnet_sa): one scale in the row layout SV_GROUP_SSG, one pass - the scale lookup and the pass
+//   loop fold away at compile time, which keeps this instance's registers (and so its occupancy) below the other's;
+//   MSG = true (sv_pointnet_sa_msg): up to SV_PN_MAX_SCALES scales in the row layout SV_GROUP_MSG, one or two passes.
+template <bool MSG>
+__global__ __launch_bounds__(PN_THREADS) void pointnet_sa_kernel(const PnParams<MSG ? SV_PN_MAX_SCALES : 1> p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int r = 0;
-  while (r + 1 < p.R && (int64_t)blockIdx.x >= p.sc[r + 1].blk0) ++r;
+  if (MSG)
+    while (r + 1 < p.R && (int64_t)blockIdx.x >= p.sc[r + 1].blk0) ++r;
   const PnScale& sc = p.sc[r];
   float* bufs[2] = {lds, lds + sc.buf1};
   float* run = lds + sc.run;
   const int ns = sc.nsample;
-  const int rows_c = ns < PN_ROWS ? ns : PN_ROWS;  // rows of one centroid in one pass
-  const int tc = PN_ROWS / rows_c;                 // centroids per workgroup
-  const int npass = ns / rows_c;
-  const int64_t q0 = ((int64_t)blockIdx.x - sc.blk0) * tc;
+  const int rows_c = MSG && ns > PN_ROWS ? PN_ROWS : ns;  // rows of one centroid in one pass
+  const int tc = PN_ROWS / rows_c;                         // centroids per workgroup
+  const int npass = MSG ? ns / rows_c : 1;
+  const int64_t q0 = ((int64_t)blockIdx.x - (MSG ? sc.blk0 : 0)) * tc;
   const int cout = sc.layer[sc.L - 1].cout;
   const int nsub = rows_c / 16;
+  __builtin_assume(sc.idx != nullptr);  // the entry points check it: pn_group_element's group_all branch is not built
   for (int pass = 0; pass < npass; ++pass) {
-    // ---- gather: row rr = (centroid q0 + rr / rows_c, neighbour pass * rows_c + rr % rows_c)
+    // ---- gather: row rr = (centroid q0 + rr / rows_c, neighbour pass * rows_c + rr % rows_c), zero-padded to kpad
     {
       const PnLayer& l0 = sc.layer[0];
       const int c_real = p.D + 3;
-      float* dst = bufs[0];
       for (int e = tid; e < PN_ROWS * l0.kpad; e += PN_THREADS) {
         const int rr = e / l0.kpad, c = e - rr * l0.kpad;
         const int64_t q = q0 + rr / rows_c;
         float v = 0.f;
-        if (q < p.nq && c < c_real) {
-          const int64_t b = q / p.S;
-          const int64_t j = sc.idx[q * ns + pass * rows_c + rr % rows_c];
-          const int64_t row = b * p.N + j;
-          if (j < 0 || j >= p.N)
-            v = NAN;  // an index outside the cloud (an empty ball's N) reads nothing: a NaN row, as sv_group_rows
-          else if (c < p.D)
-            v = p.points[row * p.D + c];
-          else
-            v = __fsub_rn(p.xyz[row * 3 + (c - p.D)], p.new_xyz[q * 3 + (c - p.D)]);
-        }
-        dst[rr * l0.sa_in + c] = v;
+        if (q < p.nq && c < c_real)
+          v = pn_group_element(p.xyz, p.points, p.new_xyz, sc.idx, q / p.S, q, pass * rows_c + rr % rows_c, ns, p.N, p.D,
+                               MSG ? SV_GROUP_MSG : SV_GROUP_SSG, c);
+        bufs[0][rr * l0.sa_in + c] = v;
       }
     }
     __syncthreads();
+    // ---- layers: layer l reads bufs[l & 1], writes bufs[(l + 1) & 1]
     for (int l = 0; l < sc.L; ++l) {
       pn_layer_any(sc.params, sc.layer[l], bufs[l & 1], bufs[(l + 1) & 1], l == sc.L - 1, wave, lane);
       __syncthreads();
@@ -369,96 +304,95 @@ static int pn_plan(const char* fn, const int* widths, int L, PnLayer* layer, int
   return SV_OK;
 }
 
+// Validates and plans one scale (widths [L + 1], ns neighbours, over nq centroids of D features) for entry point fn, which
+// takes balls of up to max_ns neighbours: fills sc but for its device pointers and appends the scale to the launch - its
+// columns to ctot, its workgroups to blocks, its LDS need to lds_bytes (the maximum over the scales).
+static int pn_plan_scale(const char* fn, int max_ns, const int* widths, int L, int ns, int D, int64_t nq, PnScale& sc,
+                         int& ctot, int64_t& blocks, size_t& lds_bytes) {
+  const bool msg = max_ns > PN_ROWS;
+  if (L < 1 || L > SV_PN_MAX_LAYERS) {
+    set_error("%s: %s", fn, "layer count outside 1..SV_PN_MAX_LAYERS");
+    return SV_ERR_UNSUPPORTED;
+  }
+  if (widths[0] != 3 + D) {
+    set_error("%s: %s", fn, msg ? "widths[0] of every scale must be 3 + D" : "widths[0] must be 3 + D");
+    return SV_ERR_INVALID;
+  }
+  if ((ns != 16 && ns != 32 && ns != 64 && ns != 128) || ns > max_ns) {
+    set_error("%s: %s", fn, msg ? "nsample must be 16, 32, 64 or 128" : "nsample must be 16, 32 or 64");
+    return SV_ERR_UNSUPPORTED;
+  }
+  int64_t need[2];
+  const int rc = pn_plan(fn, widths, L, sc.layer, need);
+  if (rc != SV_OK) return rc;
+  const int64_t cout = widths[L];
+  const int64_t floats = need[0] + need[1] + (ns > PN_ROWS ? cout : 0);  // + running maxima of a two-pass ball
+  const size_t bytes = (size_t)floats * sizeof(float);
+  if (bytes > PN_LDS_MAX) {
+    set_error("%s: %s", fn, "layer widths exceed the LDS of one CU");
+    return SV_ERR_UNSUPPORTED;
+  }
+  if (bytes > lds_bytes) lds_bytes = bytes;
+  sc.nsample = ns; sc.L = L; sc.col = ctot;
+  sc.buf1 = (int)need[0];
+  sc.run = (int)(need[0] + need[1]);
+  ctot += (int)cout;
+  const int tc = PN_ROWS / (ns < PN_ROWS ? ns : PN_ROWS);
+  sc.blk0 = blocks;
+  blocks += (nq + tc - 1) / tc;
+  return SV_OK;
+}
+
+template <bool MSG, int MAXR>
+static int pn_launch(const PnParams<MAXR>& p, int64_t blocks, size_t lds_bytes, hipStream_t stream) {
+  static std::atomic<bool> attr_set[64];
+  const int arc = pn_allow_lds((const void*)pointnet_sa_kernel<MSG>, attr_set, 64);
+  if (arc != SV_OK) return arc;
+  hipLaunchKernelGGL(pointnet_sa_kernel<MSG>, dim3((unsigned)blocks), dim3(PN_THREADS), lds_bytes, stream, p);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 extern "C" int sv_pointnet_sa(const float* xyz, const float* points, const float* new_xyz, const int64_t* group_idx, int B,
                               int N, int D, int S, int nsample, const float* params, const int* widths, int L, float* out,
                               sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1 && D >= 0, "bad shape");
   SV_CHECK_ARG(widths, "null pointer");
-  if (L < 1 || L > SV_PN_MAX_LAYERS) {
-    set_error("%s: %s", __func__, "layer count outside 1..SV_PN_MAX_LAYERS");
-    return SV_ERR_UNSUPPORTED;
-  }
-  SV_CHECK_ARG(widths[0] == 3 + D, "widths[0] must be 3 + D");
-  if (nsample != 16 && nsample != 32 && nsample != 64) {
-    set_error("%s: %s", __func__, "nsample must be 16, 32 or 64");
-    return SV_ERR_UNSUPPORTED;
-  }
-  PnParams p;
-  p.N = N; p.S = S; p.D = D; p.nsample = nsample; p.L = L;
+  PnParams<1> p;
+  p.N = N; p.S = S; p.D = D; p.R = 1; p.ctot = 0;
   p.nq = (int64_t)B * S;
-  int64_t need[2];
-  const int rc = pn_plan(__func__, widths, L, p.layer, need);
+  size_t lds_bytes = 0;
+  int64_t blocks = 0;
+  const int rc = pn_plan_scale(__func__, 64, widths, L, nsample, D, p.nq, p.sc[0], p.ctot, blocks, lds_bytes);
   if (rc != SV_OK) return rc;
-  const size_t lds_bytes = (size_t)(need[0] + need[1]) * sizeof(float);
-  if (lds_bytes > PN_LDS_MAX) {
-    set_error("%s: %s", __func__, "layer widths exceed the LDS of one CU");
-    return SV_ERR_UNSUPPORTED;
-  }
   if (B == 0) return SV_OK;
   SV_CHECK_ARG(xyz && new_xyz && group_idx && params && out && (D == 0 || points), "null pointer");
-  const int tc = PN_ROWS / nsample;
-  const int64_t grid = (p.nq + tc - 1) / tc;
-  SV_CHECK_ARG(grid < (1ll << 31), "too many centroids");
-  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.idx = group_idx; p.params = params; p.out = out;
-  p.buf1 = (int)need[0];
-  static std::atomic<bool> attr_set[64];
-  const int arc = pn_allow_lds((const void*)pointnet_sa_kernel, attr_set, 64);
-  if (arc != SV_OK) return arc;
-  hipLaunchKernelGGL(pointnet_sa_kernel, dim3((unsigned)grid), dim3(PN_THREADS), lds_bytes, stream, p);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  SV_CHECK_ARG(blocks < (1ll << 31), "too many centroids");
+  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.out = out;
+  p.sc[0].idx = group_idx;
+  p.sc[0].params = params;
+  return pn_launch<false>(p, blocks, lds_bytes, (hipStream_t)stream_);
 }
 
 extern "C" int sv_pointnet_sa_msg(const float* xyz, const float* points, const float* new_xyz, int B, int N, int D, int S,
                                   int R, const int* nsamples, const int64_t* const* group_idx,
                                   const float* const* params, const int* widths, const int* nlayers, float* out,
                                   sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1 && D >= 0, "bad shape");
   SV_CHECK_ARG(nsamples && group_idx && params && widths && nlayers, "null pointer");
   if (R < 1 || R > SV_PN_MAX_SCALES) {
     set_error("%s: %s", __func__, "scale count outside 1..SV_PN_MAX_SCALES");
     return SV_ERR_UNSUPPORTED;
   }
-  PnMsgParams p;
-  p.N = N; p.S = S; p.D = D; p.R = R;
+  PnParams<SV_PN_MAX_SCALES> p;
+  p.N = N; p.S = S; p.D = D; p.R = R; p.ctot = 0;
   p.nq = (int64_t)B * S;
-  size_t lds_max = 0;
-  int ctot = 0, wofs = 0;
+  size_t lds_bytes = 0;
   int64_t blocks = 0;
-  for (int r = 0; r < R; ++r) {
-    PnScale& sc = p.sc[r];
-    const int L = nlayers[r], ns = nsamples[r];
-    if (L < 1 || L > SV_PN_MAX_LAYERS) {
-      set_error("%s: %s", __func__, "layer count outside 1..SV_PN_MAX_LAYERS");
-      return SV_ERR_UNSUPPORTED;
-    }
-    const int* w = widths + wofs;
-    wofs += L + 1;
-    SV_CHECK_ARG(w[0] == 3 + D, "widths[0] of every scale must be 3 + D");
-    if (ns != 16 && ns != 32 && ns != 64 && ns != 128) {
-      set_error("%s: %s", __func__, "nsample must be 16, 32, 64 or 128");
-      return SV_ERR_UNSUPPORTED;
-    }
-    int64_t need[2];
-    const int rc = pn_plan(__func__, w, L, sc.layer, need);
+  for (int r = 0, wofs = 0; r < R; wofs += nlayers[r] + 1, ++r) {
+    const int rc = pn_plan_scale(__func__, 128, widths + wofs, nlayers[r], nsamples[r], D, p.nq, p.sc[r], p.ctot, blocks,
+                                 lds_bytes);
     if (rc != SV_OK) return rc;
-    const int64_t cout = w[L];
-    const int64_t floats = need[0] + need[1] + (ns > PN_ROWS ? cout : 0);  // + running maxima of a two-pass ball
-    const size_t bytes = (size_t)floats * sizeof(float);
-    if (bytes > PN_LDS_MAX) {
-      set_error("%s: %s", __func__, "layer widths exceed the LDS of one CU");
-      return SV_ERR_UNSUPPORTED;
-    }
-    if (bytes > lds_max) lds_max = bytes;
-    sc.nsample = ns; sc.L = L; sc.col = ctot;
-    sc.buf1 = (int)need[0];
-    sc.run = (int)(need[0] + need[1]);
-    ctot += (int)cout;
-    const int tc = PN_ROWS / (ns < PN_ROWS ? ns : PN_ROWS);
-    sc.blk0 = blocks;
-    blocks += (p.nq + tc - 1) / tc;
   }
   if (B == 0) return SV_OK;
   SV_CHECK_ARG(xyz && new_xyz && out && (D == 0 || points), "null pointer");
@@ -468,11 +402,6 @@ extern "C" int sv_pointnet_sa_msg(const float* xyz, const float* points, const f
     p.sc[r].params = params[r];
   }
   SV_CHECK_ARG(blocks < (1ll << 31), "too many centroids");
-  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.out = out; p.ctot = ctot;
-  static std::atomic<bool> attr_set[64];
-  const int arc = pn_allow_lds((const void*)pointnet_sa_msg_kernel, attr_set, 64);
-  if (arc != SV_OK) return arc;
-  hipLaunchKernelGGL(pointnet_sa_msg_kernel, dim3((unsigned)blocks), dim3(PN_THREADS), lds_max, stream, p);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  p.xyz = xyz; p.points = points; p.new_xyz = new_xyz; p.out = out;
+  return pn_launch<true>(p, blocks, lds_bytes, (hipStream_t)stream_);
 }

@@ -10,6 +10,7 @@
 // No float atomics anywhere: every sum runs in a fixed order, so two identical steps give identical bits.  Plain
 // element-per-thread kernels: these layers are thin (3 .. 1024 columns) and bound by memory traffic.
 #include "sv_common.h"
+#include "sv_pointnet_dev.h"
 
 namespace sv {
 
@@ -33,22 +34,9 @@ __global__ __launch_bounds__(PG_THREADS) void group_rows_kernel(const float* __r
   const uint32_t row = e / (uint32_t)ld;
   const int col = (int)(e - row * (uint32_t)ld);
   const uint32_t g = row / (uint32_t)nsample;  // (b, s)
-  const uint32_t b = g / (uint32_t)S;
-  float v = 0.0f;
-  if (col < 3 + D) {
-    const int64_t i = idx ? idx[row] : (int64_t)(row - g * (uint32_t)nsample);
-    const int64_t src = (int64_t)b * N + i;
-    const int xc = order == SV_GROUP_SSG ? col : col - D;  // coordinate column, or < 0 / >= 3 for a feature column
-    if (i < 0 || i >= N) {
-      v = NAN;  // an index outside the cloud reads nothing
-    } else if (xc >= 0 && xc < 3) {
-      v = xyz[src * 3 + xc];
-      if (idx) v = __fsub_rn(v, new_xyz[(int64_t)g * 3 + xc]);
-    } else {
-      v = points[src * D + (order == SV_GROUP_SSG ? col - 3 : col)];
-    }
-  }
-  out[e] = v;
+  out[e] = col < 3 + D ? pn_group_element(xyz, points, new_xyz, idx, g / (uint32_t)S, g, (int)(row - g * (uint32_t)nsample),
+                                          nsample, N, D, order, col)
+                       : 0.0f;
 }
 
 // ---- index transpose (CSR over the targets) ------------------------------------------------------------------------
@@ -132,55 +120,25 @@ __global__ __launch_bounds__(PG_THREADS) void group_max_backward_kernel(const fl
 }
 
 // ---- 3-NN search and weighted gather -------------------------------------------------------------------------------
-// The phase 1 of three_nn_interpolate_kernel (sv_points.hip) with one query per thread: the same expanded float32
-// distance (-2 q.p + |q|^2) + |p|^2, the same strict-less insertion (ascending, the first index wins a tie) and the same
-// normalised 1 / (d + 1e-8) weights; the file is compiled with the same flags (-ffp-contract=off), so the bits agree.
+// sv_three_nn_interpolate (sv_points.hip) in two launches, so that the neighbours and weights can be kept for the
+// backward: the same three_nn_search and three_nn_mix (sv_pointnet_dev.h), here with one query per thread.
+static_assert(PG_THREADS == NN_THREADS, "three_nn_search stages NN_THREADS points per step");
+
 __global__ __launch_bounds__(PG_THREADS) void three_nn_kernel(const float* __restrict__ xyz1,
                                                               const float* __restrict__ xyz2, int N, int S,
                                                               int32_t* __restrict__ idx, float* __restrict__ w) {
-  __shared__ float src[PG_THREADS * 3];
   const int b = blockIdx.y;
   const int q = blockIdx.x * PG_THREADS + threadIdx.x;
-  const float* x1 = xyz1 + (int64_t)b * N * 3;
-  const float* x2 = xyz2 + (int64_t)b * S * 3;
-  const bool active = q < N;
-  float qx = 0.f, qy = 0.f, qz = 0.f, qq = 0.f;
-  if (active) {
-    qx = x1[q * 3 + 0];
-    qy = x1[q * 3 + 1];
-    qz = x1[q * 3 + 2];
-    qq = (qx * qx + qy * qy) + qz * qz;
-  }
-  float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
-  int i0 = 0, i1 = 0, i2 = 0;
-  for (int s0 = 0; s0 < S; s0 += PG_THREADS) {
-    const int cnt = min(PG_THREADS, S - s0);
-    __syncthreads();
-    for (int e = threadIdx.x; e < cnt * 3; e += PG_THREADS) src[e] = x2[(int64_t)s0 * 3 + e];
-    __syncthreads();
-    if (active) {
-      for (int j = 0; j < cnt; ++j) {
-        const float px = src[j * 3], py = src[j * 3 + 1], pz = src[j * 3 + 2];
-        const float dot = (qx * px + qy * py) + qz * pz;
-        const float pp = (px * px + py * py) + pz * pz;
-        const float d = (-2.0f * dot + qq) + pp;
-        const int i = s0 + j;
-        if (d < d2) {
-          if (d < d1) {
-            d2 = d1; i2 = i1;
-            if (d < d0) { d1 = d0; i1 = i0; d0 = d; i0 = i; }
-            else { d1 = d; i1 = i; }
-          } else { d2 = d; i2 = i; }
-        }
-      }
-    }
-  }
-  if (!active) return;
-  const float w0 = 1.0f / (d0 + 1e-8f), w1 = 1.0f / (d1 + 1e-8f), w2 = 1.0f / (d2 + 1e-8f);
-  const float ws = (w0 + w1) + w2;
+  int32_t qi[3];
+  float qw[3];
+  three_nn_search(xyz1 + (int64_t)b * N * 3, xyz2 + (int64_t)b * S * 3, S, q, q < N, qi, qw);
+  if (q >= N) return;
   const int64_t o = ((int64_t)b * N + q) * 3;
-  idx[o + 0] = i0; idx[o + 1] = i1; idx[o + 2] = i2;
-  w[o + 0] = w0 / ws; w[o + 1] = w1 / ws; w[o + 2] = w2 / ws;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    idx[o + k] = qi[k];
+    w[o + k] = qw[k];
+  }
 }
 
 __global__ __launch_bounds__(PG_THREADS) void three_nn_gather_kernel(const float* __restrict__ points2,
@@ -193,12 +151,11 @@ __global__ __launch_bounds__(PG_THREADS) void three_nn_gather_kernel(const float
   const int c = (int)(e - row * (uint32_t)C);
   const float* p2 = points2 + (int64_t)(row / (uint32_t)N) * S * C;
   const int32_t* ix = idx + (int64_t)row * 3;
-  const float* wr = w + (int64_t)row * 3;
   if ((uint32_t)ix[0] >= (uint32_t)S || (uint32_t)ix[1] >= (uint32_t)S || (uint32_t)ix[2] >= (uint32_t)S) {
     out[e] = NAN;  // an index outside the source cloud reads nothing
     return;
   }
-  out[e] = (p2[(int64_t)ix[0] * C + c] * wr[0] + p2[(int64_t)ix[1] * C + c] * wr[1]) + p2[(int64_t)ix[2] * C + c] * wr[2];
+  out[e] = three_nn_mix(p2, C, c, ix, w + (int64_t)row * 3);
 }
 
 static int bits_for(uint64_t v) {  // bits that hold every value 0 .. v

@@ -9,8 +9,11 @@
 // Up to 16k points the cloud and the running min-distances live in registers and a round is a DPP argmax + one
 // barrier (fps_reg_kernel); larger clouds keep the distances in LDS and re-read the points (fps_kernel).
 // Ball query: one wavefront per query centre scans the cloud in index order, 64 points per step, and compacts the
-// hits with ballot/popcount — no distance matrix, no sort.
+// hits with ballot/popcount — no distance matrix, no sort.  One kernel template serves both entries: sv_ball_query is
+// its one-radius instance, sv_ball_query_multi the SV_BQ_MAX_RADII one.
+// 3-NN interpolation: the search and the weighted sum are sv_pointnet_dev.h's, shared with the training kernels.
 #include "sv_common.h"
+#include "sv_pointnet_dev.h"
 
 namespace sv {
 
@@ -214,73 +217,39 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_reg_kernel(const float* __res
   }
 }
 
-// 4 waves per block, one query centre per wave
-__global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ xyz,
-                                                          const float* __restrict__ new_xyz, int B, int N, int S,
-                                                          float r2, int nsample, int64_t* __restrict__ out) {
-  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= (int64_t)B * S) return;
-  const int lane = threadIdx.x & 63;
-  const int b = (int)(q / S);
-  const float* P = xyz + (int64_t)b * N * 3;
-  const float qx = new_xyz[q * 3], qy = new_xyz[q * 3 + 1], qz = new_xyz[q * 3 + 2];
-  const float qq = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
-  int64_t* dst = out + q * nsample;
-  int count = 0;
-  int first = N;
-  for (int base = 0; base < N && count < nsample; base += 64) {
-    const int i = base + lane;
-    bool hit = false;
-    if (i < N) {
-      const float x = P[i * 3], y = P[i * 3 + 1], z = P[i * 3 + 2];
-      const float dot = __fadd_rn(__fadd_rn(__fmul_rn(qx, x), __fmul_rn(qy, y)), __fmul_rn(qz, z));
-      const float pp = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
-      // reference: dist = -2 * (q . p); dist += |q|^2; dist += |p|^2; keep when NOT (dist > r^2)
-      const float d = __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), qq), pp);
-      hit = !(d > r2);
-    }
-    const unsigned long long m = __ballot(hit);
-    if (m) {
-      if (first == N) first = base + (int)__builtin_ctzll(m);
-      const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-      if (hit && pos < nsample) dst[pos] = i;
-      count += __popcll(m);
-    }
-  }
-  if (count > nsample) count = nsample;
-  for (int j = count + lane; j < nsample; j += 64) dst[j] = first;
-}
-
-// R radii of one multi-scale grouping layer in one scan over the cloud: per radius its own r^2, cap, count, first hit and
-// output, each the exact result of ball_query_kernel with that (radius, nsample): the same distance, compare, ascending
-// order and padding.  The scan stops once every ball is full (a full ball takes no more writes, and its first hit is set).
-struct BallQueryMulti {
-  float r2[SV_BQ_MAX_RADII];
-  int nsample[SV_BQ_MAX_RADII];
-  int64_t* out[SV_BQ_MAX_RADII];
+// Ball query, 4 waves per block, one query centre per wave: up to MAXR radii in one scan over the cloud, per radius its own
+// r^2, cap, count, first hit and output - the same distance, compare, ascending order and padding whatever the other radii
+// are.  The scan stops once every ball is full (a full ball takes no more writes, and its first hit is set).  MAXR sizes
+// the argument struct and the per-radius registers: sv_ball_query is the MAXR = 1 instance.
+template <int MAXR>
+struct BallQueryArgs {
+  float r2[MAXR];
+  int nsample[MAXR];
+  int64_t* out[MAXR];
   int R;
 };
 
-__global__ __launch_bounds__(256) void ball_query_multi_kernel(const float* __restrict__ xyz,
-                                                                const float* __restrict__ new_xyz, int B, int N, int S,
-                                                                const BallQueryMulti a) {
+template <int MAXR>
+__global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz,
+                                                          int B, int N, int S, const BallQueryArgs<MAXR> a) {
   const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= (int64_t)B * S) return;
   const int lane = threadIdx.x & 63;
   const int b = (int)(q / S);
+  const int R = MAXR == 1 ? 1 : a.R;
   const float* P = xyz + (int64_t)b * N * 3;
   const float qx = new_xyz[q * 3], qy = new_xyz[q * 3 + 1], qz = new_xyz[q * 3 + 2];
   const float qq = __fadd_rn(__fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy)), __fmul_rn(qz, qz));
-  int count[SV_BQ_MAX_RADII], first[SV_BQ_MAX_RADII];
+  int count[MAXR], first[MAXR];
 #pragma unroll
-  for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
+  for (int r = 0; r < MAXR; ++r) {
     count[r] = 0;
     first[r] = N;
   }
   for (int base = 0; base < N; base += 64) {
     bool open = false;
 #pragma unroll
-    for (int r = 0; r < SV_BQ_MAX_RADII; ++r) open |= r < a.R && count[r] < a.nsample[r];
+    for (int r = 0; r < MAXR; ++r) open |= r < R && count[r] < a.nsample[r];
     if (!open) break;
     const int i = base + lane;
     float d = 0.f;
@@ -288,11 +257,12 @@ __global__ __launch_bounds__(256) void ball_query_multi_kernel(const float* __re
       const float x = P[i * 3], y = P[i * 3 + 1], z = P[i * 3 + 2];
       const float dot = __fadd_rn(__fadd_rn(__fmul_rn(qx, x), __fmul_rn(qy, y)), __fmul_rn(qz, z));
       const float pp = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
+      // reference: dist = -2 * (q . p); dist += |q|^2; dist += |p|^2; keep when NOT (dist > r^2)
       d = __fadd_rn(__fadd_rn(__fmul_rn(-2.0f, dot), qq), pp);
     }
 #pragma unroll
-    for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
-      if (r >= a.R) break;
+    for (int r = 0; r < MAXR; ++r) {
+      if (r >= R) break;
       const bool hit = i < N && !(d > a.r2[r]);
       const unsigned long long m = __ballot(hit);
       if (m) {
@@ -304,8 +274,8 @@ __global__ __launch_bounds__(256) void ball_query_multi_kernel(const float* __re
     }
   }
 #pragma unroll
-  for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
-    if (r >= a.R) break;
+  for (int r = 0; r < MAXR; ++r) {
+    if (r >= R) break;
     const int ns = a.nsample[r];
     const int c = count[r] > ns ? ns : count[r];
     int64_t* dst = a.out[r] + q * ns;
@@ -314,69 +284,35 @@ __global__ __launch_bounds__(256) void ball_query_multi_kernel(const float* __re
 }
 
 // ---- 3-nearest-neighbour inverse-distance interpolation (PointNetFeaturePropagation.forward,
-//      model/pointnet2_utils.py:298-305): a workgroup serves 64 query points.  Phase 1: one thread per query walks the S
-//      source points (staged through LDS, 256 at a time) with the reference's expanded float32 distance
-//      (-2 q.p + |q|^2) + |p|^2 and keeps the three smallest (ascending, first index wins a tie - the order of the
-//      reference's full sort); weights 1 / (d + 1e-8) normalised.  Phase 2: all 256 threads write out[q][c], channel fastest.
-__global__ __launch_bounds__(256) void three_nn_interpolate_kernel(const float* __restrict__ xyz1,
-                                                                    const float* __restrict__ xyz2,
-                                                                    const float* __restrict__ points2, int N, int S, int C,
-                                                                    float* __restrict__ out) {
-  __shared__ float src[256 * 3];
-  __shared__ int nn_idx[64 * 3];
+//      model/pointnet2_utils.py:298-305): a workgroup serves 64 query points.  Phase 1: one thread per query runs
+//      three_nn_search (sv_pointnet_dev.h) and leaves its neighbours and weights in LDS.  Phase 2: all 256 threads write
+//      out[q][c] = three_nn_mix, channel fastest.
+__global__ __launch_bounds__(NN_THREADS) void three_nn_interpolate_kernel(const float* __restrict__ xyz1,
+                                                                           const float* __restrict__ xyz2,
+                                                                           const float* __restrict__ points2, int N, int S,
+                                                                           int C, float* __restrict__ out) {
+  __shared__ int32_t nn_idx[64 * 3];
   __shared__ float nn_w[64 * 3];
   const int b = blockIdx.y;
   const int q0 = blockIdx.x * 64;
-  const float* x1 = xyz1 + (int64_t)b * N * 3;
-  const float* x2 = xyz2 + (int64_t)b * S * 3;
   const int q = q0 + threadIdx.x;
-  const bool active = threadIdx.x < 64 && q < N;
-  float qx = 0.f, qy = 0.f, qz = 0.f, qq = 0.f;
-  if (active) {
-    qx = x1[q * 3 + 0];
-    qy = x1[q * 3 + 1];
-    qz = x1[q * 3 + 2];
-    qq = (qx * qx + qy * qy) + qz * qz;
-  }
-  float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
-  int i0 = 0, i1 = 0, i2 = 0;
-  for (int s0 = 0; s0 < S; s0 += 256) {
-    const int cnt = min(256, S - s0);
-    __syncthreads();
-    for (int e = threadIdx.x; e < cnt * 3; e += 256) src[e] = x2[(int64_t)s0 * 3 + e];
-    __syncthreads();
-    if (active) {
-      for (int j = 0; j < cnt; ++j) {
-        const float px = src[j * 3], py = src[j * 3 + 1], pz = src[j * 3 + 2];
-        const float dot = (qx * px + qy * py) + qz * pz;
-        const float pp = (px * px + py * py) + pz * pz;
-        const float d = (-2.0f * dot + qq) + pp;
-        const int i = s0 + j;
-        if (d < d2) {
-          if (d < d1) {
-            d2 = d1; i2 = i1;
-            if (d < d0) { d1 = d0; i1 = i0; d0 = d; i0 = i; }
-            else { d1 = d; i1 = i; }
-          } else { d2 = d; i2 = i; }
-        }
-      }
-    }
-  }
+  int32_t idx[3];
+  float w[3];
+  three_nn_search(xyz1 + (int64_t)b * N * 3, xyz2 + (int64_t)b * S * 3, S, q, threadIdx.x < 64 && q < N, idx, w);
   if (threadIdx.x < 64) {
-    float w0 = 1.0f / (d0 + 1e-8f), w1 = 1.0f / (d1 + 1e-8f), w2 = 1.0f / (d2 + 1e-8f);
-    const float ws = (w0 + w1) + w2;
-    nn_idx[threadIdx.x * 3 + 0] = i0; nn_idx[threadIdx.x * 3 + 1] = i1; nn_idx[threadIdx.x * 3 + 2] = i2;
-    nn_w[threadIdx.x * 3 + 0] = w0 / ws; nn_w[threadIdx.x * 3 + 1] = w1 / ws; nn_w[threadIdx.x * 3 + 2] = w2 / ws;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      nn_idx[threadIdx.x * 3 + k] = idx[k];
+      nn_w[threadIdx.x * 3 + k] = w[k];
+    }
   }
   __syncthreads();
   const float* p2 = points2 + (int64_t)b * S * C;
   float* o = out + ((int64_t)b * N + q0) * C;
   const int nq = min(64, N - q0);
-  for (int e = threadIdx.x; e < nq * C; e += 256) {
+  for (int e = threadIdx.x; e < nq * C; e += NN_THREADS) {
     const int ql = e / C, c = e - ql * C;
-    const float v = (p2[(int64_t)nn_idx[ql * 3] * C + c] * nn_w[ql * 3] + p2[(int64_t)nn_idx[ql * 3 + 1] * C + c] * nn_w[ql * 3 + 1]) +
-                    p2[(int64_t)nn_idx[ql * 3 + 2] * C + c] * nn_w[ql * 3 + 2];
-    o[e] = v;
+    o[e] = three_nn_mix(p2, C, c, nn_idx + ql * 3, nn_w + ql * 3);
   }
 }
 
@@ -392,8 +328,8 @@ int sv_three_nn_interpolate(const float* xyz1, const float* xyz2, const float* p
   SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 3 && C >= 1, "bad shape (S >= 3 source points)");
   if (B == 0) return SV_OK;
   SV_CHECK_ARG(xyz1 && xyz2 && points2 && out, "null pointer");
-  hipLaunchKernelGGL(three_nn_interpolate_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)B), dim3(256), 0, stream, xyz1,
-                     xyz2, points2, N, S, C, out);
+  hipLaunchKernelGGL(three_nn_interpolate_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)B), dim3(NN_THREADS), 0, stream,
+                     xyz1, xyz2, points2, N, S, C, out);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -466,10 +402,9 @@ int sv_ball_query(const float* xyz, const float* new_xyz, int B, int N, int S, d
   SV_CHECK_ARG(B >= 0 && N >= 1 && S >= 1 && nsample >= 1, "bad shape");
   if (B == 0) return SV_OK;
   SV_CHECK_ARG(xyz && new_xyz && out, "null pointer");
-  const float r2 = (float)(radius * radius);
+  const BallQueryArgs<1> a = {{(float)(radius * radius)}, {nsample}, {out}, 1};
   const int64_t nq = (int64_t)B * S;
-  hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz, new_xyz, B, N, S, r2,
-                     nsample, out);
+  hipLaunchKernelGGL(ball_query_kernel<1>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz, new_xyz, B, N, S, a);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -483,7 +418,7 @@ int sv_ball_query_multi(const float* xyz, const float* new_xyz, int B, int N, in
     set_error("%s: %s", __func__, "radius count outside 1..SV_BQ_MAX_RADII");
     return SV_ERR_UNSUPPORTED;
   }
-  BallQueryMulti a;
+  BallQueryArgs<SV_BQ_MAX_RADII> a;
   a.R = R;
   for (int r = 0; r < SV_BQ_MAX_RADII; ++r) {
     a.r2[r] = 0.f;
@@ -502,8 +437,8 @@ int sv_ball_query_multi(const float* xyz, const float* new_xyz, int B, int N, in
     a.out[r] = out[r];
   }
   const int64_t nq = (int64_t)B * S;
-  hipLaunchKernelGGL(ball_query_multi_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz, new_xyz, B, N,
-                     S, a);
+  hipLaunchKernelGGL(ball_query_kernel<SV_BQ_MAX_RADII>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, xyz,
+                     new_xyz, B, N, S, a);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

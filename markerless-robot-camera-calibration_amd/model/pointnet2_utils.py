@@ -7,11 +7,17 @@ index_points, square_distance: thin torch helpers with the reference's semantics
 set_training_path(model, "torch" | "hip"): which kernels the set abstraction / feature propagation layers and the
 PointNet++ heads train on (default "torch": the reference's torch expressions).
 """
-from ctypes import c_double, c_int, c_int64
+from ctypes import c_double, c_int, c_int64, c_void_p
 
+import numpy as np
 import torch
+import torch.nn as nn
+import torch.nn.functional as F
 
-from .._lib import call, ptr, require_cuda, stream_ptr
+from .. import _lib
+from .. import nn as svnn
+from .._lib import (SV_ACT_RELU, SV_BQ_MAX_RADII, SV_GROUP_MSG, SV_GROUP_SSG, call, ptr, require_cuda,
+                    stream_ptr)
 
 
 def farthest_point_sample(xyz, npoint, start=None):
@@ -41,10 +47,6 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
 def query_ball_point_multi(radius_list, nsample_list, xyz, new_xyz):
     """[query_ball_point(radius_list[r], nsample_list[r], xyz, new_xyz) for r], the radii of one multi-scale layer in one
     scan over the cloud per launch (sv_ball_query_multi, up to SV_BQ_MAX_RADII radii a launch); bit-identical per radius."""
-    from ctypes import c_void_p
-
-    from .._lib import SV_BQ_MAX_RADII
-
     require_cuda(xyz, "xyz")
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
@@ -73,13 +75,26 @@ def square_distance(src, dst):
     return dist
 
 
-def _group(xyz, points, new_xyz, idx):
-    """[xyz[idx] - new_xyz, points[idx]] -> [B, S, nsample, 3 + D] (reference :131-137)."""
+def sample_and_group_all(xyz, points):
+    B, N, C = xyz.shape
+    new_xyz = torch.zeros(B, 1, C, device=xyz.device)
+    grouped = xyz.view(B, 1, N, C)
+    new_points = grouped if points is None else torch.cat([grouped, points.view(B, 1, N, -1)], dim=-1)
+    return new_xyz, new_points
+
+
+def _group(xyz, points, new_xyz, idx, order):
+    """the grouped tensor [B, S, nsample, 3 + D]: SV_GROUP_SSG [xyz[idx] - new_xyz, points[idx]] (reference :131-137) or
+    SV_GROUP_MSG [points[idx], xyz[idx] - new_xyz] (the multi-scale grouping's order, features first, :245-250);
+    idx None is group_all: every point once, as it is (:143-160)"""
+    if idx is None:
+        return sample_and_group_all(xyz, points)[1]
     B, S, C = new_xyz.shape
-    grouped_xyz = index_points(xyz, idx)
-    grouped_xyz_norm = grouped_xyz - new_xyz.view(B, S, 1, C)
-    new_points = grouped_xyz_norm if points is None else torch.cat([grouped_xyz_norm, index_points(points, idx)], -1)
-    return grouped_xyz, new_points
+    grouped_xyz = index_points(xyz, idx) - new_xyz.view(B, S, 1, C)
+    if points is None:
+        return grouped_xyz
+    feats = index_points(points, idx)
+    return torch.cat([grouped_xyz, feats] if order == SV_GROUP_SSG else [feats, grouped_xyz], dim=-1)
 
 
 def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, fps_start=None):
@@ -87,9 +102,9 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, fps_
     fps_idx = farthest_point_sample(xyz, npoint, start=fps_start)
     new_xyz = index_points(xyz, fps_idx)
     idx = query_ball_point(radius, nsample, xyz, new_xyz)
-    grouped_xyz, new_points = _group(xyz, points, new_xyz, idx)
+    new_points = _group(xyz, points, new_xyz, idx, SV_GROUP_SSG)
     if returnfps:
-        return new_xyz, new_points, grouped_xyz, fps_idx
+        return new_xyz, new_points, index_points(xyz, idx), fps_idx
     return new_xyz, new_points
 
 
@@ -98,14 +113,6 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, fps_
 # (mlp_convs.i = nn.Conv2d / nn.Conv1d 1x1, mlp_bns.i = BatchNorm) so its checkpoints load by key; in eval mode the
 # shared MLPs run as dense rows through the fp32-MFMA kernel with the BatchNorm folded into the epilogue.
 # ----------------------------------------------------------------------------------------------------------------------
-import numpy as np  # noqa: E402
-import torch.nn as nn  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-from .. import nn as svnn  # noqa: E402
-from .._lib import SV_ACT_RELU, SV_GROUP_MSG, SV_GROUP_SSG  # noqa: E402
-
-
 def _fold_conv_bn(conv, bn):
     """1x1 conv or Linear (+bias) followed by BatchNorm(eval) -> W[1,Cin,Cout], scale, shift with the bias folded in."""
     w = conv.weight.detach().reshape(conv.weight.shape[0], -1).t().contiguous().unsqueeze(0)  # Conv 1x1 or Linear
@@ -120,11 +127,13 @@ def _fold_conv_bn(conv, bn):
     return w, torch.from_numpy(scale).to(dev), torch.from_numpy(shift).to(dev)
 
 
+def _fold_mlp(convs, bns):
+    return [_fold_conv_bn(conv, bn) for conv, bn in zip(convs, bns)]
+
+
 def _mlp_rows(rows, convs, bns, folds=None):
     """rows [R, Cin] -> relu(bn(conv(.))) stack, one fused launch per layer (folds: the layers' _fold_conv_bn results)."""
-    if folds is None:
-        folds = [_fold_conv_bn(conv, bn) for conv, bn in zip(convs, bns)]
-    for w, scale, shift in folds:
+    for w, scale, shift in folds if folds is not None else _fold_mlp(convs, bns):
         rows = svnn.conv_forward(rows, w, None, rows.shape[0], scale, shift, None, SV_ACT_RELU)
     return rows
 
@@ -200,8 +209,6 @@ def _hip_train(module, *coords):
 
 def _csr(idx, N, module):
     """sv_index_transpose: (offsets int32 [B*N + 1], pos int32 [B*M]) of the index table idx [B, ...] (values in [0, N))"""
-    from .. import _lib
-
     B = idx.shape[0]
     M = idx.numel() // max(B, 1)
     lib = _lib.load()
@@ -232,8 +239,6 @@ class GroupRowsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, points, xyz, new_xyz, idx, order, module):
-        from .._lib import SV_GROUP_SSG
-
         B, N, _ = xyz.shape
         S, K = (1, N) if idx is None else (idx.shape[1], idx.shape[2])
         D = 0 if points is None else points.shape[2]
@@ -383,16 +388,127 @@ def _mlp_rows_train(rows, convs, bns):
     return rows
 
 
-def sample_and_group_all(xyz, points):
-    B, N, C = xyz.shape
-    new_xyz = torch.zeros(B, 1, C, device=xyz.device)
-    grouped = xyz.view(B, 1, N, C)
-    new_points = grouped if points is None else torch.cat([grouped, points.view(B, 1, N, -1)], dim=-1)
-    return new_xyz, new_points
+def _cat(tensors, dim):
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, dim=dim)
 
 
-class PointNetSetAbstraction(FoldCache):
+class _SetAbstraction(FoldCache):
+    """What PointNetSetAbstraction and PointNetSetAbstractionMsg share - everything but the parameter names and the fused
+    entry point.  A layer is a list of scales (radius, nsample, convs, bns) around the same farthest-point centroids,
+    grouped in the column order `_order`, the pooled features concatenated; single-scale is a list of one scale in the
+    order SV_GROUP_SSG.  Eval on the GPU: sv_fps, the ball query, then the fused kernel (all scales in one launch); shapes
+    it declines, `fused = False` or group_all run every scale's layers one launch each (sv_conv_fwd dense rows),
+    torch.max and torch.cat - the same bits."""
+
     _hip_trainable = True  # set_training_path
+    _order = SV_GROUP_SSG
+    group_all = False  # one group of all points around the origin instead of sampled balls (single-scale only)
+
+    def __init__(self):
+        super().__init__()
+        self.fused = True  # False: the unfused eval path (tests, timing)
+
+    def _scales(self):
+        """[(radius, nsample, convs, bns)]"""
+        raise NotImplementedError
+
+    def _launch_fused(self, x, p, q, idxs, B, N, D, S, packed, host, out):
+        """the class's fused entry point on every scale -> its return code"""
+        raise NotImplementedError
+
+    def _folded(self):
+        """(per-scale layer folds, per-scale packed parameters, host arrays (nsamples, params, widths, nlayers) of the
+        fused entry point) - built once per weights / device"""
+        def build():
+            scales = self._scales()
+            folds = [_fold_mlp(convs, bns) for _, _, convs, bns in scales]
+            packed = [torch.cat([t.reshape(-1).to(torch.float32) for f in fs for t in f]).contiguous() for fs in folds]
+            widths = [w for _, _, convs, _ in scales for w in [convs[0].in_channels] + [c.out_channels for c in convs]]
+            R = len(scales)
+            host = ((c_int * R)(*[k or 0 for _, k, _, _ in scales]), (c_void_p * R)(*[p.data_ptr() for p in packed]),
+                    (c_int * len(widths))(*widths), (c_int * R)(*[len(convs) for _, _, convs, _ in scales]))
+            return folds, packed, host
+
+        return self._fold_get(build)
+
+    def _fused(self, xyz, points, new_xyz, idxs, folds):
+        """every scale's gather + shared MLP + max in one launch -> [B, S, sum C_r], or None where the kernel does not
+        cover the shapes (SV_ERR_UNSUPPORTED: nothing was launched, the caller runs the layers one by one).  idxs: the
+        scales' ball-query tables (a single scale's may come bare)."""
+        _, packed, host = folds
+        idxs = [idxs] if torch.is_tensor(idxs) else idxs
+        B, N, _ = xyz.shape
+        S = new_xyz.shape[1]
+        x = xyz.to(torch.float32).contiguous()
+        p = points.to(torch.float32).contiguous() if points is not None else None
+        D = p.shape[2] if p is not None else 0
+        if host[2][0] != 3 + D:
+            raise ValueError(f"set abstraction expects {host[2][0] - 3} point features, got {D}")
+        q = new_xyz.to(torch.float32).contiguous()
+        ctot = sum(convs[-1].out_channels for _, _, convs, _ in self._scales())
+        out = torch.empty((B, S, ctot), dtype=torch.float32, device=xyz.device)
+        rc = self._launch_fused(x, p, q, idxs, B, N, D, S, packed, host, out)
+        if rc == _lib.SV_ERR_UNSUPPORTED:
+            return None
+        _lib._check(rc, self._entry)
+        return out
+
+    # ---- one scale, from its ball-query table to its pooled features
+    def _pool_eval(self, xyz, points, new_xyz, idx, convs, bns, folds):
+        """unfused eval: the layers one launch each (dense rows), then torch.max -> [B, S, C']"""
+        grouped = _group(xyz, points, new_xyz, idx, self._order)
+        B, S, Kn, C = grouped.shape
+        rows = _mlp_rows(grouped.reshape(B * S * Kn, C).contiguous(), convs, bns, folds)
+        return rows.view(B, S, Kn, -1).max(dim=2)[0]
+
+    def _pool_train_hip(self, xyz, points, new_xyz, idx, convs, bns):
+        """train() on the HIP path: sv_group_rows -> shared MLP on rows -> sv_group_max -> [B, S, C']"""
+        B, S = new_xyz.shape[0], new_xyz.shape[1]
+        rows = group_rows(xyz, points, new_xyz, idx, self._order, self)
+        rows = _mlp_rows_train(rows, convs, bns)
+        return group_max(rows, rows.shape[0] // (B * S), self).view(B, S, -1)
+
+    def _pool_train_torch(self, xyz, points, new_xyz, idx, convs, bns):
+        """train() on the reference's torch expressions (:194-203 / :247-258) -> [B, C', S]"""
+        t = _group(xyz, points, new_xyz, idx, self._order).permute(0, 3, 2, 1)
+        for conv, bn in zip(convs, bns):
+            t = F.relu(bn(conv(t)))
+        return torch.max(t, 2)[0]
+
+    def forward(self, xyz, points, fps_start=None):
+        """xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points [B, sum C_r, S].  fps_start int64 [B] pins
+        the first farthest-point centroids (None: drawn as the reference draws them, torch.randint on the device)."""
+        hip = _hip_train(self, xyz)
+        xyz = xyz.permute(0, 2, 1)
+        if points is not None:
+            points = points.permute(0, 2, 1)
+        scales = self._scales()
+        if self.group_all:
+            new_xyz, idxs = torch.zeros(xyz.shape[0], 1, xyz.shape[2], device=xyz.device), [None]
+        else:  # sampling and ball query on libsvhip, the same groups on every path
+            new_xyz = index_points(xyz, farthest_point_sample(xyz, self.npoint, start=fps_start))
+            if len(scales) == 1:
+                idxs = [query_ball_point(scales[0][0], scales[0][1], xyz, new_xyz)]
+            else:
+                idxs = query_ball_point_multi([r for r, _, _, _ in scales], [k for _, k, _, _ in scales], xyz, new_xyz)
+        args = [(xyz, points, new_xyz, idx, convs, bns) for idx, (_, _, convs, bns) in zip(idxs, scales)]
+        if hip:
+            pooled = _cat([self._pool_train_hip(*a) for a in args], -1)
+        elif self.training:
+            return new_xyz.permute(0, 2, 1), _cat([self._pool_train_torch(*a) for a in args], 1)
+        else:
+            folds = self._folded()
+            fused = self.fused and not self.group_all and xyz.is_cuda
+            pooled = self._fused(xyz, points, new_xyz, idxs, folds) if fused else None
+            if pooled is None:
+                pooled = _cat([self._pool_eval(*a, f) for a, f in zip(args, folds[0])], -1)
+        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)  # [B, D', S]
+
+
+class PointNetSetAbstraction(_SetAbstraction):
+    """reference :163-204; fused eval kernel sv_pointnet_sa"""
+
+    _entry = "sv_pointnet_sa"
 
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
         super().__init__()
@@ -405,119 +521,28 @@ class PointNetSetAbstraction(FoldCache):
             self.mlp_bns.append(nn.BatchNorm2d(out))
             last = out
 
-    def _folded(self):
-        """(per-layer folds, packed sv_pointnet_sa parameters, host widths) - built once per weights / device"""
-        def build():
-            folds = [_fold_conv_bn(conv, bn) for conv, bn in zip(self.mlp_convs, self.mlp_bns)]
-            packed = torch.cat([t.reshape(-1).to(torch.float32) for f in folds for t in f]).contiguous()
-            widths = [self.mlp_convs[0].in_channels] + [conv.out_channels for conv in self.mlp_convs]
-            return folds, packed, (c_int * len(widths))(*widths)
+    def _scales(self):
+        return [(self.radius, self.nsample, self.mlp_convs, self.mlp_bns)]
 
-        return self._fold_get(build)
-
-    def _fused(self, xyz, points, new_xyz, idx, folds):
-        """sv_pointnet_sa: gather + shared MLP + max in one launch -> [B, S, C_last], or None where the kernel does not
-        cover the shape (SV_ERR_UNSUPPORTED: nothing was launched, the caller runs the layers one by one)."""
-        from .. import _lib
-
-        _, packed, widths = folds
-        B, N, _ = xyz.shape
-        S = new_xyz.shape[1]
-        x = xyz.to(torch.float32).contiguous()
-        p = points.to(torch.float32).contiguous() if points is not None else None
-        D = p.shape[2] if p is not None else 0
-        if widths[0] != 3 + D:
-            raise ValueError(f"set abstraction expects {widths[0] - 3} point features, got {D}")
-        q = new_xyz.to(torch.float32).contiguous()
-        out = torch.empty((B, S, widths[len(widths) - 1]), dtype=torch.float32, device=xyz.device)
-        lib = _lib.load()
-        rc = lib.sv_pointnet_sa(ptr(x), ptr(p), ptr(q), ptr(idx), B, N, D, S, self.nsample, ptr(packed), widths,
-                                len(widths) - 1, ptr(out), stream_ptr())
-        if rc == _lib.SV_ERR_UNSUPPORTED:
-            return None
-        _lib._check(rc, "sv_pointnet_sa")
-        return out
-
-    def forward(self, xyz, points, fps_start=None):
-        """xyz [B,3,N], points [B,D,N] -> new_xyz [B,3,S], new_points [B,D',S].  fps_start int64 [B] pins the first
-        farthest-point centroids (None: drawn as the reference draws them, torch.randint on the device)."""
-        if _hip_train(self, xyz):
-            return self._train_hip(xyz, points, fps_start)
-        xyz = xyz.permute(0, 2, 1)
-        if points is not None:
-            points = points.permute(0, 2, 1)
-        if self.training or self.group_all:
-            if self.group_all:
-                new_xyz, new_points = sample_and_group_all(xyz, points)
-            else:
-                new_xyz, new_points = sample_and_group(self.npoint, self.radius, self.nsample, xyz, points,
-                                                       fps_start=fps_start)
-            if self.training:
-                t = new_points.permute(0, 3, 2, 1)
-                for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-                    t = F.relu(bn(conv(t)))
-                return new_xyz.permute(0, 2, 1), torch.max(t, 2)[0]
-            B, S, Kn, C = new_points.shape
-            rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns,
-                             self._folded()[0])
-            return new_xyz.permute(0, 2, 1), rows.view(B, S, Kn, -1).max(dim=2)[0].permute(0, 2, 1)
-        # eval: sampling and ball query on libsvhip, then the fused set abstraction (sv_pointnet_sa)
-        fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
-        new_xyz = index_points(xyz, fps_idx)
-        idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz)
-        folds = self._folded()
-        pooled = self._fused(xyz, points, new_xyz, idx, folds) if xyz.is_cuda else None
-        if pooled is None:  # shapes outside the fused kernel: the layers one launch each, then torch.max
-            _, new_points = _group(xyz, points, new_xyz, idx)
-            B, S, Kn, C = new_points.shape
-            rows = _mlp_rows(new_points.reshape(B * S * Kn, C).contiguous(), self.mlp_convs, self.mlp_bns, folds[0])
-            pooled = rows.view(B, S, Kn, -1).max(dim=2)[0]
-        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)  # [B, D', S]
-
-    def _train_hip(self, xyz, points, fps_start):
-        """train() on the HIP path: sv_group_rows -> shared MLP on rows -> sv_group_max (the sampling and ball query of
-        the torch path, so the same groups)"""
-        xyz = xyz.permute(0, 2, 1)
-        if points is not None:
-            points = points.permute(0, 2, 1)
-        B, N, C = xyz.shape
-        if self.group_all:
-            new_xyz = torch.zeros(B, 1, C, device=xyz.device)
-            S, K, idx = 1, N, None
-        else:
-            fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
-            new_xyz = index_points(xyz, fps_idx)
-            S, K = self.npoint, self.nsample
-            idx = query_ball_point(self.radius, K, xyz, new_xyz)
-        rows = group_rows(xyz, points, new_xyz, idx, SV_GROUP_SSG, self)
-        rows = _mlp_rows_train(rows, self.mlp_convs, self.mlp_bns)
-        pooled = group_max(rows, K, self).view(B, S, -1)
-        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)
+    def _launch_fused(self, x, p, q, idxs, B, N, D, S, packed, host, out):
+        nsamples, _, widths, nlayers = host
+        return _lib.load().sv_pointnet_sa(ptr(x), ptr(p), ptr(q), ptr(idxs[0]), B, N, D, S, nsamples[0], ptr(packed[0]),
+                                          widths, nlayers[0], ptr(out), stream_ptr())
 
 
-def _group_msg(xyz, points, new_xyz, idx):
-    """[points[idx], xyz[idx] - new_xyz] -> [B, S, nsample, D + 3]: the multi-scale grouping's order, features first
-    (reference :245-250)."""
-    B, S, C = new_xyz.shape
-    grouped_xyz = index_points(xyz, idx) - new_xyz.view(B, S, 1, C)
-    return grouped_xyz if points is None else torch.cat([index_points(points, idx), grouped_xyz], dim=-1)
-
-
-class PointNetSetAbstractionMsg(FoldCache):
+class PointNetSetAbstractionMsg(_SetAbstraction):
     """Multi-scale grouping (reference :207-264): R radii around the same farthest-point centroids, one shared MLP per
-    radius, the pooled features concatenated.  Parameter names conv_blocks.i.j / bn_blocks.i.j as in the reference.  Eval
-    on the GPU: sv_fps, sv_ball_query_multi, then sv_pointnet_sa_msg (all scales in one launch); shapes the fused kernel
-    declines, or `fused = False`, run every scale's layers one launch each (sv_conv_fwd dense rows), torch.max and
-    torch.cat - the same bits."""
+    radius.  Parameter names conv_blocks.i.j / bn_blocks.i.j as in the reference.  Fused eval kernel
+    sv_pointnet_sa_msg, nsample up to 128."""
 
-    _hip_trainable = True  # set_training_path
+    _entry = "sv_pointnet_sa_msg"
+    _order = SV_GROUP_MSG
 
     def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
         super().__init__()
         self.npoint = npoint
         self.radius_list = list(radius_list)
         self.nsample_list = list(nsample_list)
-        self.fused = True  # False: the unfused eval path (tests, timing)
         self.conv_blocks = nn.ModuleList()
         self.bn_blocks = nn.ModuleList()
         for mlp in mlp_list:
@@ -530,105 +555,28 @@ class PointNetSetAbstractionMsg(FoldCache):
             self.conv_blocks.append(convs)
             self.bn_blocks.append(bns)
 
-    def _folded(self):
-        """(per-scale layer folds, per-scale packed parameters, host arrays of sv_pointnet_sa_msg) - built once per
-        weights / device"""
-        from ctypes import c_void_p
+    def _scales(self):
+        return list(zip(self.radius_list, self.nsample_list, self.conv_blocks, self.bn_blocks))
 
-        def build():
-            folds = [[_fold_conv_bn(c, b) for c, b in zip(convs, bns)]
-                     for convs, bns in zip(self.conv_blocks, self.bn_blocks)]
-            packed = [torch.cat([t.reshape(-1).to(torch.float32) for f in fs for t in f]).contiguous() for fs in folds]
-            widths = [w for convs in self.conv_blocks for w in [convs[0].in_channels] + [c.out_channels for c in convs]]
-            R = len(folds)
-            host = ((c_int * R)(*self.nsample_list), (c_void_p * R)(*[p.data_ptr() for p in packed]),
-                    (c_int * len(widths))(*widths), (c_int * R)(*[len(convs) for convs in self.conv_blocks]))
-            return folds, packed, host
-
-        return self._fold_get(build)
-
-    def _fused(self, xyz, points, new_xyz, idxs, folds):
-        """sv_pointnet_sa_msg: every scale's gather + shared MLP + max in one launch -> [B, S, sum C_r], or None where the
-        kernel does not cover the shapes (SV_ERR_UNSUPPORTED: nothing was launched)."""
-        from ctypes import c_void_p
-
-        from .. import _lib
-
-        _, _, (nsamples, params, widths, nlayers) = folds
-        B, N, _ = xyz.shape
-        S = new_xyz.shape[1]
-        x = xyz.to(torch.float32).contiguous()
-        p = points.to(torch.float32).contiguous() if points is not None else None
-        D = p.shape[2] if p is not None else 0
-        q = new_xyz.to(torch.float32).contiguous()
+    def _launch_fused(self, x, p, q, idxs, B, N, D, S, packed, host, out):
+        nsamples, params, widths, nlayers = host
         R = len(idxs)
-        ctot = sum(convs[-1].out_channels for convs in self.conv_blocks)
-        out = torch.empty((B, S, ctot), dtype=torch.float32, device=xyz.device)
-        rc = _lib.load().sv_pointnet_sa_msg(ptr(x), ptr(p), ptr(q), B, N, D, S, R, nsamples,
-                                            (c_void_p * R)(*[t.data_ptr() for t in idxs]), params, widths, nlayers,
-                                            ptr(out), stream_ptr())
-        if rc == _lib.SV_ERR_UNSUPPORTED:
-            return None
-        _lib._check(rc, "sv_pointnet_sa_msg")
-        return out
-
-    def _unfused(self, xyz, points, new_xyz, idxs, folds):
-        """every scale: MSG-order gather, its layers one launch each (dense rows), torch.max; then torch.cat"""
-        pooled = []
-        for i, idx in enumerate(idxs):
-            grouped = _group_msg(xyz, points, new_xyz, idx)
-            B, S, Kn, C = grouped.shape
-            rows = _mlp_rows(grouped.reshape(B * S * Kn, C).contiguous(), self.conv_blocks[i], self.bn_blocks[i],
-                             folds[0][i])
-            pooled.append(rows.view(B, S, Kn, -1).max(dim=2)[0])
-        return torch.cat(pooled, dim=-1)
+        return _lib.load().sv_pointnet_sa_msg(ptr(x), ptr(p), ptr(q), B, N, D, S, R, nsamples,
+                                              (c_void_p * R)(*[t.data_ptr() for t in idxs]), params, widths, nlayers,
+                                              ptr(out), stream_ptr())
 
     def forward(self, xyz, points, fps_start=None):
-        """xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points [B, sum C_r, S].  fps_start int64 [B] pins
-        the first farthest-point centroids (None: drawn as the reference draws them)."""
         D = 0 if points is None else points.shape[1]
         want = self.conv_blocks[0][0].in_channels - 3
         if xyz.dim() != 3 or xyz.shape[1] != 3 or D != want:
             raise ValueError(f"multi-scale set abstraction expects xyz [B, 3, N] and {want} point features, got "
                              f"xyz {tuple(xyz.shape)} and {D} features")
-        xyz = xyz.permute(0, 2, 1)
-        if points is not None:
-            points = points.permute(0, 2, 1)
-        hip = _hip_train(self, xyz)
-        fps_idx = farthest_point_sample(xyz, self.npoint, start=fps_start)
-        new_xyz = index_points(xyz, fps_idx)
-        if hip:  # every scale: sv_group_rows (MSG order) -> shared MLP on rows -> sv_group_max, then torch.cat
-            B, S = new_xyz.shape[0], new_xyz.shape[1]
-            pooled = []
-            for i, idx in enumerate(query_ball_point_multi(self.radius_list, self.nsample_list, xyz, new_xyz)):
-                rows = group_rows(xyz, points, new_xyz, idx, SV_GROUP_MSG, self)
-                rows = _mlp_rows_train(rows, self.conv_blocks[i], self.bn_blocks[i])
-                pooled.append(group_max(rows, self.nsample_list[i], self).view(B, S, -1))
-            return new_xyz.permute(0, 2, 1), torch.cat(pooled, dim=-1).permute(0, 2, 1)
-        if self.training:  # the reference's torch path (:238-262)
-            pooled = []
-            for i, (radius, K) in enumerate(zip(self.radius_list, self.nsample_list)):
-                idx = query_ball_point(radius, K, xyz, new_xyz)
-                t = _group_msg(xyz, points, new_xyz, idx).permute(0, 3, 2, 1)
-                for conv, bn in zip(self.conv_blocks[i], self.bn_blocks[i]):
-                    t = F.relu(bn(conv(t)))
-                pooled.append(torch.max(t, 2)[0])
-            return new_xyz.permute(0, 2, 1), torch.cat(pooled, dim=1)
-        idxs = query_ball_point_multi(self.radius_list, self.nsample_list, xyz, new_xyz)
-        folds = self._folded()
-        pooled = self._fused(xyz, points, new_xyz, idxs, folds) if self.fused and xyz.is_cuda else None
-        if pooled is None:
-            pooled = self._unfused(xyz, points, new_xyz, idxs, folds)
-        return new_xyz.permute(0, 2, 1), pooled.permute(0, 2, 1)
+        return super().forward(xyz, points, fps_start)
 
 
 def three_nn_interpolate(xyz1, xyz2, points2):
     """[B,N,3], [B,S,3], [B,S,C] -> [B,N,C]: 3-NN inverse-distance interpolation on libsvhip (sv_three_nn_interpolate),
     replacing the reference's full [B,N,S] distance matrix + sort (model/pointnet2_utils.py:298-305)."""
-    from ctypes import c_int
-
-    from .._lib import call, ptr, stream_ptr
-
     B, N, _ = xyz1.shape
     S, C = points2.shape[1], points2.shape[2]
     x1, x2, p2 = (t.to(torch.float32).contiguous() for t in (xyz1, xyz2, points2))
@@ -653,15 +601,17 @@ class PointNetFeaturePropagation(FoldCache):
 
     def forward(self, xyz1, xyz2, points1, points2):
         """3-NN inverse-distance interpolation of points2 (at xyz2) onto xyz1, concat points1, shared MLP."""
-        if _hip_train(self, xyz1, xyz2):
-            return self._train_hip(xyz1, xyz2, points1, points2)
+        hip = _hip_train(self, xyz1, xyz2)
         xyz1 = xyz1.permute(0, 2, 1)
         xyz2 = xyz2.permute(0, 2, 1)
         points2 = points2.permute(0, 2, 1)
         B, N, _ = xyz1.shape
         S = xyz2.shape[1]
-        if S == 1:
+        if S == 1:  # one source point: the torch broadcast
             interpolated = points2.repeat(1, N, 1)
+        elif hip:  # the fused kernel in two launches: the neighbours and weights are kept for the backward
+            idx, w = three_nn(xyz1, xyz2, self)
+            interpolated = three_nn_gather(points2, idx, w, self)
         elif not self.training and xyz1.is_cuda and S >= 3:
             interpolated = three_nn_interpolate(xyz1, xyz2, points2)
         else:
@@ -670,27 +620,15 @@ class PointNetFeaturePropagation(FoldCache):
             weight = recip / recip.sum(dim=2, keepdim=True)
             interpolated = torch.sum(index_points(points2, idx) * weight.view(B, N, 3, 1), dim=2)
         new_points = interpolated if points1 is None else torch.cat([points1.permute(0, 2, 1), interpolated], dim=-1)
-        if self.training:
+        if self.training and not hip:
             t = new_points.permute(0, 2, 1)
             for conv, bn in zip(self.mlp_convs, self.mlp_bns):
                 t = F.relu(bn(conv(t)))
             return t
-        folds = self._fold_get(lambda: [_fold_conv_bn(conv, bn) for conv, bn in zip(self.mlp_convs, self.mlp_bns)])
-        rows = _mlp_rows(new_points.reshape(B * N, -1).contiguous(), self.mlp_convs, self.mlp_bns, folds)
-        return rows.view(B, N, -1).permute(0, 2, 1)
-
-    def _train_hip(self, xyz1, xyz2, points1, points2):
-        """train() on the HIP path: sv_three_nn + sv_three_nn_gather (one source point: the torch broadcast), concat
-        points1, shared MLP on rows"""
-        xyz1 = xyz1.permute(0, 2, 1)
-        xyz2 = xyz2.permute(0, 2, 1)
-        points2 = points2.permute(0, 2, 1)
-        B, N, _ = xyz1.shape
-        if xyz2.shape[1] == 1:
-            interpolated = points2.repeat(1, N, 1)
+        rows = new_points.reshape(B * N, -1)
+        if hip:
+            rows = _mlp_rows_train(rows, self.mlp_convs, self.mlp_bns)
         else:
-            idx, w = three_nn(xyz1, xyz2, self)
-            interpolated = three_nn_gather(points2, idx, w, self)
-        new_points = interpolated if points1 is None else torch.cat([points1.permute(0, 2, 1), interpolated], dim=-1)
-        rows = _mlp_rows_train(new_points.reshape(B * N, -1), self.mlp_convs, self.mlp_bns)
+            folds = self._fold_get(lambda: _fold_mlp(self.mlp_convs, self.mlp_bns))
+            rows = _mlp_rows(rows.contiguous(), self.mlp_convs, self.mlp_bns, folds)
         return rows.view(B, N, -1).permute(0, 2, 1)

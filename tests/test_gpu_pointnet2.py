@@ -127,7 +127,7 @@ def test_fused_set_abstraction_tail_workgroup(gpu, nsample):
         x = xyz.permute(0, 2, 1).contiguous()
         p = pts.permute(0, 2, 1).contiguous()
         rc = load().sv_pointnet_sa(ptr(x), ptr(p), ptr(nx.contiguous()), ptr(idx), B, N, cin - 3, S, nsample,
-                                   ptr(folds[1]), folds[2], len(mlp), ptr(out), stream_ptr())
+                                   ptr(folds[1][0]), folds[2][2], len(mlp), ptr(out), stream_ptr())
     assert rc == 0
     assert torch.equal(got, want)
     assert torch.equal(out[:B * S].view(B, S, -1).permute(0, 2, 1), want)

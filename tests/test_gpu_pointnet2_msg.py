@@ -69,6 +69,34 @@ def test_ball_query_multi_equals_per_radius_ball_query(gpu, case):
     assert padded > 0  # first-hit padding occurs in every case
 
 
+@pytest.mark.parametrize("nsample,shift", [(16, 0.0), (65, 0.0), (16, 10.0)])
+def test_one_radius_instance_equals_the_multi_instance_with_one_radius(gpu, nsample, shift):
+    """sv_ball_query (the kernel template's one-radius instance) against sv_ball_query_multi called with R = 1 (its
+    SV_BQ_MAX_RADII instance), bit for bit.  N = 130 is two full 64-point steps and a partial one; B * S = 10 leaves the
+    last 4-query workgroup half full.  130 uniform points put 5 .. 21 neighbours into these balls of radius 0.3 (nearest
+    distance to the r^2 boundary 4.5e-5, far above float32 rounding): nsample 16 meets padded and full balls, which the
+    test asserts; nsample 65 pads every ball past lane 63 of the padding loop - no ball of this cloud can hold 65, so
+    that case asserts the padded balls alone; centres shifted by +10 leave every ball empty, every entry N."""
+    from mrcc_amd.model.pointnet2_utils import query_ball_point, query_ball_point_multi
+
+    B, N, S, radius = 2, 130, 5, 0.3
+    xyz = (torch.rand(B, N, 3, generator=torch.Generator().manual_seed(1)) - 0.5).to(gpu)
+    new_xyz = (xyz[:, :S] + shift).contiguous()
+    one = query_ball_point(radius, nsample, xyz, new_xyz)
+    multi = query_ball_point_multi([radius], [nsample], xyz, new_xyz)
+    assert len(multi) == 1 and one.shape == (B, S, nsample)
+    assert torch.equal(one, multi[0])
+    padded = one[..., -1] == one[..., 0]  # a ball with fewer hits than nsample ends in copies of its first hit
+    if shift:
+        assert (one == N).all()
+    else:
+        assert (one < N).all() and padded.any()
+        if nsample == 16:
+            assert (~padded).any()
+        else:
+            assert padded.all()
+
+
 def _layer(gpu, shape, seed, B=2, S=None, D=None, N=None):
     from mrcc_amd.model import pointnet2_utils as P2
 
@@ -114,7 +142,7 @@ def test_fused_msg_layer_is_the_unfused_eval_path(gpu, layer):
     nx = P2.index_points(x, P2.farthest_point_sample(x, sa.npoint, start=start))
     cols = []
     for i, (r, k) in enumerate(zip(sa.radius_list, sa.nsample_list)):
-        t = P2._group_msg(x, p, nx, P2.query_ball_point(r, k, x, nx)).double().permute(0, 3, 2, 1)
+        t = P2._group(x, p, nx, P2.query_ball_point(r, k, x, nx), P2.SV_GROUP_MSG).double().permute(0, 3, 2, 1)
         for conv, bn in zip(sa.conv_blocks[i], sa.bn_blocks[i]):
             t = F.relu(F.batch_norm(F.conv2d(t, conv.weight.double(), conv.bias.double()), bn.running_mean.double(),
                                     bn.running_var.double(), bn.weight.double(), bn.bias.double(), False, 0.0, bn.eps))

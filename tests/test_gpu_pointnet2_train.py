@@ -47,7 +47,7 @@ def test_group_rows_equals_torch_gather(mods, order, D):
     idx = U.query_ball_point(0.15, K, xyz, new_xyz)  # small radius: many balls padded with the first hit
     assert (idx[..., -1] == idx[..., 0]).any()
     rows = U.group_rows(xyz, pts, new_xyz, idx, order)
-    want = U._group(xyz, pts, new_xyz, idx)[1] if order == 0 else U._group_msg(xyz, pts, new_xyz, idx)
+    want = U._group(xyz, pts, new_xyz, idx, order)
     assert torch.equal(rows.view(B, S, K, -1), want)
 
 

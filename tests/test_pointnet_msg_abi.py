@@ -120,3 +120,36 @@ def test_msg_modules_check_channels_without_gpu():
         net.sa2(torch.zeros(1, 3, 64), torch.zeros(1, 300, 64))
     with pytest.raises(ValueError):
         PointNetSetAbstractionMsg(8, [0.1], [16], 0, [[32]])(torch.zeros(1, 3, 64), torch.zeros(1, 3, 64))
+
+
+# state_dict keys of the three PointNet++ layer modules, in order, as checkpoints of the reference hold them
+SA_KEYS = ["mlp_convs.0.weight", "mlp_convs.0.bias", "mlp_convs.1.weight", "mlp_convs.1.bias", "mlp_bns.0.weight",
+    "mlp_bns.0.bias", "mlp_bns.0.running_mean", "mlp_bns.0.running_var", "mlp_bns.0.num_batches_tracked",
+    "mlp_bns.1.weight", "mlp_bns.1.bias", "mlp_bns.1.running_mean", "mlp_bns.1.running_var",
+    "mlp_bns.1.num_batches_tracked"]
+MSG_KEYS = ["conv_blocks.0.0.weight", "conv_blocks.0.0.bias", "conv_blocks.0.1.weight", "conv_blocks.0.1.bias",
+    "conv_blocks.1.0.weight", "conv_blocks.1.0.bias", "conv_blocks.1.1.weight", "conv_blocks.1.1.bias",
+    "conv_blocks.1.2.weight", "conv_blocks.1.2.bias", "bn_blocks.0.0.weight", "bn_blocks.0.0.bias",
+    "bn_blocks.0.0.running_mean", "bn_blocks.0.0.running_var", "bn_blocks.0.0.num_batches_tracked",
+    "bn_blocks.0.1.weight", "bn_blocks.0.1.bias", "bn_blocks.0.1.running_mean", "bn_blocks.0.1.running_var",
+    "bn_blocks.0.1.num_batches_tracked", "bn_blocks.1.0.weight", "bn_blocks.1.0.bias", "bn_blocks.1.0.running_mean",
+    "bn_blocks.1.0.running_var", "bn_blocks.1.0.num_batches_tracked", "bn_blocks.1.1.weight", "bn_blocks.1.1.bias",
+    "bn_blocks.1.1.running_mean", "bn_blocks.1.1.running_var", "bn_blocks.1.1.num_batches_tracked",
+    "bn_blocks.1.2.weight", "bn_blocks.1.2.bias", "bn_blocks.1.2.running_mean", "bn_blocks.1.2.running_var",
+    "bn_blocks.1.2.num_batches_tracked"]
+
+
+def test_layer_modules_keep_their_state_dict_keys_and_training_switch():
+    """parameter and buffer names (so checkpoints load by key) of the single-scale, multi-scale and feature-propagation
+    layers, and the modules set_training_path switches in a container of the three"""
+    import torch
+
+    from mrcc_amd.model import pointnet2_utils as U
+
+    sa = U.PointNetSetAbstraction(32, 0.2, 16, 6, [16, 32], False)
+    msg = U.PointNetSetAbstractionMsg(32, [0.1, 0.2], [16, 32], 3, [[16, 32], [16, 16, 32]])
+    fp = U.PointNetFeaturePropagation(48, [32, 16])
+    assert list(sa.state_dict().keys()) == SA_KEYS
+    assert list(msg.state_dict().keys()) == MSG_KEYS
+    assert list(fp.state_dict().keys()) == SA_KEYS  # mlp_convs.i / mlp_bns.i, as the single-scale layer
+    assert U.set_training_path(torch.nn.ModuleList([sa, msg, fp]), "hip") == ["0", "1", "2"]

@@ -66,7 +66,8 @@ const char* sv_last_error(void);
  * 4: sv_conv_set_dispatch (per-thread dispatch thresholds: one frame alone vs frames overlapped), the frame composites
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
- *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5 */
+ *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
+ *    entries of N6 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -587,6 +588,70 @@ int sv_augment_points(const void* points, int points_f64, const int32_t* offsets
                       size_t workspace_bytes, double* out, double* stats, sv_stream_t stream);
 int sv_quantise_points(const double* points, const int32_t* offsets, int64_t N, int B, const double* stats, int origin,
                        double quantization_size, int32_t* coords, float* shifted, double* shift_out, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N6  per-frame training labels synthesised from the frame's pose (replace utils/data.py:58-103 get_roi_mask / get_ee_idx,
+ *      :106-122 get_ee_cross_section_idx with utils/transformation.py:138-160, :125-335 get_closest_point / get_key_points /
+ *      get_6_key_points, :338-342 collect_closest_points and the label write of data/alivev2.py:212-238), for a batch of
+ *      frames per call.  Additions of ABI 4.
+ *
+ * Common arguments: points float32[N][3] (float64[N][3] with points_f64 != 0) of B frames, frame b owning rows
+ *   offsets[b] .. offsets[b+1]-1 (int32[B+1] on the device, non-decreasing inside [0, N]; anything else is clamped so that
+ *   no access leaves the arrays; a frame without rows is legal everywhere); pos float64[B][3] and rot float64[B][9]
+ *   (row-major get_quaternion_rotation_matrix of the frame's quaternion, computed on the host) on the device.
+ *   B in [1, SV_MAX_BATCH], N in [0, 2^29).  Every entry validates on the host before any HIP call, launches on the stream
+ *   and never waits or reads back.  No atomics: the same arguments give the same bits.
+ *
+ * dtype rules (numpy's promotion in the reference, float64 pose):
+ *   get_ee_idx                 float64 throughout: d = (double)p - pos, q = R^T d
+ *   get_key_points / get_6_..  float64 throughout: q = R^T (double)p - R^T pos (the position is rotated with the points
+ *                              and subtracted afterwards, center_at_origin of one row)
+ *   get_ee_cross_section_idx   the in-place `-= pose[:3]` rounds d to the points' dtype: d = (T)((double)p - pos), then
+ *                              q = R^T (double)d and the line distance in float64
+ *   collect_closest_points     entirely in the points' dtype T: difference, squares, (a + b) + c, sqrt, compare against (T)thr
+ *   Products R^T v and R v are three-term sums (a + b) + c without fma; norms are sqrt((x^2 + y^2) + z^2).
+ *
+ * sv_ee_mask: mask uint8[N] = 1 where q = R^T (p - pos) satisfies q.x > -500 and the six strict inequalities of
+ *   get_roi_mask against box = HOST float64[6] (min_x, max_x, min_y, max_y, min_z, max_z; NULL: the reference's ee_dim_init
+ *   -0.05, 0.05, -0.11, 0.11, -0.006, 0.12).  A row with a NaN is outside; a row no frame owns gets 0.
+ *
+ * sv_key_points: mode 10 = get_key_points, mode 6 = get_6_key_points; K = mode.  key_points float64[B][K][3] in the
+ *   camera frame, kp_idx int64[B][K] = index within the frame or ignore_label (< 0).  Every search is an arg-min over
+ *   (distance, index) on the rows a mask selects: numpy argmin's rule (a NaN distance wins at its first index, a tie goes
+ *   to the lower index); a thresholded search finds its key point when that distance < euclidean_threshold.
+ *   mode 10: P1-P4 on q.x > 0.005 (found: the key point moves to the row and its back-side twin to row + (-0.04 | -0.03,
+ *   0, 0)); P7-P10 on q.x < -0.01 against the moved twins; the gripper pair on q.z > 0.08 with q.y > 0 / < 0 against
+ *   (0, +-0.01, max z of the selection), no threshold; a missing gripper side mirrors the other one, both get the larger
+ *   z; then + R^T pos and R @.  mode 6: the rows nearest the four box corners on (q.x > -0.005) and (q.z < 0.09), kept
+ *   when within the threshold of the template key point; the same gripper pair.
+ *   kp_idx of a gripper key point is what the reference records (:227, :239), not the row the coordinates come from: the
+ *   winner's position within its side's subset, looked up in the list of all rows with q.z > 0.08.
+ *   Where the reference fails, defined here: an empty selection of a search means "not found" (index ignore_label, the
+ *   template coordinates kept; get_key_points raises a TypeError on an empty front side); mode 6 with an empty selection
+ *   gives the template key points (carried to the camera frame like any result) and ignore_label everywhere, and
+ *   selection_empty[b] = 1 (int32[B], may be NULL; 0 otherwise) so that a caller can return the reference's empty arrays.
+ *
+ * sv_line_topk: get_ee_cross_section_idx / select_closest_points_to_line.  dist(q) = ||(lp1 + t d) - q||,
+ *   t = (q - lp1) . d, d = (lp1 - lp2) / ||lp1 - lp2|| (compute_dists_to_line; lp1, lp2 HOST float64[3], distinct and
+ *   finite).  Per frame the `count` (1..1024) smallest distances in ascending order, a tie to the lower index, cut at the
+ *   first that is not < cutoff (a NaN distance never qualifies): idx int64[B][count] (index within the frame, padded with
+ *   -1), dist float64[B][count] (padded with +inf), n_sel int32[B].  workspace: sv_line_topk_workspace_bytes(N).
+ *
+ * sv_radius_labels: labels int64[N]: row i of frame b gets the largest k < K (1..64) whose anchor row kp_idx[b][k]
+ *   (int64[B][K], index within the frame; negative or >= the frame's length: takes no part) lies at distance
+ *   < euclidean_threshold, computed in the points' dtype; no such k (or a row no frame owns): ignore_label (< 0).
+ * ------------------------------------------------------------------------------------------- */
+int sv_ee_mask(const void* points, int points_f64, const int32_t* offsets, int64_t N, int B, const double* pos,
+               const double* rot, const double* box, uint8_t* mask, sv_stream_t stream);
+int sv_key_points(const void* points, int points_f64, const int32_t* offsets, int64_t N, int B, const double* pos,
+                  const double* rot, int mode, double euclidean_threshold, int64_t ignore_label, double* key_points,
+                  int64_t* kp_idx, int32_t* selection_empty, sv_stream_t stream);
+size_t sv_line_topk_workspace_bytes(int64_t N);
+int sv_line_topk(const void* points, int points_f64, const int32_t* offsets, int64_t N, int B, const double* pos,
+                 const double* rot, const double* lp1, const double* lp2, int count, double cutoff, void* workspace,
+                 size_t workspace_bytes, int64_t* idx, double* dist, int32_t* n_sel, sv_stream_t stream);
+int sv_radius_labels(const void* points, int points_f64, const int32_t* offsets, int64_t N, int B, const int64_t* kp_idx,
+                     int K, double euclidean_threshold, int64_t ignore_label, int64_t* labels, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,

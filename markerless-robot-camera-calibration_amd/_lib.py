@@ -120,6 +120,11 @@ SIGNATURES = {
     "sv_augment_points_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_augment_points": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, c_int64, _P, _P, c_size_t, _P, _P, _P]),
     "sv_quantise_points": (c_int, [_P, _P, c_int64, c_int, _P, c_int, c_double, _P, _P, _P, _P]),
+    "sv_ee_mask": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, _P, _P, _P]),
+    "sv_key_points": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, c_int, c_double, c_int64, _P, _P, _P, _P]),
+    "sv_line_topk_workspace_bytes": (c_size_t, [c_int64]),
+    "sv_line_topk": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, _P, _P, c_int, c_double, _P, c_size_t, _P, _P, _P, _P]),
+    "sv_radius_labels": (c_int, [_P, c_int, _P, c_int64, c_int, _P, c_int, c_double, c_int64, _P, _P]),
     "sv_fps": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_interpolate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "sv_cluster_workspace_bytes": (c_size_t, [c_int64]),

@@ -325,7 +325,7 @@ def augment_segmentation(points, scale=200, probability=0.2, copy=False, elastic
 def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quantization_size, probability=0.2,
                            elastic=False, noise=False, transform=False, flip=False, gravity=False,
                            center_at_origin=False, base_at_origin=False, ignore_label=-100, rng=None, generator=None,
-                           device="cuda", return_extras=False):
+                           device="cuda", return_extras=False, point_offsets=None):
     """A training batch from the frames a dataset yields: augment_segmentation, centring (center_at_origin, else
     base_at_origin: data/alivev2.py:199-208), ME.utils.sparse_quantize and the collate of data/alivev2.py:358-365, on
     the device, for all frames at once.
@@ -333,6 +333,11 @@ def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quan
     points / feats / labels: lists of host arrays [n_b, 3] / [n_b, C] / [n_b] (or [n_b, 1]).  draws: one
     AugmentationDraws per frame (draw_augmentations(...) with `rng` when None).  Per-point normals a frame's draws do not
     carry come from torch.randn(..., dtype=float64, generator=generator) on the device.
+
+    With point_offsets ([B + 1], host or device) points / feats / labels may each instead be ONE CUDA tensor of the
+    frames' concatenated rows ([N, 3] float32 or float64, [N, C], [N] or [N, 1]), e.g. what utils.data.ee_crop_batch and
+    key_point_labels_batch return: nothing visits the host.  Device offsets are only read back when the host needs the
+    frames' lengths: to draw augmentations (draws None with a stage enabled) or to place normals a draws object carries.
 
     Returns device tensors (coords_batch int32 [V, 4], feats_batch float32 [V, C], labels_batch int64 [V],
     voxel_offsets int32 [B + 1]), ready for ME.SparseTensor(feats_batch, coordinates=coords_batch).  Voxels are in
@@ -343,13 +348,20 @@ def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quan
 
     Launches: sv_elastic_field (if any frame has an elastic stage), sv_augment_points, sv_quantise_points, sv_voxelize.
     The only host wait is sv_voxelize's voxel-count read-back."""
-    from ..MinkowskiEngine.utils import resolve_voxel_labels
-    from ..sparse import _voxelize
-
+    dev = torch.device(device)
+    if point_offsets is not None:
+        if dev.type != "cuda":
+            raise SvHipError(f"augment_quantize_batch runs on the GPU (got device {dev}); there is no CPU fallback")
+        return _augment_quantize_device(points, feats, labels, point_offsets, dev, draws=draws, scale=scale,
+                                        quantization_size=quantization_size, probability=probability,
+                                        flags=dict(elastic=elastic, noise=noise, transform=transform, flip=flip,
+                                                   gravity=gravity),
+                                        center_at_origin=center_at_origin, base_at_origin=base_at_origin,
+                                        ignore_label=ignore_label, rng=rng, generator=generator,
+                                        return_extras=return_extras)
     B = len(points)
     if not (B == len(feats) == len(labels)) or not 1 <= B <= _lib.SV_MAX_BATCH:
         raise ValueError(f"need the same number (1 to {_lib.SV_MAX_BATCH}) of point, feature and label arrays")
-    dev = torch.device(device)
     if dev.type != "cuda":
         raise SvHipError(f"augment_quantize_batch runs on the GPU (got device {dev}); there is no CPU fallback")
     pts = [np.asarray(p) for p in points]
@@ -391,6 +403,16 @@ def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quan
                 if d.noise and d.normals is not None:
                     normals[off_np[b]: off_np[b + 1]] = torch.from_numpy(
                         np.asarray(d.normals, dtype=np.float64).reshape(int(lens[b]), 3)).to(dev)
+    return _augment_quantize_launch(pts_d, off_d, table_d, feats_d, labels_d, normals, raw, dims, B, dev,
+                                    center_at_origin, base_at_origin, quantization_size, ignore_label, return_extras)
+
+
+def _augment_quantize_launch(pts_d, off_d, table_d, feats_d, labels_d, normals, raw, dims, B, dev, center_at_origin,
+                             base_at_origin, quantization_size, ignore_label, return_extras):
+    """the launches of augment_quantize_batch on device tensors"""
+    from ..MinkowskiEngine.utils import resolve_voxel_labels
+    from ..sparse import _voxelize
+
     with torch.cuda.device(dev):
         fields = elastic_fields(raw, dims, dev) if len(dims) else None
         aug, stats = augment_points(pts_d, off_d, table_d, fields, normals)
@@ -405,3 +427,76 @@ def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quan
     if return_extras:
         return res + ({"origin_offset": shift, "points": shifted, "point_offsets": off_d, "inverse": inverse},)
     return res
+
+
+def _rows_on_device(x, what, dev, dtype, N=None):
+    """one CUDA tensor of concatenated rows, or a list of per-frame host arrays (concatenated and uploaded)"""
+    if isinstance(x, torch.Tensor):
+        if not x.is_cuda:
+            raise SvHipError(f"{what} must be a CUDA tensor or a list of host arrays (got a {x.device} tensor)")
+        t = x if dtype is None else x.to(dtype)
+    else:
+        a = np.concatenate([np.asarray(f).reshape(len(f), -1) for f in x])
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        t = t if dtype is None else t.to(dtype)
+    if N is not None and t.shape[0] != N:
+        raise ValueError(f"{what} need one row per point ({N}), got {t.shape[0]}")
+    return t
+
+
+def _augment_quantize_device(points, feats, labels, point_offsets, dev, *, draws, scale, quantization_size, probability,
+                             flags, center_at_origin, base_at_origin, ignore_label, rng, generator, return_extras):
+    """augment_quantize_batch on concatenated device tensors with point_offsets"""
+    pts_d = _rows_on_device(points, "points", dev, None)
+    if pts_d.dim() != 2 or pts_d.shape[1] != 3:
+        raise ValueError(f"points must be [N, 3], got {tuple(pts_d.shape)}")
+    if pts_d.dtype not in (torch.float32, torch.float64):
+        pts_d = pts_d.to(torch.float64)
+    pts_d = pts_d.contiguous()
+    N = pts_d.shape[0]
+    if N < 1:
+        raise ValueError("the batch has no points")
+    feats_d = _rows_on_device(feats, "feats", dev, torch.float32, N).reshape(N, -1).contiguous()
+    labels_d = _rows_on_device(labels, "labels", dev, torch.int64, N).reshape(-1).contiguous()
+    if labels_d.numel() != N:
+        raise ValueError("labels need one value per point")
+    host_off = None
+    if isinstance(point_offsets, torch.Tensor) and point_offsets.is_cuda:
+        off_d = point_offsets.to(torch.int32).contiguous().reshape(-1)
+    else:
+        host_off = np.asarray(point_offsets, dtype=np.int64).reshape(-1)
+        if len(host_off) < 2 or host_off[0] != 0 or host_off[-1] != N or (np.diff(host_off) < 0).any():
+            raise ValueError(f"point_offsets must rise from 0 to the number of points ({N})")
+        off_d = torch.from_numpy(host_off.astype(np.int32)).to(dev)
+    B = off_d.numel() - 1
+    if not 1 <= B <= _lib.SV_MAX_BATCH:
+        raise ValueError(f"need 1 to {_lib.SV_MAX_BATCH} frames, got {B}")
+
+    def offsets_on_host():
+        nonlocal host_off
+        if host_off is None:
+            host_off = off_d.cpu().numpy().astype(np.int64)
+        return host_off
+
+    if draws is None:
+        if any(flags.values()):
+            o = offsets_on_host()
+            abs_max = torch.stack([pts_d[o[b]: o[b + 1]].abs().amax(0) if o[b + 1] > o[b] else pts_d.new_zeros(3)
+                                   for b in range(B)]).cpu().numpy()
+            draws = draw_augmentations(abs_max, scale=scale, probability=probability, rng=rng, **flags)
+        else:
+            draws = [AugmentationDraws() for _ in range(B)]
+    if len(draws) != B:
+        raise ValueError("one draws object per frame")
+    table, raw, dims = _table_and_fields(draws)
+    normals = None
+    if any(d.noise for d in draws):
+        normals = torch.randn((N, 3), dtype=torch.float64, device=dev, generator=generator)
+        for b, d in enumerate(draws):
+            if d.noise and d.normals is not None:
+                o = offsets_on_host()
+                normals[o[b]: o[b + 1]] = torch.from_numpy(
+                    np.asarray(d.normals, dtype=np.float64).reshape(int(o[b + 1] - o[b]), 3)).to(dev)
+    table_d = torch.from_numpy(table).to(dev, non_blocking=True)
+    return _augment_quantize_launch(pts_d, off_d, table_d, feats_d, labels_d, normals, raw, dims, B, dev,
+                                    center_at_origin, base_at_origin, quantization_size, ignore_label, return_extras)

@@ -5,6 +5,7 @@
   get_rigid_transform_3D_batched(...)                         B problems in one launch (one wavefront each)
   get_quaternion_rotation_matrix / get_transformation_matrix(_inverse) / get_pose_from_matrix / get_base2cam_pose /
   transform_pose2pose                                          reference: :16-77, :87-93, :225-266 (small host algebra)
+  compute_dists_to_line / compute_vec_dist_to_line / select_closest_points_to_line   reference: :134-160 (host numpy)
 Arguments, return types (numpy float64) and error behaviour follow the reference.
 """
 from ctypes import c_int
@@ -138,3 +139,29 @@ def transform_pose2pose_matrix(pose1, pose2):
 
 def transform_pose2pose(pose1, pose2):
     return get_pose_from_matrix(transform_pose2pose_matrix(pose1, pose2))
+
+
+def compute_dists_to_line(p, lp1, lp2):
+    """Distance of every row of p [n, 3] to the line through lp1 and lp2 (utils/transformation.py:138-147): with the
+    unit direction d = (lp1 - lp2) / ||lp1 - lp2||, the foot of the perpendicular is lp1 + ((p - lp1) . d) d.  Host
+    numpy: callers use it on a handful of points; a batch of frames goes through sv_line_topk (utils/data.py)."""
+    lp1, lp2 = np.asarray(lp1), np.asarray(lp2)
+    d = (lp1 - lp2) / np.linalg.norm(lp1 - lp2)
+    t = np.dot(p - lp1, d).reshape((-1, 1))
+    return np.linalg.norm((lp1 + t * d) - p, axis=1)
+
+
+def compute_vec_dist_to_line(p, lp1, lp2):
+    """:134-135: the first entry of compute_dists_to_line on p as a column, with the broadcasting that implies."""
+    return compute_dists_to_line(np.asarray(p).reshape((-1, 1)), lp1, lp2)[0]
+
+
+def select_closest_points_to_line(points, lp1, lp2, count=0, cutoff=0.008):
+    """(dists, idx) of the `count` rows closest to the line (all rows when count <= 0), ascending, those at or beyond
+    `cutoff` dropped (:150-160).  As there, the distances are taken with the two line points swapped."""
+    n = len(points)
+    count = min(count, n) if count > 0 else n
+    dists = compute_dists_to_line(points, lp2, lp1)
+    first = np.argsort(dists)[:count]
+    idx = first[dists[first] < cutoff]
+    return dists[idx], idx

@@ -14,7 +14,8 @@ get_pred_center and get_key_point_predictions, are pure torch/numpy and never to
 `pose_losses` imports the reference's utils/loss.py with `utils.config` replaced by a stub (_StubConfig) that carries the
 keys the criteria read: the real module parses sys.argv and creates directories when it is imported.  `augmentation`
 imports the reference's utils/augmentation.py with an empty `open3d` module beside the `ipdb` one (only
-change_background, which is not recorded, uses it).
+change_background, which is not recorded, uses it).  `labels` runs the reference's utils/data.py with `np.int = int` set
+for the call (get_6_key_points uses the alias numpy removed).
 """
 import os
 import sys
@@ -594,6 +595,140 @@ def gen_augmentation(rng):
     return out
 
 
+def _gap(d):
+    """smallest minus second smallest of d (inf with fewer than two entries)"""
+    d = np.sort(np.asarray(d, dtype=np.float64))
+    return np.inf if len(d) < 2 else float(d[1] - d[0])
+
+
+def _label_margins(points, crop, pose, cs_count, cs_cutoff, radius, kp_idx_sets):
+    """The smallest distance of any decision the five functions take on this case to its tipping point, in the
+    reference's own expressions: (float64 decisions, decisions computed in the points' dtype)."""
+    R = T.get_quaternion_rotation_matrix(pose[3:], switch_w=False)
+    m64, mT = [], []
+    q = (R.T @ (points - pose[:3]).reshape((-1, 3, 1))).reshape((-1, 3))  # get_ee_idx
+    for c, (lo, hi) in enumerate(((-0.05, 0.05), (-0.11, 0.11), (-0.006, 0.12))):
+        m64 += [np.abs(q[:, c] - lo).min(), np.abs(q[:, c] - hi).min()]
+    q = (R.T @ np.concatenate((crop, pose[:3].reshape(1, 3))).reshape((-1, 3, 1))).reshape((-1, 3))  # key points
+    q = q[:-1] - q[-1:]
+    for c, v in ((0, 0.005), (0, -0.01), (0, -0.005), (2, 0.08), (2, 0.09)):
+        m64.append(np.abs(q[:, c] - v).min())
+    grip = q[:, 2] > 0.08
+    if grip.any():
+        m64.append(np.abs(q[grip, 1]).min())
+
+    def search(target, mask, thr=None):
+        d = np.linalg.norm(q[mask] - target, axis=1)
+        if len(d) == 0:
+            return None
+        m64.append(_gap(d))
+        if thr is not None:
+            m64.append(abs(d.min() - thr))
+        return q[mask][d.argmin()], d.min()
+
+    def gripper():
+        for side, y in ((q[:, 1] > 0, 0.01), (q[:, 1] < 0, -0.01)):
+            if (grip & side).any():
+                search(np.array([0, y, q[grip & side, 2].max()]), grip & side)
+
+    kp = np.array([[0.02, 0.09, 0], [0.02, -0.09, 0], [0.014, 0.095, 0.07], [0.014, -0.095, 0.07]])
+    back = kp + [[-0.042, 0, 0], [-0.042, 0, 0], [-0.028, 0, 0], [-0.028, 0, 0]]
+    for s, dx in enumerate((-0.04, -0.04, -0.03, -0.03)):  # get_key_points
+        r = search(kp[s], q[:, 0] > 0.005, 0.018)
+        if r is not None and r[1] < 0.018:
+            back[s] = r[0] + [dx, 0, 0]
+    for s in range(4):
+        search(back[s], q[:, 0] < -0.01, 0.018)
+    gripper()
+    sel = (q[:, 0] > -0.005) & (q[:, 2] < 0.09)  # get_6_key_points
+    kp6 = kp.copy()
+    kp6[1] = [0.01, -0.1, 0]
+    for s, corner in enumerate(([0.24, 0.32, -0.2], [0.24, -0.32, -0.2], [0.24, 0.32, 0.2], [0.24, -0.32, 0.2])):
+        r = search(np.array(corner), sel)
+        if r is not None:
+            m64.append(abs(np.linalg.norm(kp6[s] - r[0]) - 0.03))
+    # cross-section: the first count + 1 distances decide the result
+    moved = np.array(crop, copy=True)
+    moved -= pose[:3]
+    ql = (R.T @ moved.reshape((-1, 3, 1))).reshape((-1, 3))
+    d = np.sort(T.compute_dists_to_line(ql, np.array([0.05, 0, 0]), np.array([-0.05, 0, 0])))[:cs_count + 1]
+    mT += [np.diff(d).min() if len(d) > 1 else np.inf, np.abs(d - cs_cutoff).min()]
+    for kp_idx in kp_idx_sets:  # collect_closest_points
+        real = kp_idx[kp_idx > -1]
+        if len(real):
+            n = np.linalg.norm(crop[real].reshape(-1, 1, 3) - crop, axis=2)
+            mT.append(np.abs(n.astype(np.float64) - float(crop.dtype.type(radius))).min())
+    return float(min(m64)), float(min(mT))
+
+
+def gen_labels(rng):
+    """utils/data.py get_ee_idx, get_ee_cross_section_idx, get_key_points, get_6_key_points and collect_closest_points
+    (with load_key_points' label write, data/alivev2.py:227-236) on a synthetic gripper (tests/label_helpers.py
+    gripper_cloud): body sizes 50 (12 rod points: fewer cross-section candidates than count), 400 and 3000 (60 rod points:
+    more) as float32, and the 400 case again as float64; float64 pose, w first.  The crop points[ee_idx] feeds the other
+    four functions.  utils/transformation.py's three line functions on a handful of float64 points.
+    A case is written only when every decision in it clears its tipping point: arg-min gaps, mask and threshold
+    comparisons by more than 1e-9 (1e-6 for what the reference computes in float32: collect_closest_points and the
+    cross-section of float32 points), the deciding cross-section distances pairwise distinct by the same amount;
+    otherwise the case is drawn again from the next seed."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    from label_helpers import gripper_cloud
+
+    count, cutoff, radius, ignore = 32, 0.004, 0.006, -100
+    out = dict(count=np.int64(count), cutoff=np.float64(cutoff), radius=np.float64(radius), ignore_label=np.int64(ignore))
+    had_int = hasattr(np, "int")
+    np.int = int  # get_6_key_points:273 uses the alias numpy removed
+    try:
+        cases, seed = [(50, 12, np.float32), (400, 60, np.float32), (3000, 60, np.float32), (400, 60, np.float64)], 7000
+        for ci, (n_body, n_rod, dtype) in enumerate(cases):
+            while True:
+                seed += 1
+                if ci == 3:  # the float64 copy of case 1
+                    points, pose = out["c1_points"].astype(np.float64), out["c1_pose"]
+                else:
+                    points, pose, _ = gripper_cloud(np.random.default_rng(seed), n_body, n_rod)
+                try:
+                    ee = Dat.get_ee_idx(points, pose, switch_w=False)
+                    crop = points[ee]
+                    cs_d, cs_i = Dat.get_ee_cross_section_idx(crop, pose, count=count, cutoff=cutoff, switch_w=False)
+                    kp10, kp10_idx = Dat.get_key_points(crop, pose, switch_w=False, ignore_label=ignore)
+                    kp6, kp6_idx = Dat.get_6_key_points(crop, pose, switch_w=False, ignore_label=ignore)
+                except TypeError:  # get_key_points on an empty front side
+                    assert ci != 3
+                    continue
+                m64, mT = _label_margins(points, crop, pose, count, cutoff, radius, (kp10_idx, kp6_idx))
+                ok = m64 > 1e-9 and mT > (1e-6 if dtype == np.float32 else 1e-9)
+                print(f"labels case {ci} seed {seed}: crop {len(crop)}, cross-section {len(cs_i)}, margins {m64:.2e} / "
+                      f"{mT:.2e} -> {'kept' if ok else 'drawn again'}")
+                if ok:
+                    break
+                assert ci != 3, "the float64 copy fails the margin condition: pick another seed range"
+            rec = dict(points=points, pose=pose, ee_idx=ee.astype(np.int64), cs_dists=cs_d, cs_idx=cs_i.astype(np.int64),
+                       kp10=kp10, kp10_idx=kp10_idx.astype(np.int64), kp6=kp6, kp6_idx=kp6_idx.astype(np.int64))
+            for name, kidx in (("10", kp10_idx), ("6", kp6_idx)):
+                real = kidx > -1
+                pcls, pidx = Dat.collect_closest_points(kidx[real], crop, euclidean_threshold=radius)
+                labels = np.zeros(len(crop), dtype=np.int64) + ignore
+                labels[pidx] = np.arange(len(kidx), dtype=np.int64)[real][pcls]
+                rec.update({f"pcls{name}": pcls.astype(np.int64), f"pidx{name}": pidx.astype(np.int64),
+                            f"labels{name}": labels})
+            out.update({f"c{ci}_{k}": v for k, v in rec.items()})
+        out["n_cases"] = np.int64(len(cases))
+    finally:
+        if not had_int:
+            del np.int
+    lp1, lp2 = rng.uniform(-0.1, 0.1, 3), rng.uniform(-0.1, 0.1, 3)
+    pts = rng.uniform(-0.1, 0.1, (12, 3))
+    d_sorted = np.sort(T.compute_dists_to_line(pts, lp2, lp1))
+    line_cutoff = float((d_sorted[2] + d_sorted[3]) / 2)  # cuts inside the first `count`
+    sel_d, sel_i = T.select_closest_points_to_line(pts, lp1, lp2, count=5, cutoff=line_cutoff)
+    all_d, all_i = T.select_closest_points_to_line(pts, lp1, lp2, cutoff=1.0)  # count 0: every point
+    out.update(line_lp1=lp1, line_lp2=lp2, line_points=pts, line_cutoff=np.float64(line_cutoff), line_dists=T.compute_dists_to_line(pts, lp1, lp2),
+               line_vec_dist=np.float64(T.compute_vec_dist_to_line(pts[0], lp1, lp2)), line_sel_dists=sel_d,
+               line_sel_idx=sel_i.astype(np.int64), line_all_dists=all_d, line_all_idx=all_i.astype(np.int64))
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
@@ -601,7 +736,8 @@ def main():
                            ("preprocess", gen_preprocess, 105), ("metrics", gen_metrics, 106),
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
                            ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110),
-                           ("pose_losses", gen_pose_losses, 111), ("augmentation", gen_augmentation, 112)]:
+                           ("pose_losses", gen_pose_losses, 111), ("augmentation", gen_augmentation, 112),
+                           ("labels", gen_labels, 113)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))

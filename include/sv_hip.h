@@ -67,7 +67,7 @@ const char* sv_last_error(void);
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
  *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
- *    entries of N6 */
+ *    entries of N6, the segmentation criterion and step metrics of N7 */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -654,7 +654,52 @@ int sv_radius_labels(const void* points, int points_f64, const int32_t* offsets,
                      int K, double euclidean_threshold, int64_t ignore_label, int64_t* labels, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * A8  PointNet++ sampling / grouping / set abstraction  (replace model/pointnet2_utils.py:65-86 farthest_point_sample,
+ * N7  segmentation criterion and step metrics (replace nn.CrossEntropyLoss(ignore_index, reduction) on out.features of
+ *      train_segmentation.py / train_vote.py / train_key_points.py, compute_accuracies of train_segmentation.py:34-46 and
+ *      train_vote.py:35-45, and the per-frame vote sort of compute_center_dists, train_vote.py:48-65).  Additions of ABI 4.
+ *
+ * Common arguments: B frames, frame b owning the consecutive rows offsets[b] .. offsets[b+1]-1 (int32[B+1] on the
+ *   device, non-decreasing).  B in [1, SV_MAX_BATCH], N in [0, 2^31); N = 0 is valid.  Both entries validate on the host
+ *   before any HIP call (a workspace below *_workspace_bytes is one of the argument errors, SV_ERR_INVALID), launch on the
+ *   stream and never wait or read back; the same arguments give the same bits.
+ *
+ * sv_seg_criterion: one pass over logits float32[N][ld] (columns 0 .. C-1, 1 <= C <= 32 - the limit of
+ *   sv_key_point_predictions -, ld >= C) and labels int64[N].
+ *   Row loss  lse(x) - x[y],  lse = m + log(sum_c exp(x_c - m)),  m = the row maximum, everything in float64 from the
+ *   float32 logits.  A row with a NaN logit gives NaN, and so does a row that holds +inf (inf - inf), both as torch's
+ *   log-softmax.
+ *   sums float64[2] = (sum of the row losses over the counted rows, number of counted rows).  The sum is taken in float64
+ *   in an order that depends on (N, B, C) only, never on scheduling; no floating-point atomics.  The reduction ("mean":
+ *   sums[0] / sums[1], 0 / 0 = NaN as torch; "sum": sums[0]) is the caller's.
+ *   grad float32[N][C] dense (may be NULL): the UNSCALED softmax(x) - onehot(y) of a counted row (the label's column as
+ *   -(sum of the other columns' exp) / sum, which does not cancel), 0 for an ignored row; the caller's backward multiplies
+ *   by the reduction's factor and the incoming gradient, so the kernel needs no second pass to learn the count.
+ *   pred = torch's max(1), the rule of sv_slice_argmax: the first index among equal maxima; the first NaN of a row is its
+ *   maximum.  confusion int64[B][C][C] (may be NULL): [b][gt][pred] over the counted rows of frame b.
+ *   label == ignore_index: the row is not counted, its gradient row is 0, it adds one to n_rows_ignored[b] (int64[B], may
+ *   be NULL) and appears in no confusion cell.
+ *   Any other label outside [0, C): the row is not counted, its gradient row is NaN and n_invalid[0] (int32) goes up by
+ *   one; nothing faults (torch device-asserts here).  A caller turns n_invalid != 0 into a NaN loss.
+ *   Rows before offsets[0] or at or after offsets[B] count for sums and grad but belong to no frame.
+ *   Integer counts use LDS and global integer atomics (integer addition is order-free).
+ *   workspace: sv_seg_criterion_workspace_bytes(N, B, C).
+ *
+ * sv_segment_topk: the per-frame form of sv_topk_indices on x[i * ld], i < N: idx int64[B][k] = row within the frame of
+ *   its j-th largest x, padded with -1 when the frame has fewer than k rows (an empty frame: all -1).  sv_topk_indices'
+ *   order: ties go to the lower row, NaN sorts above +inf; frame by frame the result equals sv_topk_indices on that frame's
+ *   rows alone.  1 <= k <= 64, ld >= 1; offsets outside [0, N] are clamped so that no access leaves x.
+ *   workspace: sv_segment_topk_workspace_bytes(N, B, k) (k keys per frame and 4096-row chunk of x).
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_seg_criterion_workspace_bytes(int64_t N, int B, int C);
+int sv_seg_criterion(const float* logits, int64_t ld, int C, int64_t N, const int64_t* labels, int64_t ignore_index,
+                     const int32_t* offsets, int B, void* workspace, size_t workspace_bytes, double* sums, float* grad,
+                     int64_t* confusion, int64_t* n_rows_ignored, int32_t* n_invalid, sv_stream_t stream);
+size_t sv_segment_topk_workspace_bytes(int64_t N, int B, int k);
+int sv_segment_topk(const float* x, int64_t ld, int64_t N, const int32_t* offsets, int B, int k, void* workspace,
+                    size_t workspace_bytes, int64_t* idx, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * A8  PointNet++ sampling / grouping / set abstraction (replace model/pointnet2_utils.py:65-86 farthest_point_sample,
  *      :89-109 query_ball_point, :178-204 the set abstraction's shared MLP + max, utils/data.py:13-34 numpy FPS)
  * ------------------------------------------------------------------------------------------- */
 /* xyz float32[B][N][3]; start int64[B] first centroid (the reference draws it at random: pass it in);

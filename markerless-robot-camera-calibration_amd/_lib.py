@@ -125,6 +125,10 @@ SIGNATURES = {
     "sv_line_topk_workspace_bytes": (c_size_t, [c_int64]),
     "sv_line_topk": (c_int, [_P, c_int, _P, c_int64, c_int, _P, _P, _P, _P, c_int, c_double, _P, c_size_t, _P, _P, _P, _P]),
     "sv_radius_labels": (c_int, [_P, c_int, _P, c_int64, c_int, _P, c_int, c_double, c_int64, _P, _P]),
+    "sv_seg_criterion_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "sv_seg_criterion": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P, _P]),
+    "sv_segment_topk_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "sv_segment_topk": (c_int, [_P, c_int64, c_int64, _P, c_int, c_int, _P, c_size_t, _P, _P]),
     "sv_fps": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_interpolate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "sv_cluster_workspace_bytes": (c_size_t, [c_int64]),

@@ -115,6 +115,14 @@ __device__ __forceinline__ int hash_find(const uint64_t* __restrict__ tkeys, con
   }
 }
 
+// Packed top-k key of sv_topk_indices / sv_segment_topk: order-preserving value bits << 32 | ~index, so the largest key is
+// the largest value at the lowest index and keys of distinct indices are distinct.
+__device__ __forceinline__ unsigned long long topk_key(float v, unsigned idx) {
+  unsigned u = __float_as_uint(v);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - idx);
+}
+
 // Order-preserving stream compaction of head flags (ballot + popcount prefix, no atomics):
 //  compact_count  : per-block number of set flags
 //  compact_offsets: exclusive scan of the block counts (single block) and total

@@ -266,11 +266,7 @@ __global__ void kp_finalize_kernel(const unsigned long long* __restrict__ best, 
 //      the largest value at the lowest index, keys are distinct, so the j-th selection is "the largest key below the
 //      (j-1)-th" - no masking, no sort.  Stage 1: every block of 256 threads selects the k largest of its chunk; stage 2: one
 //      block selects the k largest of the blocks' candidates.  NaN orders above +inf (torch.sort places NaN first).
-__device__ __forceinline__ unsigned long long topk_key(float v, unsigned idx) {
-  unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - idx);
-}
+//      topk_key is in sv_common.h (sv_segment_topk shares it).
 
 constexpr int TOPK_CHUNK = 8192;  // values per stage-1 block
 template <bool KEYS_IN>

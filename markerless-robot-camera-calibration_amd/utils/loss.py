@@ -6,6 +6,10 @@ pose_match, kp_pose_match; :166-249), which the reference computes in a Python l
 sv_pose_match_loss call for the whole batch: loss and gradient from the same float64 pass (include/sv_hip.h N4).  The
 quaternion -> matrix step stays in torch, so autograd carries its Jacobian and non-unit quaternions behave as in the
 reference.  No criterion waits on the device.
+
+SegmentationCriterion is the criterion of the segmentation, vote and key-point trainers
+(nn.CrossEntropyLoss(ignore_index, reduction) on out.features) as one sv_seg_criterion call that also yields the step's
+per-frame confusion counts (StepMetrics; include/sv_hip.h N7).
 """
 from ctypes import c_int, c_int64, c_size_t
 from enum import Enum
@@ -309,3 +313,145 @@ def get_criterion(device="cuda", loss_type=LossType.ANGLE, reduction="mean"):
     if loss_type == LossType.KP_POSE_MATCH:
         return _point_matching("kp_pose_match", _lib.SV_LOSS_KP_POSE_MATCH, True, _kp_rows_of)
     return compute_loss
+
+
+# ---- segmentation criterion and step metrics (train_segmentation.py / train_vote.py / train_key_points.py) -----------
+
+def _seg_logits(logits):
+    """float32 CUDA [N, C] with unit column stride; the row stride goes to the kernel as ld"""
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError(f"logits must be a [N, C] tensor, got {type(logits).__name__}"
+                         f"{tuple(logits.shape) if torch.is_tensor(logits) else ''}")
+    _lib.require_cuda(logits, "logits")
+    x = logits.detach()
+    N, C = x.shape
+    if x.dtype != torch.float32 or (C > 1 and x.stride(1) != 1) or (N > 1 and x.stride(0) < C):
+        x = x.to(torch.float32).contiguous()
+    return x, (x.stride(0) if N > 1 and x.stride(0) >= C else C)
+
+
+def _seg_labels(labels, N):
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != N:
+        raise ValueError(f"labels must be a [{N}] tensor, one entry per row of logits")
+    _lib.require_cuda(labels, "labels")
+    if labels.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"labels must be int64 or int32, got {labels.dtype}")
+    return labels.to(torch.int64).contiguous()
+
+
+def _seg_offsets(offsets, N, device):
+    """int32 CUDA [B + 1] row offsets from: None (one frame), an int32 device tensor, a host sequence of B + 1 offsets,
+    or the `others` list of dicts with "offset" = (first row, end row) that the reference's collate yields"""
+    if offsets is None:
+        return _pinned_offsets([N], device)
+    if torch.is_tensor(offsets) and offsets.is_cuda:
+        if offsets.dim() != 1 or offsets.shape[0] < 2 or offsets.dtype not in (torch.int32, torch.int64):
+            raise ValueError("offsets on the device must be an integer tensor of B + 1 >= 2 entries")
+        return offsets.to(torch.int32).contiguous()
+    if len(offsets) and isinstance(offsets[0], dict):
+        seq = [int(oi["offset"][0]) for oi in offsets] + [int(offsets[-1]["offset"][1])]
+    else:
+        seq = [int(v) for v in offsets]
+    if len(seq) < 2 or seq[0] != 0 or seq[-1] != N or any(b < a for a, b in zip(seq, seq[1:])):
+        raise ValueError(f"offsets must rise from 0 to N = {N} over B + 1 >= 2 entries, got {seq}")
+    if len(seq) - 1 > _lib.SV_MAX_BATCH:
+        raise ValueError(f"{len(seq) - 1} frames: at most {_lib.SV_MAX_BATCH}")
+    return _pinned_offsets(np.diff(seq), device)
+
+
+class StepMetrics:
+    """Per-frame counts of one criterion call, device tensors only: confusion int64 [B, C, C] ([b][gt][pred] over the
+    counted rows), rows int64 [B] (frame lengths), ignored int64 [B], invalid int32 [1] (labels that are neither the ignore
+    index nor a class)."""
+
+    def __init__(self, confusion, rows, ignored, invalid):
+        self.confusion, self.rows, self.ignored, self.invalid = confusion, rows, ignored, invalid
+
+    def accuracies(self):
+        """float64 [B]: trace / rows, the reference's compute_accuracies (ignored rows count as wrong); NaN for an empty
+        frame, where the reference raises ZeroDivisionError"""
+        trace = self.confusion.diagonal(dim1=1, dim2=2).sum(1)
+        return trace.to(torch.float64) / self.rows.to(torch.float64)
+
+    def to_host(self):
+        """the one read-back: dict of numpy arrays (confusion, rows, ignored, invalid, accuracies)"""
+        B, C, _ = self.confusion.shape
+        flat = torch.cat([self.confusion.reshape(-1), self.rows, self.ignored, self.invalid.to(torch.int64)]).cpu().numpy()
+        confusion = flat[:B * C * C].reshape(B, C, C)
+        rows = flat[B * C * C:B * C * C + B]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            acc = np.trace(confusion, axis1=1, axis2=2).astype(np.float64) / rows.astype(np.float64)
+        return {"confusion": confusion, "rows": rows, "ignored": flat[B * C * C + B:B * C * C + 2 * B],
+                "invalid": int(flat[-1]), "accuracies": acc}
+
+
+def seg_criterion_call(logits, labels, offsets=None, ignore_index=-100, want_grad=True, want_metrics=True):
+    """One sv_seg_criterion call: (sums float64 [2], grad float32 [N, C] or None, StepMetrics; its confusion and ignored are
+    None without want_metrics).  No host wait."""
+    x, ld = _seg_logits(logits)
+    N, C = x.shape
+    y = _seg_labels(labels, N)
+    off = _seg_offsets(offsets, N, x.device)
+    B = off.shape[0] - 1
+    dev = x.device
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    grad = torch.empty((N, C), dtype=torch.float32, device=dev) if want_grad else None
+    ncell = B * C * C if want_metrics else 0
+    counts = torch.empty(ncell + (B if want_metrics else 0) + 1, dtype=torch.int64, device=dev)
+    confusion = counts[:ncell].view(B, C, C) if want_metrics else None
+    ignored = counts[ncell:ncell + B] if want_metrics else None
+    invalid = counts[-1:].view(torch.int32)[:1]
+    nbytes = _lib.load().sv_seg_criterion_workspace_bytes(N, B, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("sv_seg_criterion", ptr(x), c_int64(ld), c_int(C), c_int64(N), ptr(y), c_int64(ignore_index), ptr(off), c_int(B),
+         ptr(ws), c_size_t(nbytes), ptr(sums), ptr(grad), ptr(confusion), ptr(ignored), ptr(invalid), stream_ptr())
+    rows = (off[1:] - off[:-1]).to(torch.int64) if want_metrics else None
+    return sums, grad, StepMetrics(confusion, rows, ignored, invalid)
+
+
+class SegmentationLossFunction(torch.autograd.Function):
+    """loss = sum or mean over the counted rows of lse(x) - x[y].  The call also writes the unscaled d loss / d logits
+    (softmax - onehot), which the backward multiplies by the reduction's factor and the incoming gradient; the integer
+    outputs carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, offsets, ignore_index, mean, want_metrics):
+        sums, grad, m = seg_criterion_call(logits, labels, offsets, ignore_index, ctx.needs_input_grad[0], want_metrics)
+        loss = sums[0] / sums[1] if mean else sums[0]  # 0 / 0: NaN, as torch's mean over no row
+        loss = torch.where(m.invalid[0] != 0, torch.full_like(loss, float("nan")), loss).to(torch.float32)
+        ctx.scale = 1.0 / sums[1].clamp(min=1.0) if mean else None  # no counted row: the gradient rows stay 0 (or NaN)
+        ctx.in_dtype = logits.dtype
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        outs = (loss, m.invalid) + ((m.confusion, m.rows, m.ignored) if want_metrics else ())
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss, *_):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        (grad,) = ctx.saved_tensors
+        factor = dloss if ctx.scale is None else dloss.to(torch.float64) * ctx.scale
+        return ((grad * factor.to(torch.float32)).to(ctx.in_dtype),) + (None,) * 5
+
+
+class SegmentationCriterion(nn.Module):
+    """nn.CrossEntropyLoss(ignore_index=..., reduction=...) on [N, C] logits as one sv_seg_criterion call (include/sv_hip.h
+    N7): loss, gradient and the per-frame confusion counts from one float64 pass, no host wait.
+    forward(logits, labels) -> loss (0-dim float32); forward(logits, labels, offsets=..., return_metrics=True) ->
+    (loss, StepMetrics)."""
+
+    def __init__(self, ignore_index=-100, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"reduction {reduction!r}: 'mean' or 'sum' (the trainers call .item() on the loss)")
+        self.ignore_index, self.reduction = int(ignore_index), reduction
+
+    def forward(self, logits, labels, offsets=None, return_metrics=False):
+        out = SegmentationLossFunction.apply(logits, labels, offsets, self.ignore_index, self.reduction == "mean",
+                                             bool(return_metrics))
+        if not return_metrics:
+            return out[0]
+        return out[0], StepMetrics(out[2], out[3], out[4], out[1])

@@ -11,7 +11,7 @@ from ctypes import c_int
 import numpy as np
 import torch
 
-from .._lib import call, ptr, stream_ptr
+from .._lib import call, ptr, require_cuda, stream_ptr
 
 
 def compute_ADD_batched(points, P, gt_pose, pred_pose, device=None):
@@ -158,3 +158,53 @@ def compute_segmentation_metrics(gt, pred, classes=("background", "arm", "ee")):
     results["recall"] = float(np.mean(recalls))
     results["miou"] = float(np.mean(ious)) if ious else float("nan")
     return results
+
+
+def _logit_rows(out):
+    """[N, C] logits of a SparseTensor (train_segmentation.py passes `out`) or of a tensor (train_vote.py: out.features)"""
+    return out if torch.is_tensor(out) else out.F
+
+
+def compute_accuracies(out, labels, others, ignore_index=None):
+    """train_segmentation.py:34-46 / train_vote.py:35-45: per frame, rows whose arg-max equals the label over the frame's
+    length (ignored rows count as wrong), as a list of B Python floats.  One sv_seg_criterion call and ONE read-back for
+    the batch, where the reference takes the arg-max of all N rows once per frame and leaves the device once per frame.
+    `others`: the collate's list of dicts with "offset", a host sequence of B + 1 offsets or an int32 device tensor.  An
+    empty frame gives NaN (the reference raises ZeroDivisionError)."""
+    from .config import Config
+    from .loss import seg_criterion_call
+
+    if ignore_index is None:
+        ignore_index = Config().DATA.ignore_label
+    _, _, m = seg_criterion_call(_logit_rows(out), labels, others, ignore_index, want_grad=False)
+    return [float(a) for a in m.to_host()["accuracies"]]
+
+
+def segmentation_metrics_batch(confusion):
+    """segmentation_metrics_from_confusion per frame and for the sum over frames, from the [B, C, C] counts of a
+    StepMetrics (device tensor: one read-back; numpy is taken as it is): {"frames": [B dicts], "total": dict}."""
+    cm = confusion.cpu().numpy() if torch.is_tensor(confusion) else np.asarray(confusion)
+    if cm.ndim != 3 or cm.shape[1] != cm.shape[2]:
+        raise ValueError(f"confusion must be [B, C, C], got {cm.shape}")
+    return {"frames": [segmentation_metrics_from_confusion(c) for c in cm],
+            "total": segmentation_metrics_from_confusion(cm.sum(axis=0))}
+
+
+def compute_center_dists_batch(out, labels, coords, poses, offsets, quantization_size, ee_r=0.03):
+    """train_vote.py:48-65 for the whole batch without a host wait: (dist float32 [B], valid bool [B]).  dist[b] = distance
+    between get_pred_centers_batch's centre of frame b (moved by the frame's quaternion poses[b, 3:7]) and poses[b, :3], in
+    float64 and rounded once; valid[b] = the frame has a row with label 1 (the reference's `continue` otherwise: its list
+    holds dist[valid])."""
+    from .loss import _seg_offsets
+    from .output import _pred_centers_f64
+
+    logits = require_cuda(_logit_rows(out), "out")
+    off = _seg_offsets(offsets, logits.shape[0], logits.device)
+    poses = torch.as_tensor(poses).to(logits.device)
+    centers = _pred_centers_f64(logits, coords, off, quantization_size, ee_r, poses[:, 3:7])
+    d = centers - poses[:, :3].to(torch.float64)
+    dist = torch.sqrt((d * d).sum(1)).to(torch.float32)
+    ones = torch.cat([torch.zeros(1, dtype=torch.int64, device=logits.device), (labels == 1).cumsum(0)])
+    idx = off.to(torch.int64)
+    valid = (ones[idx[1:]] - ones[idx[:-1]]) > 0
+    return dist, valid

@@ -166,3 +166,58 @@ class ClusterUtil:
         # scipy numbers components by their first member, so the first maximum is the cluster with the lowest index
         unique, counts = np.unique(labels, return_counts=True)
         return np.where(labels == unique[counts.argmax()])[0]
+
+
+def segment_topk_indices(column, offsets, k):
+    """per frame the rows (within the frame) of the k largest entries of a float32 CUDA column (any stride), largest
+    first, ties to the lower row, NaN above +inf: int64 CUDA [B, k], -1 where the frame has fewer than k rows
+    (sv_segment_topk; frame by frame topk_indices on the frame's slice).  offsets: int32 CUDA [B + 1]."""
+    from ctypes import c_int, c_int64, c_size_t
+
+    from .._lib import call, load, ptr, require_cuda, stream_ptr
+
+    x = require_cuda(column, "column").detach()
+    if x.dim() != 1:
+        raise ValueError(f"column must be one-dimensional, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        x = x.to(torch.float32)
+    off = require_cuda(offsets, "offsets")
+    if off.dtype != torch.int32 or off.dim() != 1 or off.shape[0] < 2:
+        raise ValueError("offsets must be an int32 tensor of B + 1 >= 2 entries")
+    off = off.contiguous()
+    n, B = x.shape[0], off.shape[0] - 1
+    nbytes = load().sv_segment_topk_workspace_bytes(c_int64(n), c_int(B), c_int(k))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    idx = torch.empty((B, k), dtype=torch.int64, device=x.device)
+    call("sv_segment_topk", ptr(x), c_int64(x.stride(0) if n > 1 and x.stride(0) >= 1 else 1), c_int64(n), ptr(off), c_int(B),
+         c_int(k), ptr(ws), c_size_t(nbytes), ptr(idx), stream_ptr())
+    return idx
+
+
+def _pred_centers_f64(out, coords, offsets, quantization_size, ee_r, q):
+    """float64 [B, 3] centres of get_pred_centers_batch before the one rounding"""
+    from .._lib import require_cuda
+    from .transformation import get_quaternion_rotation_matrix_torch
+
+    require_cuda(out, "out")
+    coords = require_cuda(torch.as_tensor(coords) if not torch.is_tensor(coords) else coords, "coords")
+    sel = segment_topk_indices(out[:, 1], offsets, 8)  # [B, 8], -1 padded
+    live = sel >= 0
+    rows = (offsets[:-1].to(torch.int64).unsqueeze(1) + sel.clamp(min=0)).clamp(max=coords.shape[0] - 1)  # padding: masked
+    if coords.shape[0] == 0:  # nothing to gather: every frame is empty
+        return torch.full((sel.shape[0], 3), float("nan"), dtype=torch.float64, device=out.device)
+    xyz = coords[:, 1:][rows].to(torch.float64) * quantization_size  # [B, 8, 3]
+    centers = (xyz * live.unsqueeze(2)).sum(1) / live.sum(1, keepdim=True)  # no row: 0 / 0 = NaN
+    if q is not None:
+        rot = get_quaternion_rotation_matrix_torch(q.to(device=out.device, dtype=torch.float64))
+        centers = centers + rot[:, :, 0] * (-ee_r)  # R(q) @ (-ee_r, 0, 0)
+    return centers
+
+
+def get_pred_centers_batch(out, coords, offsets, quantization_size, ee_r=0.03, q=None):
+    """get_pred_center (utils/output.py:45-64) for every frame of a batch, on the device and without a host wait:
+    float32 CUDA [B, 3].  Per frame the 8 highest votes out[:, 1] (sv_segment_topk instead of a full sort), the mean of
+    coords[:, 1:] * quantization_size over the selected rows (all of them when the frame has fewer than 8; an empty frame
+    gives NaN) summed in float64, plus R(q[b]) @ (-ee_r, 0, 0) with q [B, 4] (w first).  out: [N, C >= 2] CUDA logits,
+    coords: [N, 4] (batch, x, y, z) CUDA, offsets: int32 CUDA [B + 1]."""
+    return _pred_centers_f64(out, coords, offsets, quantization_size, ee_r, q).to(torch.float32)

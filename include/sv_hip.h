@@ -462,6 +462,44 @@ int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const floa
                        sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3c  batched ICP: P registrations of one source cloud per call, independent or with one shared transform
+ *      (beyond the reference, opt-in; additive, sv_abi_version() stays 4).
+ *
+ *   src float32[S][3], shared by the P problems.  pre double[P][16] (device) or NULL: with pre, the source point of
+ *   problem p is pre_p . m, in float64 with the row expressions of T . x, never rounded to float32; NULL skips the
+ *   multiply.  tgt float32[sum T_p][3]: the P target clouds concatenated; tgt_normals the same layout or NULL.
+ *   NULL tgt_normals = the point-to-point update of N3, otherwise the point-to-plane update of N3b.  tgt_offsets is a
+ *   HOST array int64[P + 1], ascending from 0, every T_p = tgt_offsets[p+1] - tgt_offsets[p] in [1, 2^24); it is
+ *   validated on the host and travels as a kernel argument, so the call never waits for the device.
+ *   P in [1, 64]; S, max_distance, max_iterations as N3.
+ *
+ *   shared == 0: P independent problems.  init_T double[P][16] (device) or NULL = identities; out_T double[P][16];
+ *   out_stats double[P][3] = {fitness, rmse, updates} (or NULL).  Every problem has its own state and stops on its own;
+ *   problem p's out_T and out_stats are, bit for bit, those of sv_icp_point2point / sv_icp_point2plane on
+ *   (src, target p, init_T[p]) - the kernels share the single calls' device functions - whatever else is in the call
+ *   and whatever its order.
+ *
+ *   shared == 1: one transform T for all problems, minimising the pooled objective.  init_T double[16] or NULL; out_T
+ *   double[16]; out_stats double[3 + 2 P] = pooled {fitness, rmse, updates}, then {fitness_p, rmse_p} of the last
+ *   evaluation of every problem.  Each problem's sums (N3: n, sum p, sum q, sum p q^T, sum d^2; N3b: inliers,
+ *   contributing inliers, sum d^2, A, b) are formed exactly as the single call forms them; the pooled sums are problem
+ *   0's with problems 1 .. P-1 added in ascending order (no float atomics: repeated runs give the same bits, and P = 1
+ *   without pre is the single call bit for bit).  Pooled fitness = sum_p inliers_p / (P S), pooled rmse =
+ *   sqrt(sum d^2 / sum inliers); the stop rule and the no-update conditions (fewer than 3 inliers; fewer than 6
+ *   contributing inliers; a bad pivot) are the single calls', applied to the pooled values; the update is Kabsch /
+ *   Cholesky on the pooled sums.
+ *
+ *   Nearest-neighbour rule, inlier rule, max_iterations == 0, zero inliers (out_T = init_T bit for bit) and NaN handling
+ *   as N3 / N3b.  Launches per call: 2 + (max_iterations + 1) * 2, or * 3 in shared mode, whatever P is; no read-back.
+ *   workspace: sv_icp_batched_workspace_bytes(S, P).
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_icp_batched_workspace_bytes(int64_t S, int P);
+int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* tgt, const float* tgt_normals,
+                   const int64_t* tgt_offsets, int P, const double* init_T, int shared, double max_distance,
+                   int max_iterations, double rel_fitness, double rel_rmse, void* workspace, size_t workspace_bytes,
+                   double* out_T, double* out_stats, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188
  *      compute_pose_loss, :190-209 compute_shape_match_loss, :211-227 compute_pose_match_loss, :229-249
  *      compute_kp_pose_match_loss; call sites train.py:89,189 and train_kp_to_pose.py:297).  Additions of ABI 4.

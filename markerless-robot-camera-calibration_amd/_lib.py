@@ -113,6 +113,9 @@ SIGNATURES = {
     "sv_icp_point2plane_workspace_bytes": (c_size_t, [c_int64]),
     "sv_icp_point2plane": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_double, c_int, c_double, c_double, _P, c_size_t, _P,
                                    _P, _P]),
+    "sv_icp_batched_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "sv_icp_batched": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int, _P, c_int, c_double, c_int, c_double, c_double, _P,
+                               c_size_t, _P, _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),

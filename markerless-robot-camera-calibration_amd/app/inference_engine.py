@@ -15,6 +15,7 @@ the Kabsch / averaging solves run through libsvhip.  Differences that are delibe
   * predict_translation with q=None: the reference reads an unbound `rot_mat` (F8d); here it raises ValueError.
 """
 import collections
+import dataclasses
 import os
 
 import numpy as np
@@ -61,8 +62,10 @@ ICP_METHODS = ("point2point", "point2plane")
 
 class InferenceEngine:
     def __init__(self, calibration_only=False, device="cuda", allow_random_init=False, seed=1, cad_points=None,
-                 seg_precision=None, icp_method="point2point"):
-        """icp_method: the objective of the ICP refinement when INFERENCE.icp_enabled: "point2point" (the reference's) or
+                 seg_precision=None, icp_method="point2point", icp_batched=False):
+        """icp_batched: refine all poses of a group of frames with ONE sv_icp_batched call (match_icp.many) instead of
+        one call and one read-back per pose; the results are identical.
+        icp_method: the objective of the ICP refinement when INFERENCE.icp_enabled: "point2point" (the reference's) or
         "point2plane" (normals estimated on the crop once per frame, utils/icp.py get_point2plane_matcher).
         seg_precision: "fp32" or "bf16" compute precision of the segmentation network's wide conv / linear layers
         (nn.set_compute_precision; None = INFERENCE.SEGMENTATION.precision when the config has it, else fp32).  The pose
@@ -78,6 +81,8 @@ class InferenceEngine:
         if icp_method not in ICP_METHODS:
             raise ValueError(f"icp_method must be one of {ICP_METHODS}, got {icp_method!r}")
         self.icp_method = icp_method
+        self.icp_batched = bool(icp_batched)
+        self.cad_points = cad_points
         # CAD-to-crop ICP (utils/icp.py): the reference samples its CAD points from app/hand_files/hand_notblender.obj,
         # which does not ship with this build -> the caller supplies the model points
         self.match_icp = None
@@ -646,15 +651,25 @@ class InferenceEngine:
                 _, t, q = next(sol)
                 result.key_points_pose = np.concatenate((t, q))
             result.is_confident = self.check_sanity(data, result)
-            if self.match_icp is not None and self.icp_method == "point2plane":
+            if self.match_icp is None or self.icp_batched:
+                continue
+            if self.icp_method == "point2plane":
                 if result.ee_pose is not None or result.key_points_pose is not None:
                     crop = torch.as_tensor(np.ascontiguousarray(ee_pts, dtype=np.float32)).to(self.device)
                     normals = self.match_icp.crop_normals(crop)  # once per frame, shared by both refinements
                     result.ee_pose = self.match_icp(crop, result.ee_pose, normals)
                     result.key_points_pose = self.match_icp(crop, result.key_points_pose, normals)
-            elif self.match_icp is not None:  # app/inference_engine.py:358-362
+            else:  # app/inference_engine.py:358-362
                 result.ee_pose = self.match_icp(ee_pts, result.ee_pose)
                 result.key_points_pose = self.match_icp(ee_pts, result.key_points_pose)
+        if self.match_icp is not None and self.icp_batched:
+            # the group's up to 2 G refinements in one call; a frame's crop appears twice and is moved (and, for
+            # point-to-plane, given its normals) once
+            crops = [ee_pts for _, _, ee_pts, _, _ in work for _ in range(2)]
+            poses = [pose for result, *_ in work for pose in (result.ee_pose, result.key_points_pose)]
+            refined = iter(self.match_icp.many(crops, poses))
+            for result, *_ in work:
+                result.ee_pose, result.key_points_pose = next(refined), next(refined)
         # ---- solve 2: the base poses' quaternions (get_base2cam_pose -> get_q_from_matrix), all frames at once
         mats = []
         for result, data, *_ in work:
@@ -705,6 +720,31 @@ class InferenceEngine:
         calibration = CalibrationResultDTO(pose_camera_link=calib_util.compute_poses_average(stack))
         calibration.load_from_test_result(raw)
         return calibration
+
+    def refine_calibration(self, calibration, frames, results):
+        """The step calibrate() lacks: ONE registration of the CAD model to the end-effector crops of all usable frames
+        with the camera<-base transform as the single unknown (utils/calibration.py refine_base_pose), started from
+        calibration.pose_camera_link, with the engine's icp_method.  frames / results: the PointCloudDTOs and the
+        ResultDTOs predict() gave for them.  A frame is used when its result is confident, it has an ee2base_pose and
+        its crop (points[segmentation == 2], as _pose_enqueue) holds at least ee_point_counts_threshold points.
+        -> (calibration with the refined pose_camera_link, info); with fewer than 2 usable frames the calibration comes
+        back unchanged and info is {"frames_used": n}."""
+        if self.cad_points is None:
+            raise ValueError("refine_calibration needs the engine's cad_points (the CAD model of the end effector, [P,3])")
+        crops, ee2base = [], []
+        for data, result in zip(frames, results):
+            if not result.is_confident or data.ee2base_pose is None:
+                continue
+            crop = data.points[result.segmentation == 2]
+            if len(crop) >= self._config.INFERENCE.ee_point_counts_threshold:
+                crops.append(crop)
+                ee2base.append(data.ee2base_pose)
+        if len(crops) < 2 or calibration.pose_camera_link is None:
+            return calibration, {"frames_used": len(crops)}
+        pose, info = calib_util.refine_base_pose(self.cad_points, crops, ee2base, calibration.pose_camera_link,
+                                                 method=self.icp_method, device=self.device)
+        info["frames_used"] = len(crops)
+        return dataclasses.replace(calibration, pose_camera_link=pose), info
 
     def _calibrate_individual(self, data, weights=None, confident_count=2):
         result = TestResultDTO(segmentation=None, is_confident=True)

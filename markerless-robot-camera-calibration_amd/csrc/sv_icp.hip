@@ -12,6 +12,13 @@
 // sv_icp_point2plane shares the search, the state record and the loop; only step (2) differs (icp_plane_update_kernel:
 // the 6x6 normal equations of the linearised point-to-plane residual, Cholesky, T <- U T).  The target normals come from
 // sv_estimate_normals (sv_normals.hip) or from the caller.
+//
+// N3c, sv_icp_batched: P problems (one source cloud, P target clouds) per launch - the search on a grid of
+// (ceil(S / 256), P), one update workgroup per problem.  The kernels of the single calls and of the batch are thin
+// wrappers round the same device functions (icp_nn_search, icp_p2p_sums / icp_p2p_step, icp_plane_sums /
+// icp_plane_step), so a problem of an independent batch runs the single call's arithmetic in the single call's order.
+// In shared mode (one transform for all problems) the update workgroups write their totals to the workspace and a
+// one-wave tail kernel adds them in ascending problem order and takes the step on the pooled sums.
 #include "sv_common.h"
 #include "sv_dense_math.h"
 
@@ -27,15 +34,29 @@ struct IcpState {
 
 constexpr int NN_TILE = 1024;
 
-__global__ __launch_bounds__(256) void icp_nn_kernel(const float* __restrict__ src, int S, const float* __restrict__ tgt,
-                                                      int T, const IcpState* __restrict__ st, float max_d2,
-                                                      int32_t* __restrict__ nn, float* __restrict__ d2out) {
-  __shared__ float tile[NN_TILE * 3];
+// source point i of a problem: the model point m, or pre . m in float64 (the row expressions of T . x, never rounded)
+__device__ __forceinline__ void icp_source_point(const float* __restrict__ src, int i, const double* __restrict__ pre,
+                                                 double& x, double& y, double& z) {
+  x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+  if (pre) {
+    const double mx = x, my = y, mz = z;
+    x = pre[0] * mx + pre[1] * my + pre[2] * mz + pre[3];
+    y = pre[4] * mx + pre[5] * my + pre[6] * mz + pre[7];
+    z = pre[8] * mx + pre[9] * my + pre[10] * mz + pre[11];
+  }
+}
+
+// one workgroup of 256 source points against the T target points; tile: NN_TILE * 3 floats of LDS
+__device__ __forceinline__ void icp_nn_search(const float* __restrict__ src, int S, const double* __restrict__ pre,
+                                              const float* __restrict__ tgt, int T, const IcpState* __restrict__ st,
+                                              float max_d2, int32_t* __restrict__ nn, float* __restrict__ d2out,
+                                              float* tile) {
   if (st->converged) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   float px = 0.f, py = 0.f, pz = 0.f;
   if (i < S) {
-    const double x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    double x, y, z;
+    icp_source_point(src, i, pre, x, y, z);
     px = (float)(st->T[0] * x + st->T[1] * y + st->T[2] * z + st->T[3]);
     py = (float)(st->T[4] * x + st->T[5] * y + st->T[6] * z + st->T[7]);
     pz = (float)(st->T[8] * x + st->T[9] * y + st->T[10] * z + st->T[11]);
@@ -65,6 +86,13 @@ __global__ __launch_bounds__(256) void icp_nn_kernel(const float* __restrict__ s
   }
 }
 
+__global__ __launch_bounds__(256) void icp_nn_kernel(const float* __restrict__ src, int S, const float* __restrict__ tgt,
+                                                      int T, const IcpState* __restrict__ st, float max_d2,
+                                                      int32_t* __restrict__ nn, float* __restrict__ d2out) {
+  __shared__ float tile[NN_TILE * 3];
+  icp_nn_search(src, S, nullptr, tgt, T, st, max_d2, nn, d2out, tile);
+}
+
 __device__ __forceinline__ double block_sum(double v, double* red) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -77,16 +105,12 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return t;
 }
 
-__global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restrict__ src, int S,
-                                                           const float* __restrict__ tgt,
-                                                           const int32_t* __restrict__ nn,
-                                                           const float* __restrict__ d2, IcpState* __restrict__ st,
-                                                           double rel_fitness, double rel_rmse, int last) {
-  __shared__ double red[16];
-  if (st->converged) return;
-  double Tm[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+constexpr int P2P_ACC = 17;  // n, sp(3), sq(3), spq(9), err
+
+// a problem's inlier sums under Tm, by one workgroup of 1024: tot[P2P_ACC] on every thread
+__device__ __forceinline__ void icp_p2p_sums(const float* __restrict__ src, int S, const double* __restrict__ pre,
+                                             const float* __restrict__ tgt, const int32_t* __restrict__ nn,
+                                             const float* __restrict__ d2, const double* Tm, double* tot, double* red) {
   double acc[16];  // n, sp(3), sq(3), spq(9) -> 16 values
 #pragma unroll
   for (int k = 0; k < 16; ++k) acc[k] = 0.0;
@@ -94,7 +118,8 @@ __global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restric
   for (int i = threadIdx.x; i < S; i += 1024) {
     const int j = nn[i];
     if (j < 0) continue;
-    const double x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    double x, y, z;
+    icp_source_point(src, i, pre, x, y, z);
     const double p[3] = {Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3], Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7],
                          Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11]};
     const double q[3] = {tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2]};
@@ -108,14 +133,17 @@ __global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restric
     }
     err += (double)d2[i];
   }
-  double tot[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) tot[k] = block_sum(acc[k], red);
-  const double e2 = block_sum(err, red);
-  if (threadIdx.x != 0) return;
+  tot[16] = block_sum(err, red);
+}
+
+// one thread: evaluation (fitness = inliers / points), stop rule and Kabsch update from the sums tot[P2P_ACC]
+__device__ __forceinline__ void icp_p2p_step(IcpState* __restrict__ st, const double* Tm, const double* tot,
+                                             double points, double rel_fitness, double rel_rmse, int last) {
   const double n = tot[0];
-  const double fitness = n / (double)S;
-  const double rmse = n > 0 ? sqrt(e2 / n) : 0.0;
+  const double fitness = n / points;
+  const double rmse = n > 0 ? sqrt(tot[16] / n) : 0.0;
   // open3d: stop when both the fitness and the rmse moved by less than the tolerances since the previous evaluation
   const bool stop = (st->iterations > 0 || st->fitness >= 0) &&
                     fabs(st->fitness - fitness) < rel_fitness && fabs(st->rmse - rmse) < rel_rmse;
@@ -151,7 +179,23 @@ __global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restric
   st->iterations += 1;
 }
 
-__global__ void icp_init_kernel(IcpState* st, const double* init_T) {
+__global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restrict__ src, int S,
+                                                           const float* __restrict__ tgt,
+                                                           const int32_t* __restrict__ nn,
+                                                           const float* __restrict__ d2, IcpState* __restrict__ st,
+                                                           double rel_fitness, double rel_rmse, int last) {
+  __shared__ double red[16];
+  if (st->converged) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  double tot[P2P_ACC];
+  icp_p2p_sums(src, S, nullptr, tgt, nn, d2, Tm, tot, red);
+  if (threadIdx.x != 0) return;
+  icp_p2p_step(st, Tm, tot, (double)S, rel_fitness, rel_rmse, last);
+}
+
+__device__ __forceinline__ void icp_init_state(IcpState* st, const double* init_T) {
   if (threadIdx.x < 16) st->T[threadIdx.x] = init_T ? init_T[threadIdx.x] : ((threadIdx.x % 5 == 0) ? 1.0 : 0.0);
   if (threadIdx.x == 0) {
     st->fitness = -1.0;
@@ -160,6 +204,8 @@ __global__ void icp_init_kernel(IcpState* st, const double* init_T) {
     st->converged = 0;
   }
 }
+
+__global__ void icp_init_kernel(IcpState* st, const double* init_T) { icp_init_state(st, init_T); }
 
 __global__ void icp_finish_kernel(const IcpState* st, double* out_T, double* out_stats) {
   if (threadIdx.x < 16) out_T[threadIdx.x] = st->T[threadIdx.x];
@@ -187,16 +233,11 @@ __device__ __forceinline__ void nan_transform(double* T) {
   T[15] = 1.0;
 }
 
-__global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
-    const float* __restrict__ src, int S, const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
-    const int32_t* __restrict__ nn, const float* __restrict__ d2, IcpState* __restrict__ st, double rel_fitness,
-    double rel_rmse, int last) {
-  __shared__ double red[PL_ACC][PL_THREADS / 64];
-  __shared__ double tot[PL_ACC];
-  if (st->converged) return;
-  double Tm[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+// a problem's sums under Tm, by one workgroup of PL_THREADS: tot[PL_ACC] (LDS), valid for every thread on return
+__device__ __forceinline__ void icp_plane_sums(const float* __restrict__ src, int S, const double* __restrict__ pre,
+                                               const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
+                                               const int32_t* __restrict__ nn, const float* __restrict__ d2,
+                                               const double* Tm, double (*red)[PL_THREADS / 64], double* tot) {
   double acc[PL_ACC];
 #pragma unroll
   for (int k = 0; k < PL_ACC; ++k) acc[k] = 0.0;
@@ -207,7 +248,8 @@ __global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
     acc[2] += (double)d2[i];
     const double n[3] = {tgt_normals[j * 3], tgt_normals[j * 3 + 1], tgt_normals[j * 3 + 2]};
     if (!(isfinite(n[0]) && isfinite(n[1]) && isfinite(n[2]))) continue;  // counts as an inlier, adds no equation
-    const double x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    double x, y, z;
+    icp_source_point(src, i, pre, x, y, z);
     const double p[3] = {Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3], Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7],
                          Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11]};
     const double q[3] = {tgt[j * 3], tgt[j * 3 + 1], tgt[j * 3 + 2]};
@@ -237,9 +279,13 @@ __global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
     tot[threadIdx.x] = t;
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
+}
+
+// one thread: evaluation (fitness = inliers / points), stop rule and point-to-plane update from the sums tot[PL_ACC]
+__device__ __forceinline__ void icp_plane_step(IcpState* __restrict__ st, const double* Tm, const double* tot,
+                                               double points, double rel_fitness, double rel_rmse, int last) {
   const double n = tot[0];
-  const double fitness = n / (double)S;
+  const double fitness = n / points;
   const double rmse = n > 0 ? sqrt(tot[2] / n) : 0.0;
   const bool stop = (st->iterations > 0 || st->fitness >= 0) &&
                     fabs(st->fitness - fitness) < rel_fitness && fabs(st->rmse - rmse) < rel_rmse;
@@ -318,6 +364,148 @@ __global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
   st->iterations += 1;
 }
 
+__global__ __launch_bounds__(PL_THREADS) void icp_plane_update_kernel(
+    const float* __restrict__ src, int S, const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
+    const int32_t* __restrict__ nn, const float* __restrict__ d2, IcpState* __restrict__ st, double rel_fitness,
+    double rel_rmse, int last) {
+  __shared__ double red[PL_ACC][PL_THREADS / 64];
+  __shared__ double tot[PL_ACC];
+  if (st->converged) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  icp_plane_sums(src, S, nullptr, tgt, tgt_normals, nn, d2, Tm, red, tot);
+  if (threadIdx.x != 0) return;
+  icp_plane_step(st, Tm, tot, (double)S, rel_fitness, rel_rmse, last);
+}
+
+// ---- N3c: P problems per launch (sv_icp_batched) -------------------------------------------------------------------
+// Problem p = blockIdx.y (search) or blockIdx.x (update): source = src (through pre[p] when given), target rows
+// off.v[p] .. off.v[p + 1] - 1 of tgt, correspondences nn / d2 [p][S], state states[p] - or states[0] in shared mode,
+// where the update workgroups only write their sums to part[p][ICP_PART] and icp_joint_tail_kernel takes the step.
+constexpr int ICP_MAX_PROBLEMS = 64;
+constexpr int ICP_PART = 32;  // doubles per problem in part: P2P_ACC or PL_ACC sums
+
+struct IcpOffsets {
+  int32_t v[ICP_MAX_PROBLEMS + 1];  // a kernel argument: the host array needs no copy and no wait
+};
+
+__global__ __launch_bounds__(256) void icp_batch_nn_kernel(const float* __restrict__ src, int S,
+                                                            const double* __restrict__ pre,
+                                                            const float* __restrict__ tgt, IcpOffsets off,
+                                                            const IcpState* __restrict__ states, int shared,
+                                                            float max_d2, int32_t* __restrict__ nn,
+                                                            float* __restrict__ d2out) {
+  __shared__ float tile[NN_TILE * 3];
+  const int p = blockIdx.y;
+  const int o = off.v[p];
+  icp_nn_search(src, S, pre ? pre + p * 16 : nullptr, tgt + (int64_t)o * 3, off.v[p + 1] - o, states + (shared ? 0 : p),
+                max_d2, nn + (size_t)p * S, d2out + (size_t)p * S, tile);
+}
+
+__global__ __launch_bounds__(1024) void icp_batch_update_kernel(
+    const float* __restrict__ src, int S, const double* __restrict__ pre, const float* __restrict__ tgt, IcpOffsets off,
+    const int32_t* __restrict__ nn, const float* __restrict__ d2, IcpState* __restrict__ states, int shared,
+    double* __restrict__ part, double rel_fitness, double rel_rmse, int last) {
+  __shared__ double red[16];
+  const int p = blockIdx.x;
+  IcpState* st = states + (shared ? 0 : p);
+  if (st->converged) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  double tot[P2P_ACC];
+  icp_p2p_sums(src, S, pre ? pre + p * 16 : nullptr, tgt + (int64_t)off.v[p] * 3, nn + (size_t)p * S, d2 + (size_t)p * S,
+               Tm, tot, red);
+  if (threadIdx.x != 0) return;
+  if (shared) {
+#pragma unroll
+    for (int k = 0; k < P2P_ACC; ++k) part[p * ICP_PART + k] = tot[k];
+    return;
+  }
+  icp_p2p_step(st, Tm, tot, (double)S, rel_fitness, rel_rmse, last);
+}
+
+__global__ __launch_bounds__(PL_THREADS) void icp_batch_plane_update_kernel(
+    const float* __restrict__ src, int S, const double* __restrict__ pre, const float* __restrict__ tgt,
+    const float* __restrict__ tgt_normals, IcpOffsets off, const int32_t* __restrict__ nn, const float* __restrict__ d2,
+    IcpState* __restrict__ states, int shared, double* __restrict__ part, double rel_fitness, double rel_rmse, int last) {
+  __shared__ double red[PL_ACC][PL_THREADS / 64];
+  __shared__ double tot[PL_ACC];
+  const int p = blockIdx.x;
+  IcpState* st = states + (shared ? 0 : p);
+  if (st->converged) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  const int64_t o = (int64_t)off.v[p] * 3;
+  icp_plane_sums(src, S, pre ? pre + p * 16 : nullptr, tgt + o, tgt_normals + o, nn + (size_t)p * S, d2 + (size_t)p * S,
+                 Tm, red, tot);
+  if (shared) {
+    if (threadIdx.x < PL_ACC) part[p * ICP_PART + threadIdx.x] = tot[threadIdx.x];
+    return;
+  }
+  if (threadIdx.x != 0) return;
+  icp_plane_step(st, Tm, tot, (double)S, rel_fitness, rel_rmse, last);
+}
+
+// shared mode, one wave: pooled sums = problem 0's, then problems 1 .. P-1 added in ascending order (one thread per
+// sum); per-problem fitness and rmse of this evaluation -> pstats[p][2]; the single call's step on the pooled sums with
+// P * S points.
+template <bool PLANE>
+__global__ __launch_bounds__(64) void icp_joint_tail_kernel(IcpState* __restrict__ st, const double* __restrict__ part,
+                                                            int P, int S, double* __restrict__ pstats,
+                                                            double rel_fitness, double rel_rmse, int last) {
+  __shared__ double tot[ICP_PART];
+  if (st->converged) return;
+  constexpr int NV = PLANE ? PL_ACC : P2P_ACC;
+  constexpr int ERR = PLANE ? 2 : 16;
+  const int t = threadIdx.x;
+  if (t < NV) {
+    double v = part[t];
+    for (int p = 1; p < P; ++p) v += part[p * ICP_PART + t];
+    tot[t] = v;
+  }
+  if (t < P) {
+    const double n = part[t * ICP_PART];
+    pstats[t * 2] = n / (double)S;
+    pstats[t * 2 + 1] = n > 0 ? sqrt(part[t * ICP_PART + ERR] / n) : 0.0;
+  }
+  __syncthreads();
+  if (t != 0) return;
+  double Tm[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) Tm[k] = st->T[k];
+  const double points = (double)P * (double)S;
+  if (PLANE)
+    icp_plane_step(st, Tm, tot, points, rel_fitness, rel_rmse, last);
+  else
+    icp_p2p_step(st, Tm, tot, points, rel_fitness, rel_rmse, last);
+}
+
+// block b: state b from init_T[b] (identity when null)
+__global__ void icp_batch_init_kernel(IcpState* states, const double* init_T) {
+  icp_init_state(states + blockIdx.x, init_T ? init_T + blockIdx.x * 16 : nullptr);
+}
+
+// independent: block p -> out_T[p], out_stats[p][3]; shared: one block -> out_T, out_stats[3 + 2 P]
+__global__ void icp_batch_finish_kernel(const IcpState* states, const double* pstats, int P, int shared, double* out_T,
+                                        double* out_stats) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const IcpState* st = states + b;
+  if (t < 16) out_T[b * 16 + t] = st->T[t];
+  if (!out_stats) return;
+  if (t == 0) {
+    out_stats[b * 3] = st->fitness;
+    out_stats[b * 3 + 1] = st->rmse;
+    out_stats[b * 3 + 2] = (double)st->iterations;
+  }
+  if (shared && t < P) {
+    out_stats[3 + t * 2] = pstats[t * 2];
+    out_stats[3 + t * 2 + 1] = pstats[t * 2 + 1];
+  }
+}
+
 }  // namespace sv
 
 using namespace sv;
@@ -382,6 +570,69 @@ int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const floa
                        rel_fitness, rel_rmse, it == max_iterations ? 1 : 0);
   }
   hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, stream, st, out_T, out_stats);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
+size_t sv_icp_batched_workspace_bytes(int64_t S, int P) {
+  if (S < 0 || P < 0) return 0;
+  const size_t p = (size_t)P;
+  return align_up(p * sizeof(IcpState), 256) + align_up(p * (size_t)S * 4, 256) * 2 +
+         align_up(p * ICP_PART * sizeof(double), 256) + align_up(p * 2 * sizeof(double), 256) + 1024;
+}
+
+int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* tgt, const float* tgt_normals,
+                   const int64_t* tgt_offsets, int P, const double* init_T, int shared, double max_distance,
+                   int max_iterations, double rel_fitness, double rel_rmse, void* workspace, size_t workspace_bytes,
+                   double* out_T, double* out_stats, sv_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SV_CHECK_ARG(P >= 1 && P <= ICP_MAX_PROBLEMS, "need 1 to 64 problems");
+  SV_CHECK_ARG(S >= 3 && S < (1 << 24), "need 3 to 2^24 - 1 source points");
+  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0 && (shared == 0 || shared == 1), "bad parameters");
+  SV_CHECK_ARG(src && tgt && tgt_offsets && out_T && workspace, "null pointer");
+  SV_CHECK_ARG(tgt_offsets[0] == 0, "tgt_offsets must start at 0");
+  IcpOffsets off;
+  off.v[0] = 0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t T = tgt_offsets[p + 1] - tgt_offsets[p];
+    SV_CHECK_ARG(T >= 1 && T < (1 << 24), "every problem needs 1 to 2^24 - 1 target points (ascending tgt_offsets)");
+    off.v[p + 1] = (int32_t)tgt_offsets[p + 1];  // <= 64 * 2^24
+  }
+  for (int p = P + 1; p <= ICP_MAX_PROBLEMS; ++p) off.v[p] = off.v[P];
+  Workspace ws(workspace, workspace_bytes);
+  IcpState* states = ws.take<IcpState>(P);
+  int32_t* nn = ws.take<int32_t>((size_t)P * S);
+  float* d2 = ws.take<float>((size_t)P * S);
+  double* part = ws.take<double>((size_t)P * ICP_PART);
+  double* pstats = ws.take<double>((size_t)P * 2);
+  if (!ws.ok) {
+    set_error("sv_icp_batched: workspace too small");
+    return SV_ERR_WORKSPACE;
+  }
+  const unsigned nstates = shared ? 1u : (unsigned)P;
+  hipLaunchKernelGGL(icp_batch_init_kernel, dim3(nstates), dim3(64), 0, stream, states, init_T);
+  const float max_d2 = (float)(max_distance * max_distance);
+  const dim3 grid_nn((unsigned)((S + 255) / 256), (unsigned)P);
+  // the single calls' loop; in shared mode a third launch per round takes the step on the pooled sums
+  for (int it = 0; it <= max_iterations; ++it) {
+    const int last = it == max_iterations ? 1 : 0;
+    hipLaunchKernelGGL(icp_batch_nn_kernel, grid_nn, dim3(256), 0, stream, src, (int)S, pre, tgt, off, states, shared,
+                       max_d2, nn, d2);
+    if (tgt_normals)
+      hipLaunchKernelGGL(icp_batch_plane_update_kernel, dim3(P), dim3(PL_THREADS), 0, stream, src, (int)S, pre, tgt,
+                         tgt_normals, off, nn, d2, states, shared, part, rel_fitness, rel_rmse, last);
+    else
+      hipLaunchKernelGGL(icp_batch_update_kernel, dim3(P), dim3(1024), 0, stream, src, (int)S, pre, tgt, off, nn, d2,
+                         states, shared, part, rel_fitness, rel_rmse, last);
+    if (shared && tgt_normals)
+      hipLaunchKernelGGL(icp_joint_tail_kernel<true>, dim3(1), dim3(64), 0, stream, states, part, P, (int)S, pstats,
+                         rel_fitness, rel_rmse, last);
+    else if (shared)
+      hipLaunchKernelGGL(icp_joint_tail_kernel<false>, dim3(1), dim3(64), 0, stream, states, part, P, (int)S, pstats,
+                         rel_fitness, rel_rmse, last);
+  }
+  hipLaunchKernelGGL(icp_batch_finish_kernel, dim3(nstates), dim3(64), 0, stream, states, pstats, P, shared, out_T,
+                     out_stats);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

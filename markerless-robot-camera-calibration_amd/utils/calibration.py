@@ -75,3 +75,37 @@ def compute_poses_average(poses, weights=None):
 def remove_pose_outliers(poses):
     # the reference computes the outlier mask and then returns the input unchanged (utils/calibration.py:55-61)
     return poses
+
+
+def refine_base_pose(cad_points, crops, ee2base_poses, base_pose, method="point2plane", normals=None, icp_threshold=0.1,
+                     max_iterations=30, device="cuda"):
+    """One registration over all frames with the camera<-base transform as the single unknown (utils/icp.py icp_joint,
+    sv_icp_batched in shared mode): frame i sees the CAD model at ee2cam_i = base2cam . ee2base_i
+    (transformation.get_base2cam_matrix), so the source of problem i is get_transformation_matrix(ee2base_poses[i]) .
+    cad_points, its target crops[i], and the shared transform starts at get_transformation_matrix(base_pose).
+    method: "point2point" or "point2plane"; for the latter `normals` holds the crops' normals, or None estimates them
+    per crop (utils/icp.py estimate_normals' defaults).  -> (pose (x, y, z, qw, qx, qy, qz), info) with info = {"fitness",
+    "rmse", "updates" (pooled), "frame_fitness", "frame_rmse" ([len(crops)] arrays)}."""
+    from . import icp as I
+    from .transformation import get_pose_from_matrix, get_transformation_matrix
+
+    if method not in ("point2point", "point2plane"):
+        raise ValueError(f"method must be 'point2point' or 'point2plane', got {method!r}")
+    if len(crops) != len(ee2base_poses) or not crops:
+        raise ValueError(f"need one ee2base pose per crop and at least one crop, got {len(crops)} crops and "
+                         f"{len(ee2base_poses)} poses")
+    if normals is not None and len(normals) != len(crops):
+        raise ValueError(f"normals must hold one array per crop ({len(crops)}), got {len(normals)}")
+    pre = np.stack([get_transformation_matrix(np.asarray(p, dtype=np.float64)) for p in ee2base_poses])
+    init = get_transformation_matrix(np.asarray(base_pose, dtype=np.float64))
+    if method == "point2plane" and normals is None:
+        I._check_batch_shapes(cad_points, crops, None, init, pre, True, icp_threshold, max_iterations)
+        dev = torch.device(device)
+        crops = [I._cloud(c, "crops", dev) for c in crops]
+        normals = [I.estimate_normals(c)[0] for c in crops]
+    T, stats = I.icp_joint(cad_points, crops, init, normals if method == "point2plane" else None, pre, icp_threshold,
+                           max_iterations, device=device)
+    per_frame = stats[3:].reshape(-1, 2)
+    info = {"fitness": float(stats[0]), "rmse": float(stats[1]), "updates": int(stats[2]),
+            "frame_fitness": per_frame[:, 0].copy(), "frame_rmse": per_frame[:, 1].copy()}
+    return get_pose_from_matrix(T), info

@@ -500,6 +500,50 @@ int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* 
                    double* out_T, double* out_stats, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * N3d  the ICP model from a triangle mesh: area-weighted surface samples and weighted sample elimination (the
+ *      reference builds its model at start-up, app/inference_engine.py:56-57 -> utils/icp.py:13-40:
+ *      read_triangle_mesh, sample_points_uniformly(16384), sample_points_poisson_disk(8192, pcl=...), keep x > 0).
+ *      Additive, the ABI version stays 4.  The definitions restate Open3D's algorithm; Open3D draws from its own generator,
+ *      so parity with Open3D binaries is by construction and unverified.  Everything is float64 and every operation
+ *      rounds as written (no fma): a numpy restatement gives the same bits.
+ *
+ *   sv_mesh_sample: verts double[Nv][3], tris int32[F][3], draws double[N][3] = (u, r1, r2) in [0, 1) ->
+ *   points double[N][3], normals double[N][3], tri int32[N], area double[1], counters int32[1].
+ *   Per triangle: e1 = v1 - v0, e2 = v2 - v0, c = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x),
+ *   len = sqrt((cx*cx + cy*cy) + cz*cz), a = 0.5*len.  A triangle with an index outside [0, Nv) has a = 0 and is counted
+ *   in counters[0].  cdf[t] = a[0] + ... + a[t], added in ascending t (np.cumsum's order); area[0] = cdf[F-1].
+ *   Per sample: t = the number of cdf entries <= u*area, clamped to F-1 (searchsorted, side "right": a draw on a boundary
+ *   goes to the next triangle, zero-area triangles are never chosen); q = sqrt(r1), w0 = 1 - q, w1 = q*(1 - r2),
+ *   w2 = q*r2; point = (w0*v0 + w1*v1) + w2*v2 and normal = c / len per component (the geometric normal of the
+ *   triangle; vertex normals are not used); tri[s] = t.  Should the clamp land on a triangle with a bad index, that
+ *   sample's point and normal are NaN.  area not finite or not > 0: tri = -1 and NaN points and normals for every sample.
+ *   F in [1, 2^20], N in [1, 2^20], Nv >= 1; workspace: sv_mesh_sample_workspace_bytes(F).  4 launches, no read-back.
+ *
+ *   sv_sample_eliminate: weighted sample elimination (Yuksel 2015) as Open3D's SamplePointsPoissonDisk runs it.
+ *   points double[N][3] -> kept int32[n_keep] (the survivors, ascending), order int32[N - n_keep] (the deleted indices
+ *   in deletion order; may be NULL when n_keep == N), counters int32[1].
+ *   Neighbours of i: the j != i with d2 = (dx*dx + dy*dy) + dz*dz < r_max*r_max, in ascending j; a NaN distance is no
+ *   neighbour, so a non-finite point has none.  Pair weight: d = max(sqrt(d2), r_min), t = 1 - d/r_max,
+ *   w = ((t*t)^2)^2 (alpha = 8 by three squarings).  weight[i] = the sum of w over the LIVE neighbours of i, added in
+ *   ascending j.  While more than n_keep points live: delete the live point of largest weight (the lowest index on a
+ *   tie), then sum again, from nothing, the weight of each of its live neighbours - so a weight never depends on the
+ *   deletions before it.  counters[0] = the largest true neighbour count; when it exceeds max_degree the table rows
+ *   were cut short, the loop is not run and kept / order are NOT valid: call again with a larger max_degree.
+ *   N in [1, 65536], n_keep in [1, N], max_degree in [1, 1024], r_max finite and > 0, 0 <= r_min <= r_max;
+ *   workspace: sv_sample_eliminate_workspace_bytes(N, max_degree) (the table is N * max_degree * 12 bytes).
+ *   3 launches whatever N - n_keep is (one workgroup runs the whole loop), no read-back; repeated calls give the
+ *   same bits.
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_mesh_sample_workspace_bytes(int64_t F);
+int sv_mesh_sample(const double* verts, int64_t Nv, const int32_t* tris, int64_t F, const double* draws, int64_t N,
+                   void* workspace, size_t workspace_bytes, double* points, double* normals, int32_t* tri,
+                   double* area, int32_t* counters, sv_stream_t stream);
+size_t sv_sample_eliminate_workspace_bytes(int64_t N, int max_degree);
+int sv_sample_eliminate(const double* points, int64_t N, int64_t n_keep, double r_max, double r_min, int max_degree,
+                        void* workspace, size_t workspace_bytes, int32_t* kept, int32_t* order, int32_t* counters,
+                        sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188
  *      compute_pose_loss, :190-209 compute_shape_match_loss, :211-227 compute_pose_match_loss, :229-249
  *      compute_kp_pose_match_loss; call sites train.py:89,189 and train_kp_to_pose.py:297).  Additions of ABI 4.

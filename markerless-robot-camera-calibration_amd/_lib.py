@@ -116,6 +116,10 @@ SIGNATURES = {
     "sv_icp_batched_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_icp_batched": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int, _P, c_int, c_double, c_int, c_double, c_double, _P,
                                c_size_t, _P, _P, _P]),
+    "sv_mesh_sample_workspace_bytes": (c_size_t, [c_int64]),
+    "sv_mesh_sample": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_size_t, _P, _P, _P, _P, _P, _P]),
+    "sv_sample_eliminate_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "sv_sample_eliminate": (c_int, [_P, c_int64, c_int64, c_double, c_double, c_int, _P, c_size_t, _P, _P, _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),

@@ -6,9 +6,11 @@ the Kabsch / averaging solves run through libsvhip.  Differences that are delibe
   * checkpoints: the reference's paths are not shipped.  `allow_random_init=True` keeps
     `pred_enabled` when a checkpoint is missing so the pipeline can be exercised with seeded random weights;
     with the reference's behaviour (False) a missing checkpoint disables prediction (all-zero segmentation, :281-283).
-  * ICP refinement (utils/icp.py) runs on libsvhip (sv_icp_point2point); the CAD model points are passed in
-    (`cad_points=`) because the reference's mesh asset does not ship with this build.  `icp_method="point2plane"`
-    is an opt-in beyond the reference: normals of the crop (sv_estimate_normals) and sv_icp_point2plane.
+  * ICP refinement (utils/icp.py) runs on libsvhip (sv_icp_point2point).  The CAD model is either passed in as
+    points (`cad_points=`) or built at start-up as the reference builds it, from the mesh file named by `cad_name=` or
+    INFERENCE.cad_name (utils/mesh.py load_cad_model); the mesh asset itself does not ship with this build, so its
+    path has to be given.  `icp_method="point2plane"` is an opt-in beyond the reference: normals of the crop
+    (sv_estimate_normals) and sv_icp_point2plane.
   * check_sanity: the reference derives ground-truth key points from the EE crop with utils/data.py:141-335
     get_6_key_points (label synthesis, out of scope); here the expected key points are the six constant
     reference_key_points moved by the predicted EE pose — the same quantity the reference compares against.
@@ -62,8 +64,10 @@ ICP_METHODS = ("point2point", "point2plane")
 
 class InferenceEngine:
     def __init__(self, calibration_only=False, device="cuda", allow_random_init=False, seed=1, cad_points=None,
-                 seg_precision=None, icp_method="point2point", icp_batched=False):
-        """icp_batched: refine all poses of a group of frames with ONE sv_icp_batched call (match_icp.many) instead of
+                 seg_precision=None, icp_method="point2point", icp_batched=False, cad_name=None):
+        """cad_points / cad_name: the CAD model of the end effector as points [P,3], or the path of its mesh (.obj) or
+        .pcd file, loaded as the reference loads it; cad_points wins, then cad_name, then INFERENCE.cad_name.
+        icp_batched: refine all poses of a group of frames with ONE sv_icp_batched call (match_icp.many) instead of
         one call and one read-back per pose; the results are identical.
         icp_method: the objective of the ICP refinement when INFERENCE.icp_enabled: "point2point" (the reference's) or
         "point2plane" (normals estimated on the crop once per frame, utils/icp.py get_point2plane_matcher).
@@ -82,9 +86,16 @@ class InferenceEngine:
             raise ValueError(f"icp_method must be one of {ICP_METHODS}, got {icp_method!r}")
         self.icp_method = icp_method
         self.icp_batched = bool(icp_batched)
+        # CAD-to-crop ICP (utils/icp.py): the reference samples its CAD points from app/hand_files/hand_notblender.obj
+        # at start-up (:56-57).  That file does not ship with this build -> the caller supplies the model points, or the
+        # path of the mesh to sample them from
+        if cad_points is None:
+            cad_name = cad_name if cad_name is not None else cfg()["INFERENCE"].get("cad_name")
+            if cad_name is not None:
+                from ..utils.mesh import load_cad_model
+
+                cad_points = load_cad_model(cad_name, device=self.device)[0]
         self.cad_points = cad_points
-        # CAD-to-crop ICP (utils/icp.py): the reference samples its CAD points from app/hand_files/hand_notblender.obj,
-        # which does not ship with this build -> the caller supplies the model points
         self.match_icp = None
         if cfg.INFERENCE.icp_enabled:
             if cad_points is None:

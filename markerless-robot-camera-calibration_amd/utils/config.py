@@ -24,7 +24,7 @@ _DEFAULTS = {
         "angle_diff_ignore_threshold": 0.4, "disable_position": False, "disable_orientation": False,
     },
     "INFERENCE": {
-        "ee_point_counts_threshold": 512, "icp_enabled": False, "num_of_dense_input_points": 2048,
+        "ee_point_counts_threshold": 512, "icp_enabled": False, "cad_name": None, "num_of_dense_input_points": 2048,
         "camera_link_transformation_pose": None,
         "SANITY": {"min_num_of_ee_points": 2048},
         "SEGMENTATION": {"backbone": "robotnet_segmentation", "scale": 200, "center_at_origin": True,

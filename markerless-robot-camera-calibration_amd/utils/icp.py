@@ -1,6 +1,7 @@
 """ICP refinement with the reference's interface (utils/icp.py:13-83) on libsvhip.
 
-    match = get_point2point_matcher(cad_points)       # the reference samples 8192 points from app/hand_files/*.obj
+    match = get_point2point_matcher(cad_points)       # points [P,3], or the mesh / .pcd file the reference reads:
+    match = get_point2point_matcher("hand_notblender.obj")   # 16384 surface samples thinned to 8192 (utils/mesh.py)
     pose = match(ee_points, pose_initial)             # (x, y, z, qw, qx, qy, qz) -> refined pose
 
 Same registration as the reference's open3d call: point-to-point, max correspondence distance 0.1 m, at most 30
@@ -33,6 +34,17 @@ from .._lib import call, ptr, stream_ptr
 from .transformation import get_pose_from_matrix, get_transformation_matrix
 
 
+def _cad_model(cad_points, device):
+    """what the matchers are given -> the model points: an array is passed on as it is, a str / os.PathLike is the
+    reference's cad_name and is loaded as utils/icp.py:17-40 does (utils/mesh.py load_cad_model)"""
+    from .mesh import is_path, load_cad_model
+
+    if cad_points is None:
+        raise ValueError("the matcher needs cad_points (the CAD model of the end effector, [P,3]) or the path of its "
+                         "mesh / .pcd file")
+    return load_cad_model(cad_points, device=device)[0] if is_path(cad_points) else cad_points
+
+
 def icp_point2point(src, tgt, init_T=None, max_distance=0.1, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
                     device="cuda"):
     """src [S,3], tgt [T,3] (numpy or tensors) -> (T 4x4 float64 numpy, fitness, inlier rmse, updates)."""
@@ -60,6 +72,7 @@ class PointToPointMatcher:
 
     def __init__(self, cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
         self.device = torch.device(device)
+        cad_points = _cad_model(cad_points, self.device)
         self.cad = torch.as_tensor(np.ascontiguousarray(cad_points, dtype=np.float32)).to(device)
         self.icp_threshold, self.max_iterations = icp_threshold, max_iterations
 
@@ -78,7 +91,7 @@ class PointToPointMatcher:
 
 
 def get_point2point_matcher(cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
-    """-> match(ee_points, pose_initial), a PointToPointMatcher"""
+    """-> match(ee_points, pose_initial), a PointToPointMatcher; cad_points: the model points or its file's path"""
     return PointToPointMatcher(cad_points, icp_threshold, max_iterations, device)
 
 
@@ -189,7 +202,7 @@ class PointToPlaneMatcher:
                  device="cuda"):
         _check_normals_args(1, normal_radius, normal_max_nn)
         self.device = torch.device(device)
-        self.cad = _cloud(cad_points, "cad_points", self.device)
+        self.cad = _cloud(_cad_model(cad_points, self.device), "cad_points", self.device)
         self.icp_threshold, self.max_iterations = float(icp_threshold), int(max_iterations)
         self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
 

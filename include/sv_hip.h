@@ -67,7 +67,7 @@ const char* sv_last_error(void);
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
  *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
- *    entries of N6, the segmentation criterion and step metrics of N7 */
+ *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -542,6 +542,50 @@ size_t sv_sample_eliminate_workspace_bytes(int64_t N, int max_degree);
 int sv_sample_eliminate(const double* points, int64_t N, int64_t n_keep, double r_max, double r_min, int max_degree,
                         void* workspace, size_t workspace_bytes, int32_t* kept, int32_t* order, int32_t* counters,
                         sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N3e  packed sensor records -> points, colours and source indices (the reference decodes a ROS PointCloud2 on the host,
+ *      utils/ros_utils.py get_points_and_colors called by app/freenect_data_engine.py, and reads .pcd frames through
+ *      Open3D, app/data_engine.py:161-204 PCDDataEngine with get_roi_mask).  A PointCloud2 `data` buffer and a binary PCD
+ *      body are the same thing, a strided array of fixed-layout records, and one entry serves both.  Additive, the ABI
+ *      version stays 4.  Every output equals a numpy restatement bit for bit; parity with sensor_msgs, PCL and Open3D is
+ *      by construction and unverified.
+ *
+ *   sv_unpack_points: data uint8[data_bytes] (device, any alignment) -> points float32[n_records][3],
+ *   rgb float32[n_records][3] (not touched and may be NULL when rgb_off < 0), src int32[n_records] (may be NULL),
+ *   count int64[1].  Record i (0 <= i < n_records) starts at byte (i / width) * row_step + (i % width) * point_step.
+ *   Field bytes: a field is the 4 (F32, rgb) or 8 (F64) bytes at record + offset, at any alignment, least significant
+ *   byte first, or most significant first when SV_UNPACK_BIGENDIAN is set.
+ *   Coordinates: SV_FIELD_F32 values are copied as bits (a kept NaN keeps its payload).  SV_FIELD_F64 values are tested
+ *   for finiteness as doubles and then rounded to float32, round-to-nearest-even (np.copyto(float32, float64)): a finite
+ *   double beyond FLT_MAX becomes +-inf and is still kept, a result below FLT_MIN is a denormal; a float64 NaN becomes
+ *   sign | 0x7fc00000 | (the top 22 bits of its payload).
+ *   Keep rule: a record is kept iff x, y and z are all finite, or SV_UNPACK_KEEP_NONFINITE is set; and, when box_host is
+ *   given, lo[a] < (double)p32[a] < hi[a] on all three axes (strict bounds, get_roi_mask), p32 being the float32
+ *   coordinate - a NaN coordinate fails it.  box_host is a HOST double[6] = lo x, y, z, hi x, y, z (or NULL); the six
+ *   values travel as kernel arguments: no copy and no wait.
+ *   Order: kept records are written in ascending record index, the order a boolean mask gives.  points[k] = the
+ *   coordinates of the k-th kept record, src[k] = its record index, count[0] = the number kept; rows at or beyond
+ *   count[0] are unspecified.
+ *   Colour: v = the uint32 at rgb_off, whatever type the field declares (PCL stores the bits in a float field);
+ *   r = (v >> 16) & 255, g = (v >> 8) & 255, b = v & 255; rgb[k] = (lut[r], lut[g], lut[b]) with lut a device float[256],
+ *   or the byte values as floats when lut is NULL.
+ *   Checked before any HIP call: n_records in [1, 2^24], width >= 1, point_step in [1, 4096],
+ *   row_step >= width * point_step, xyz_type and flags known, every field inside the record, the x, y, z and rgb fields
+ *   disjoint, data_bytes covering the last record, box bounds not NaN and lo <= hi, required pointers non-null,
+ *   workspace >= sv_unpack_points_workspace_bytes(n_records).
+ *   3 launches whatever n_records is (per-tile counts by ballot + popcount, one workgroup's exclusive scan, ordered
+ *   write), no memset, no atomics, no read-back; repeated calls give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+#define SV_FIELD_F32 7 /* the PointField datatype codes */
+#define SV_FIELD_F64 8
+#define SV_UNPACK_BIGENDIAN 1
+#define SV_UNPACK_KEEP_NONFINITE 2
+size_t sv_unpack_points_workspace_bytes(int64_t n_records);
+int sv_unpack_points(const uint8_t* data, int64_t data_bytes, int64_t n_records, int64_t width, int64_t point_step,
+                     int64_t row_step, int x_off, int y_off, int z_off, int xyz_type, int rgb_off, int flags,
+                     const double* box_host, const float* lut, void* workspace, size_t workspace_bytes, float* points,
+                     float* rgb, int32_t* src, int64_t* count, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188

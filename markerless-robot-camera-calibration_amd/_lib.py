@@ -33,6 +33,8 @@ SV_COORD_BITS = 18
 SV_MAX_BATCH = 1024
 SV_FRAME_MAX_LEVELS, SV_FRAME_MAX_CUTS, SV_FRAME_RECORD = 8, 4, 16
 SV_FRAME_K3, SV_FRAME_DOWN, SV_FRAME_UP, SV_FRAME_SPLIT = 1, 2, 4, 8
+SV_FIELD_F32, SV_FIELD_F64 = 7, 8
+SV_UNPACK_BIGENDIAN, SV_UNPACK_KEEP_NONFINITE = 1, 2
 SV_FRAME_REC_HASH, SV_FRAME_REC_K3, SV_FRAME_REC_DOWN, SV_FRAME_REC_UP, SV_FRAME_REC_SPLIT = 1, 2, 3, 4, 5
 
 
@@ -120,6 +122,9 @@ SIGNATURES = {
     "sv_mesh_sample": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_size_t, _P, _P, _P, _P, _P, _P]),
     "sv_sample_eliminate_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_sample_eliminate": (c_int, [_P, c_int64, c_int64, c_double, c_double, c_int, _P, c_size_t, _P, _P, _P, _P]),
+    "sv_unpack_points_workspace_bytes": (c_size_t, [c_int64]),
+    "sv_unpack_points": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                 _P, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),

@@ -3,6 +3,7 @@
 (README.md:55-62), listed per split in a JSON file with a "position" tag (app/data_engine.py:53-158,
 utils/file_utils.py:4-16).  `write_frame_pickle` produces that format from a synthetic scene so the loaders can be
 exercised without the authors' data (their sample frames are missing blobs)."""
+import glob
 import json
 import os
 import pickle
@@ -12,7 +13,7 @@ from itertools import cycle
 import numpy as np
 
 from ..utils.transformation import get_quaternion_rotation_matrix, switch_w
-from .dto import PointCloudDTO, RawDTO
+from .dto import PackedCloudDTO, PointCloudDTO, RawDTO
 
 
 def load_alive_file(filename):
@@ -112,3 +113,44 @@ class PickleDataEngine:
         labels[ee_idx] = 2
         return RawDTO(points, rgb, pose, labels, ee2base_pose=ee2base,
                       other={"filepath": item["filepath"], "position": item["position"]})
+
+
+class PCDDataEngine:
+    """app/data_engine.py:161-204: a folder of <n>.pcd frames, sorted by the integer n, every `step`-th kept, each with
+    its poses beside it (<n>.npy, the ground truth, which the reference loads and then leaves out of the DTO, and
+    <n>_robot2ee_pose.npy, stored x,y,z,qx,qy,qz,qw and switched to wxyz).  The frame is cut to get_roi_mask's
+    default box (+-500 on every axis, open bounds); points and colours are float32 (the reference casts Open3D's float64
+    colours byte / 255).  packed=True yields PackedCloudDTOs instead: the file's records as they are (memory-mapped), box
+    and colour convention attached, decoded by the engine on the device."""
+
+    BOX = (-500.0, -500.0, -500.0, 500.0, 500.0, 500.0)
+    COLOR = "float32"
+
+    def __init__(self, data_path, cyclic=True, step=10, packed=False):
+        self.data = glob.glob(os.path.join(data_path, "*.pcd"))
+        self.data.sort(key=lambda x: int(os.path.basename(x).split(".")[0]))
+        self.data = [self.data[i] for i in range(0, len(self.data), step)]
+        self.packed = bool(packed)
+        self.data_pool = cycle(self.data) if cyclic else iter(self.data)
+
+    def get(self):
+        from ..utils.packed import PackedFrame
+
+        try:
+            path = next(self.data_pool)
+        except StopIteration:
+            return None
+        frame = PackedFrame.from_pcd(path)
+        ee2base_pose = switch_w(np.load(path.replace(".pcd", "_robot2ee_pose.npy"), allow_pickle=True))  # -> wxyz
+        dto = PackedCloudDTO(timestamp=datetime.utcnow(), ee2base_pose=ee2base_pose, id=path, gt_pose=None, packed=frame,
+                             box=self.BOX, color=self.COLOR)
+        return dto if self.packed else dto.decoded()
+
+    def run(self):
+        return None
+
+    def exit(self):
+        return None
+
+    def __len__(self):
+        return len(self.data)

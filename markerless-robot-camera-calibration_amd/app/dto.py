@@ -17,6 +17,28 @@ class PointCloudDTO:
 
 
 @dataclass
+class PackedCloudDTO:
+    """A frame that stays in the bytes it arrived in (utils/packed.py PackedFrame): the fields of PointCloudDTO, with
+    `points` and `rgb` None, plus the packed records, the region-of-interest box (lo x, y, z, hi x, y, z, or None) and the
+    colour convention ("float64": byte / 255 in float64, "float32": float32(byte / 255)).  The engine decodes it on the
+    device; `decoded()` is the host frame it stands for."""
+    points: np.array = None
+    rgb: np.array = None
+    timestamp: datetime = None
+    ee2base_pose: np.array = None
+    joint_angles: np.array = None
+    id: str = None
+    gt_pose: np.array = None
+    packed: object = None
+    box: tuple = None
+    color: str = "float64"
+
+    def decoded(self) -> PointCloudDTO:
+        points, rgb, _ = self.packed.decode_host(box=self.box, color=self.color)
+        return PointCloudDTO(points, rgb, self.timestamp, self.ee2base_pose, self.joint_angles, self.id, self.gt_pose)
+
+
+@dataclass
 class RawDTO:
     points: np.array
     rgb: np.array

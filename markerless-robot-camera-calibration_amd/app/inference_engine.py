@@ -36,7 +36,7 @@ from ..utils.data import get_farthest_point_sample_idx
 from ..utils.transformation import (get_base2cam_matrix, get_q_from_matrix,
                                     get_quaternion_rotation_matrix, get_rigid_transform_3D,
                                     get_rigid_transform_3D_batched, transform_pose2pose)
-from .dto import CalibrationResultDTO, PointCloudDTO, ResultDTO, TestResultDTO
+from .dto import CalibrationResultDTO, PackedCloudDTO, PointCloudDTO, ResultDTO, TestResultDTO
 
 # app/inference_engine.py:128-137
 REFERENCE_KEY_POINTS = np.array([
@@ -191,23 +191,67 @@ class InferenceEngine:
             self._one_frame_stream = st
         return st.run_one(points, rgb)
 
-    def predict_segmentation_stream(self, frames, compute_streams=3, group=1):
+    def predict_segmentation_packed(self, frame, box=None, color="float64"):
+        """predict_segmentation for a frame that is still packed records (utils/packed.py PackedFrame: a PointCloud2
+        message's bytes or a binary .pcd body): the bytes go to the device once and sv_unpack_points decodes them there
+        (app/pipeline.py PackedFrameStream).  -> (labels int64 [k], src int32 [k]) over the records that are finite and inside
+        `box`, in record order; src[j] is the record of point j (PackedFrame.scatter makes the label image).  The labels equal
+        predict_segmentation(points, preprocess.normalize_colors(rgb)) of frame.decode_host(box, color=color)."""
+        from .pipeline import PackedFrameStream
+
+        key = (self._config.INFERENCE.SEGMENTATION.scale, color)
+        streams = self.__dict__.setdefault("_one_frame_packed", {})
+        if key not in streams:
+            streams[key] = PackedFrameStream(self.device, key[0], self._segment, self._largest_ee_cluster_rule, color=color,
+                                             compute_streams=1, one_frame=True)
+        return streams[key].run_one(frame, box)
+
+    def predict_segmentation_stream(self, frames, compute_streams=3, group=1, color="float64"):
         """Streaming form of predict_segmentation for a sequence of frames (the reference's consumer is the per-frame
         loop of app/main.py:432-456): `frames` yields (points, rgb) host arrays, the generator yields the label arrays in
         order, each IDENTICAL to predict_segmentation(points, rgb) - while frame i's network runs, frame i+1 is staged
         through pinned memory, uploaded and voxelised, and frame i-1's cluster rule and label download complete
         (app/pipeline.py HostFrameStream).  group > 1: that many consecutive frames share one sparse tensor (the
         reference's batched format, data/alivev2.py:358-383) - the same labels, launches `group` times longer (≈ 4 % more
-        frames/s at 4), results delivered a group at a time.  Engine-path throughput: see bench.py's `engine` block."""
-        from .pipeline import HostFrameStream
+        frames/s at 4), results delivered a group at a time.  Engine-path throughput: see bench.py's `engine` block.
+        Packed frames (utils/packed.py): items that are a PackedFrame, (PackedFrame, box) or (PackedFrame, box, color) take
+        the packed stream (app/pipeline.py PackedFrameStream) and yield (labels, src) as predict_segmentation_packed; `color`
+        is the convention of items that name none."""
+        import itertools
 
-        # one stream object per configuration, kept: its pinned staging buffers and HIP streams are expensive to create
-        key = (compute_streams, self._config.INFERENCE.SEGMENTATION.scale, max(1, int(group)))
-        streams = self.__dict__.setdefault("_seg_streams", {})
-        if key not in streams:
-            streams[key] = HostFrameStream(self.device, key[1], self._segment, self._largest_ee_cluster_rule,
-                                           compute_streams=compute_streams, group=key[2])
-        return streams[key].run(frames)
+        from ..utils.packed import PackedFrame
+        from .pipeline import HostFrameStream, PackedFrameStream
+
+        def is_packed(item):
+            return isinstance(item, PackedFrame) or (isinstance(item, tuple) and isinstance(item[0], PackedFrame))
+
+        def run():
+            # packed frames - PackedFrame, (PackedFrame, box) or (PackedFrame, box, color) items - take the packed stream and
+            # yield (labels, src) as predict_segmentation_packed; the first item decides for the whole sequence, its colour
+            # convention included (`color` where the item names none)
+            it = iter(frames)
+            first = next(it, None)
+            if first is None:
+                return
+            every = itertools.chain([first], it)
+            # one stream object per configuration, kept: its pinned staging buffers and HIP streams are expensive to create
+            key = (compute_streams, self._config.INFERENCE.SEGMENTATION.scale, max(1, int(group)))
+            if is_packed(first):
+                col = first[2] if isinstance(first, tuple) and len(first) > 2 and first[2] is not None else color
+                streams = self.__dict__.setdefault("_seg_streams_packed", {})
+                if key + (col,) not in streams:
+                    streams[key + (col,)] = PackedFrameStream(self.device, key[1], self._segment,
+                                                              self._largest_ee_cluster_rule, color=col,
+                                                              compute_streams=compute_streams, group=key[2])
+                yield from streams[key + (col,)].run((f if isinstance(f, tuple) else (f, None)) for f in every)
+                return
+            streams = self.__dict__.setdefault("_seg_streams", {})
+            if key not in streams:
+                streams[key] = HostFrameStream(self.device, key[1], self._segment, self._largest_ee_cluster_rule,
+                                               compute_streams=compute_streams, group=key[2])
+            yield from streams[key].run(every)
+
+        return run()
 
     # ---- pose stages on end-effector crops (reference :437-559), one or several crops per network run ---------------
     def _crop_runner(self):
@@ -484,9 +528,19 @@ class InferenceEngine:
                 return False
         return True
 
+    @staticmethod
+    def _n_points(data):
+        if isinstance(data, PackedCloudDTO):
+            return len(data.packed.decode_host(box=data.box, color=data.color)[2])
+        return len(data.points)
+
     def predict(self, data: PointCloudDTO):
         if not self.pred_enabled:
-            return ResultDTO(segmentation=np.zeros(len(data.points), dtype=np.int64))
+            return ResultDTO(segmentation=np.zeros(self._n_points(data), dtype=np.int64))
+        if isinstance(data, PackedCloudDTO):
+            # decoded on the device; the pose stages take their crop from the packed records (_pose_enqueue)
+            seg, src = self.predict_segmentation_packed(data.packed, box=data.box, color=data.color)
+            return self._pose_collect(self._pose_enqueue([(data, src, seg)], one_frame=True))[0]
         rgb = preprocess.normalize_colors(data.rgb)
         seg = self.predict_segmentation(data.points, rgb)
         return self._pose_collect(self._pose_enqueue([(data, rgb, seg)], one_frame=True))[0]
@@ -504,12 +558,16 @@ class InferenceEngine:
         their input)."""
         if not self.pred_enabled:
             for data in frames:
-                yield ResultDTO(segmentation=np.zeros(len(data.points), dtype=np.int64))
+                yield ResultDTO(segmentation=np.zeros(self._n_points(data), dtype=np.int64))
             return
         window = collections.deque()
 
         def inputs():
             for data in frames:
+                if isinstance(data, PackedCloudDTO):
+                    window.append((data, None))
+                    yield data.packed, data.box, data.color  # a sequence's frames share one convention
+                    continue
                 rgb = preprocess.normalize_colors(data.rgb)
                 window.append((data, rgb))
                 yield data.points, rgb
@@ -520,6 +578,8 @@ class InferenceEngine:
         if not pose_thread:
             for seg in seg_stream:
                 data, rgb = window.popleft()
+                if isinstance(data, PackedCloudDTO):
+                    seg, rgb = seg  # (labels, src): the source indices travel in the colours' place
                 cur.append((data, rgb, seg))
                 if len(cur) >= group:
                     pending.append(self._pose_enqueue(cur, one_frame=False))
@@ -575,6 +635,8 @@ class InferenceEngine:
         try:
             for seg in seg_stream:
                 data, rgb = window.popleft()
+                if isinstance(data, PackedCloudDTO):
+                    seg, rgb = seg
                 cur.append((data, rgb, seg))
                 if len(cur) >= group:
                     jobs.put(cur)
@@ -597,13 +659,19 @@ class InferenceEngine:
     def _pose_enqueue(self, items, one_frame):
         """items: [(PointCloudDTO, normalised colours, labels)].  Crops the end effector of every frame (host: the labels
         are host arrays, as in the reference :297-303) and enqueues the rotation and key-point networks for all crops that
-        pass the point-count threshold; nothing here waits for the GPU."""
+        pass the point-count threshold; nothing here waits for the GPU.  For a PackedCloudDTO the second member is `src`,
+        the record of every point, and the crop is decoded from those records on the host (a few thousand of them:
+        packed.take), with the dtypes of decoded().points[ee_idx] and normalize_colors(decoded().rgb)[ee_idx]."""
         cfg = self._config
         crops = []
         for data, rgb, seg in items:
             ee_idx = np.where(seg == 2)[0]
             if len(ee_idx) < cfg.INFERENCE.ee_point_counts_threshold:
                 crops.append(None)
+            elif isinstance(data, PackedCloudDTO):
+                from ..utils.packed import normalized_color_table
+
+                crops.append(data.packed.take(rgb[ee_idx], lut=normalized_color_table(data.color)))
             else:
                 crops.append((data.points[ee_idx], rgb[ee_idx]))
         live = [c for c in crops if c is not None]
@@ -746,7 +814,8 @@ class InferenceEngine:
         for data, result in zip(frames, results):
             if not result.is_confident or data.ee2base_pose is None:
                 continue
-            crop = data.points[result.segmentation == 2]
+            points = data.decoded().points if isinstance(data, PackedCloudDTO) else data.points  # a set-up step
+            crop = points[result.segmentation == 2]
             if len(crop) >= self._config.INFERENCE.ee_point_counts_threshold:
                 crops.append(crop)
                 ee2base.append(data.ee2base_pose)

@@ -432,6 +432,163 @@ class HostFrameStream:
             self.pipe.drain()
 
 
+class _PackedSlot:
+    """pinned buffers of one in-flight packed frame: labels | source indices (device -> host) | the raw records (host ->
+    device), one pinned allocation"""
+
+    def __init__(self):
+        self.cap = self.cap_bytes = 0
+        self.labels = self.src = self.raw = None
+        self.uploaded = None
+
+    def reserve(self, n, nbytes):
+        if self.raw is None or n > self.cap or nbytes > self.cap_bytes:
+            self.cap = cap = max(n, int(self.cap * 1.25), 1)
+            self.cap_bytes = cap_bytes = max(nbytes, int(self.cap_bytes * 1.25), 1)
+            buf = torch.empty(cap * 12 + cap_bytes, dtype=torch.uint8).pin_memory()
+            self.labels = buf[:8 * cap].view(torch.int64)
+            self.src = buf[8 * cap:12 * cap].view(torch.int32)
+            self.raw = buf[12 * cap:]
+
+
+class PackedFrameStream(HostFrameStream):
+    """HostFrameStream for frames that arrive as packed records (utils/packed.py PackedFrame): the same slots, streams,
+    grouping and finalisation, but a frame is never materialised on the host.  The upload step stages the raw bytes into the
+    slot's pinned buffer, copies them to the device on the prep stream and runs sv_unpack_points there (fields decoded,
+    non-finite and out-of-box records dropped in order, colours unpacked through the table of normalised colours), reads the
+    number kept (8 bytes) and forms the (batch, x, y, z) rows from the decoded points exactly as HostFrameStream does
+    (`points * scale` in float32).  Items are (PackedFrame, box or None[, color]); results are (labels int64 [k], src int32 [k]):
+    src[j] is the record the j-th point came from.  `color`: the convention the byte colours stand for ("float64" or
+    "float32", utils/packed.py); the network sees preprocess.normalize_colors of them."""
+
+    def __init__(self, device, scale, stage, finish=None, color="float64", **kw):
+        from ..utils.packed import device_lut_values
+
+        self._lut_values = device_lut_values(color)  # rejects an unknown convention before anything is allocated
+        super().__init__(device, scale, stage, finish, **kw)
+        self.color = color
+        self._lut = None
+        self._slots = [_PackedSlot() for _ in self._slots]
+
+    def preallocate(self, n, nbytes=None):
+        """Pin every slot's buffers for frames of up to n records (nbytes: of raw data, default 32 per record)."""
+        for slot in self._slots:
+            slot.reserve(int(n), int(nbytes if nbytes is not None else 32 * n))
+
+    def _stage_and_unpack(self, frame, box=None, color=None):
+        """one frame: pinned staging, H2D and sv_unpack_points on the prep stream -> (slot, points, rgb, src, count), the
+        device arrays unsliced; nothing is read back"""
+        if color is not None and color != self.color:
+            raise ValueError(f"this stream decodes {self.color!r} colours, the frame names {color!r}")
+        if frame.n_records < 1:
+            raise ValueError("a packed frame needs at least one record")
+        if frame.rgb_offset < 0:
+            raise ValueError("the frame has no rgb field: the segmentation network takes colours")
+        slot = self._slots[self._n % len(self._slots)]
+        self._n += 1
+        if slot.uploaded is not None:
+            slot.uploaded.synchronize()
+        nbytes = frame.nbytes_used
+        slot.reserve(frame.n_records, nbytes)
+        slot.raw.numpy()[:nbytes] = frame._bytes()[:nbytes]
+        with torch.cuda.stream(self.pipe.prep_stream):
+            if self._lut is None:
+                self._lut = torch.from_numpy(self._lut_values).to(self.device)
+            d_raw = slot.raw[:nbytes].to(self.device, non_blocking=True)
+            slot.uploaded = torch.cuda.Event()
+            slot.uploaded.record(self.pipe.prep_stream)
+            points, rgb, src, count = frame.unpack(d_raw, box=box, lut=self._lut)
+        return slot, points, rgb, src, count
+
+    def _upload_and_prepare(self, frame, box=None, color=None):
+        t0 = time.perf_counter()
+        slot, points, rgb, src, count = self._stage_and_unpack(frame, box, color)
+        with torch.cuda.stream(self.pipe.prep_stream):
+            n = int(count.item())  # waits for this frame's copy and three kernels only
+            if n < 1:
+                raise ValueError("no record of the frame is finite and inside the box")
+            d_pts = points[:n]
+            coords4 = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
+            torch.mul(d_pts, self.scale, out=coords4[:, 1:])
+        t1 = time.perf_counter()
+        out = self.pipe.prepare(coords4, rgb[:n], tag=(slot, d_pts, n, src[:n]))
+        t2 = time.perf_counter()
+        self.host_s["stage"] += t1 - t0
+        self.host_s["prepare"] += t2 - t1
+        self.host_s["frames"] += 1
+        return out
+
+    def _upload_and_prepare_group(self, members):
+        """members: [(PackedFrame, box), ...] of consecutive frames -> one PreparedFrame over all of them (batch column =
+        position in the group); every frame is unpacked before the counts are read back, once for the group"""
+        if len(members) == 1:
+            out = self._upload_and_prepare(*members[0])
+            out.tag = [out.tag]
+            return out
+        t0 = time.perf_counter()
+        staged = [self._stage_and_unpack(*m) for m in members]
+        with torch.cuda.stream(self.pipe.prep_stream):
+            sizes = [int(k) for k in torch.cat([s[4] for s in staged]).cpu()]
+            if min(sizes) < 1:
+                raise ValueError("no record of a frame is finite and inside the box")
+            coords4 = torch.empty((sum(sizes), 4), dtype=torch.float32, device=self.device)
+            feats = torch.empty((sum(sizes), 3), dtype=torch.float32, device=self.device)
+            tags, off = [], 0
+            for b, ((slot, points, rgb, src, _), n) in enumerate(zip(staged, sizes)):
+                d_pts = points[:n]
+                rows = coords4[off:off + n]
+                rows[:, 0] = float(b)
+                torch.mul(d_pts, self.scale, out=rows[:, 1:])
+                feats[off:off + n].copy_(rgb[:n])
+                tags.append((slot, d_pts, n, src[:n]))
+                off += n
+        t1 = time.perf_counter()
+        out = self.pipe.prepare(coords4, feats, tag=tags)
+        out.sizes = sizes
+        t2 = time.perf_counter()
+        self.host_s["stage"] += t1 - t0
+        self.host_s["prepare"] += t2 - t1
+        self.host_s["frames"] += len(members)
+        return out
+
+    def _download(self, prepared, tags):
+        """`finish` on every frame's slice of the labels, labels and source indices to pinned memory, one wait"""
+        import numpy as np
+
+        stream = prepared.stream if prepared.stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            off = 0
+            for slot, d_pts, n, d_src in tags:
+                label = prepared.result[off:off + n]
+                if self.finish is not None:
+                    label = self.finish(label, d_pts)
+                slot.labels[:n].copy_(label, non_blocking=True)
+                slot.src[:n].copy_(d_src, non_blocking=True)
+                off += n
+            done = torch.cuda.Event()
+            done.record(stream)
+        done.synchronize()
+        outs = [(np.array(slot.labels.numpy()[:n]), np.array(slot.src.numpy()[:n])) for slot, _, n, _ in tags]
+        prepared.result = prepared.tag = None
+        return outs
+
+    def _finalize(self, prepared):
+        t0 = time.perf_counter()
+        out = self._download(prepared, [prepared.tag])[0]
+        self.host_s["finalize"] += time.perf_counter() - t0
+        return out
+
+    def _finalize_group(self, prepared):
+        t0 = time.perf_counter()
+        outs = self._download(prepared, prepared.tag)
+        self.host_s["finalize"] += time.perf_counter() - t0
+        return outs
+
+    def run_one(self, frame, box=None):
+        """one packed frame, start to finish -> (labels, src)"""
+        return super().run_one(frame, box)
+
+
 class PinnedRing:
     """A few pinned host buffers handed out in turn; a slot is reused once the event recorded for its last transfer has
     completed (pinning memory costs hundreds of microseconds: the buffers are kept and grown, never freed per frame)."""

@@ -67,7 +67,7 @@ const char* sv_last_error(void);
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
  *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
- *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e */
+ *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e, the RGB-D ingest of N3f */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -586,6 +586,65 @@ int sv_unpack_points(const uint8_t* data, int64_t data_bytes, int64_t n_records,
                      int64_t row_step, int x_off, int y_off, int z_off, int xyz_type, int rgb_off, int flags,
                      const double* box_host, const float* lut, void* workspace, size_t workspace_bytes, float* points,
                      float* rgb, int32_t* src, int64_t* count, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N3f  a depth image and a colour image -> a registered, coloured, unorganised cloud (the reference does this on the host,
+ *      scripts/ycb_generate_point_cloud.py:127-274: filterDiscontinuities, registerDepthMap and
+ *      registeredDepthMapToPointCloud, the last two as Python loops over every pixel).  Additive, the ABI version stays 4.
+ *      Every output equals a numpy restatement bit for bit, and the filter, the registered map and the cloud equal the
+ *      reference's own three functions on tests/golden/rgbd_ycb.npz; parity with depth_image_proc, librealsense and Open3D
+ *      is by construction and unverified.
+ *
+ *   sv_rgbd_cloud: depth (device, any alignment) = Hd rows of Wd values, row v at byte v * depth_row_bytes, little-endian
+ *   uint16 (SV_DEPTH_U16) or float32 (SV_DEPTH_F32); color (device, any alignment, or NULL) = Hc rows of Wc pixels of
+ *   3 bytes r, g, b (b, g, r under SV_RGBD_BGR), row v at byte v * color_row_bytes; mask uint8[Hc * Wc] or NULL.
+ *   -> points float32[Hc * Wc][3], points64 double[Hc * Wc][3] (may be NULL), rgb float32[Hc * Wc][3] (may be NULL only if
+ *   color is; not touched then), src int32[Hc * Wc] (may be NULL), registered double[Hc * Wc] (may be NULL), count int64[1].
+ *   cam_host is a HOST double[21]: depth fx, fy, cx, cy; colour fx, fy, cx, cy; the top three rows of the colour-from-depth
+ *   transform H, row-major (12 values); depth_scale.  box_host is a HOST double[6] = lo x, y, z, hi x, y, z, or NULL.  Both
+ *   travel as kernel arguments: no copy and no wait.
+ *   ARITHMETIC: float64 throughout, every operation rounded on its own (no fused multiply-add) and in exactly the order
+ *   and bracketing written below.  This order is the contract.
+ *   Stage 1, filter (U16 only; off when filter_size == 0, else filter_size odd in 3..15): with o = filter_size / 2, pixel
+ *   (v, u) with o <= v < Hd - o and o <= u < Wd - o becomes 0 iff max(mid - min, max - mid) > filter_thresh, min and max
+ *   over the filter_size^2 window of RAW values, zeros included, compared as integers.  Border pixels never change; an
+ *   image smaller than the window is unchanged.  d = (double)value * depth_scale.  F32: a value is valid iff it is finite
+ *   and > 0, an invalid value counts as 0, and filter_size must be 0.
+ *   Stage 2, register (skipped under SV_RGBD_ALIGNED, where registered[v][u] = d and the colour intrinsics are the ones
+ *   used): for every depth pixel with d != 0
+ *     x = ((u - cxd) * d) * (1.0 / fxd), y = ((v - cyd) * d) * (1.0 / fyd), z = d
+ *     X = ((H00 * x + H01 * y) + H02 * z) + H03, Y and Z likewise from rows 1 and 2
+ *     iz = 1.0 / Z, uu = (fxc * X) * iz + cxc, vv = (fyc * Y) * iz + cyc
+ *     ui = trunc(uu + 0.5), vi = trunc(vv + 0.5): toward zero, as Python's int(), so uu in (-1.5, -0.5) lands on pixel 0
+ *   the candidate is dropped when ui or vi is not finite or lies outside [0, Wc) x [0, Hc), or when Z is not a positive
+ *   finite number; registered[vi][ui] = the LARGEST candidate Z (the reference's `>` against a zero-initialised map), the
+ *   smallest under SV_RGBD_NEAREST, 0 where none lands.  The z-buffer is a 64-bit integer atomic max / min on the bit
+ *   pattern of the positive double: the order of arrival cannot show and repeated calls give the same bits.
+ *   Stage 3, cloud: colour pixel j = v * Wc + u with r = registered[v][u] is kept iff r > 0, and mask is NULL or
+ *   mask[j] == 0, and, when box_host is given, lo[a] < (double)p32[a] < hi[a] on all three axes (strict, as
+ *   sv_unpack_points).  points64 = (((u - cxc) * r) * (1.0 / fxc), ((v - cyc) * r) * (1.0 / fyc), r); points = p32 = the
+ *   same rounded to float32, nearest-even; rgb[k] = lut[byte] per channel in r, g, b order (lut a device float[256]), or
+ *   the byte as a float when lut is NULL; src[k] = j.  Kept pixels are written in ascending j; count[0] = their number;
+ *   rows at or beyond it are unspecified.
+ *   Checked before any HIP call: dimensions >= 1 and Hd * Wd, Hc * Wc <= 2^24; row bytes covering a row; depth_type and
+ *   flags known; the filter rules above and filter_thresh >= 0; every cam_host value finite, the four focal lengths and
+ *   depth_scale non-zero; SV_RGBD_ALIGNED with Hd, Wd == Hc, Wc; box bounds not NaN and lo <= hi; required pointers
+ *   non-null; workspace >= sv_rgbd_cloud_workspace_bytes(Hd, Wd, Hc, Wc).
+ *   5 launches whatever the images hold (z-buffer clear; filter + project, the window staged through an LDS tile with
+ *   halo; per-tile counts; one workgroup's scan; ordered write), no read-back.
+ * ------------------------------------------------------------------------------------------- */
+#define SV_DEPTH_U16 4 /* the PointField datatype codes */
+#define SV_DEPTH_F32 7
+#define SV_RGBD_ALIGNED 1
+#define SV_RGBD_NEAREST 2
+#define SV_RGBD_BGR 4
+size_t sv_rgbd_cloud_workspace_bytes(int64_t Hd, int64_t Wd, int64_t Hc, int64_t Wc);
+int sv_rgbd_cloud(const void* depth, int depth_type, int64_t Hd, int64_t Wd, int64_t depth_row_bytes,
+                  const uint8_t* color, int64_t Hc, int64_t Wc, int64_t color_row_bytes,
+                  const uint8_t* mask, const double* cam_host, int filter_size, int filter_thresh, int flags,
+                  const double* box_host, const float* lut, void* workspace, size_t workspace_bytes,
+                  float* points, double* points64, float* rgb, int32_t* src, double* registered,
+                  int64_t* count, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188

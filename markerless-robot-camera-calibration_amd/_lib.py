@@ -35,6 +35,8 @@ SV_FRAME_MAX_LEVELS, SV_FRAME_MAX_CUTS, SV_FRAME_RECORD = 8, 4, 16
 SV_FRAME_K3, SV_FRAME_DOWN, SV_FRAME_UP, SV_FRAME_SPLIT = 1, 2, 4, 8
 SV_FIELD_F32, SV_FIELD_F64 = 7, 8
 SV_UNPACK_BIGENDIAN, SV_UNPACK_KEEP_NONFINITE = 1, 2
+SV_DEPTH_U16, SV_DEPTH_F32 = 4, 7
+SV_RGBD_ALIGNED, SV_RGBD_NEAREST, SV_RGBD_BGR = 1, 2, 4
 SV_FRAME_REC_HASH, SV_FRAME_REC_K3, SV_FRAME_REC_DOWN, SV_FRAME_REC_UP, SV_FRAME_REC_SPLIT = 1, 2, 3, 4, 5
 
 
@@ -125,6 +127,9 @@ SIGNATURES = {
     "sv_unpack_points_workspace_bytes": (c_size_t, [c_int64]),
     "sv_unpack_points": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, _P,
                                  _P, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "sv_rgbd_cloud_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "sv_rgbd_cloud": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, c_int, c_int,
+                              _P, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),

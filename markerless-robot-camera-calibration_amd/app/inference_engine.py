@@ -220,10 +220,12 @@ class InferenceEngine:
         import itertools
 
         from ..utils.packed import PackedFrame
+        from ..utils.rgbd import RGBDFrame
         from .pipeline import HostFrameStream, PackedFrameStream
 
-        def is_packed(item):
-            return isinstance(item, PackedFrame) or (isinstance(item, tuple) and isinstance(item[0], PackedFrame))
+        def is_packed(item):  # an RGBDFrame (utils/rgbd.py) has a PackedFrame's members and takes the same stream
+            kinds = (PackedFrame, RGBDFrame)
+            return isinstance(item, kinds) or (isinstance(item, tuple) and isinstance(item[0], kinds))
 
         def run():
             # packed frames - PackedFrame, (PackedFrame, box) or (PackedFrame, box, color) items - take the packed stream and

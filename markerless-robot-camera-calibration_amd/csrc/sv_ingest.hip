@@ -6,8 +6,8 @@
 // Three launches, no atomics, no memset, no read-back:
 //   unpack_count_kernel : one record per thread, keep flag -> ballot + popcount per wave, the four wave totals of a tile
 //                         through LDS -> tile_count[tile]
-//   unpack_scan_kernel  : ONE workgroup, exclusive scan of the tile counts in place (it loops when there are more tiles
-//                         than threads), total -> count[0]
+//   compact_scan_kernel : sv_compact.h.  ONE workgroup, exclusive scan of the tile counts in place (it loops when there
+//                         are more tiles than threads), total -> count[0]
 //   unpack_write_kernel : recomputes the keep flags, row = tile base + waves before + lanes before (the ordered-write
 //                         idiom of elim_table_kernel and the ball query), then decodes the colour of the kept records only
 //
@@ -18,10 +18,11 @@
 // call of either form took the 24 us the host needs to issue it (tools/ingest_timing.py), so the second path
 // would only have been more to test.
 #include "sv_common.h"
+#include "sv_compact.h"
 
 namespace sv {
 
-constexpr int UP_THREADS = 256;  // records per tile, and the threads of the scan's one workgroup
+constexpr int UP_THREADS = CP_THREADS;  // records per tile, and the threads of the scan's one workgroup
 constexpr int UP_WAVES = UP_THREADS / 64;
 constexpr int64_t UP_MAX_RECORDS = 1 << 24;
 constexpr int64_t UP_MAX_STEP = 4096;
@@ -94,37 +95,6 @@ __global__ __launch_bounds__(UP_THREADS) void unpack_count_kernel(UnpackArgs a, 
     for (int k = 0; k < UP_WAVES; ++k) s += wave_cnt[k];
     tile_count[blockIdx.x] = s;
   }
-}
-
-// tile_count[t] -> the number kept in the tiles before t, in place; count[0] = the number kept
-__global__ __launch_bounds__(UP_THREADS) void unpack_scan_kernel(int32_t* __restrict__ tile_count, int tiles,
-                                                                  int64_t* __restrict__ count) {
-  __shared__ int wave_sum[UP_WAVES];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int carry = 0;  // at most 2^24
-  for (int base = 0; base < tiles; base += UP_THREADS) {
-    const int t = base + threadIdx.x;
-    const int c = t < tiles ? tile_count[t] : 0;
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_sum[wid] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < UP_WAVES; ++k) {
-      const int s = wave_sum[k];
-      before += k < wid ? s : 0;
-      total += s;
-    }
-    if (t < tiles) tile_count[t] = carry + before + incl - c;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) count[0] = carry;
 }
 
 __global__ __launch_bounds__(UP_THREADS) void unpack_write_kernel(UnpackArgs a, const int32_t* __restrict__ tile_base,
@@ -237,7 +207,7 @@ int sv_unpack_points(const uint8_t* data, int64_t data_bytes, int64_t n_records,
   uint32_t* pbits = (uint32_t*)points;  // coordinates move as bits
   hipLaunchKernelGGL(unpack_count_kernel, dim3((unsigned)tiles), dim3(UP_THREADS), 0, stream, a, tile_count);
   SV_LAUNCH_CHECK();
-  hipLaunchKernelGGL(unpack_scan_kernel, dim3(1), dim3(UP_THREADS), 0, stream, tile_count, tiles, count);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(UP_THREADS), 0, stream, tile_count, tiles, count);
   SV_LAUNCH_CHECK();
   hipLaunchKernelGGL(unpack_write_kernel, dim3((unsigned)tiles), dim3(UP_THREADS), 0, stream, a, tile_count, lut, pbits, rgb,
                      src);

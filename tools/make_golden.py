@@ -729,6 +729,88 @@ def gen_labels(rng):
     return out
 
 
+def _ycb_functions():
+    """The reference's im2col, filterDiscontinuities, registerDepthMap and registeredDepthMapToPointCloud, lifted out of
+    scripts/ycb_generate_point_cloud.py with `ast`: the script reads sys.argv and imports h5py, imageio and open3d at module
+    level, so it cannot be imported.  `np.float` (removed from numpy) is aliased for the last of them."""
+    import ast
+    import math
+
+    path = os.path.join(REF, "scripts", "ycb_generate_point_cloud.py")
+    tree = ast.parse(open(path).read(), path)
+    names = ("im2col", "filterDiscontinuities", "registerDepthMap", "registeredDepthMapToPointCloud")
+    body = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in names]
+    assert sorted(n.name for n in body) == sorted(names)
+    if not hasattr(np, "float"):
+        np.float = float
+    scope = {"np": np, "math": math}
+    exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), scope)
+    return [scope[n] for n in names[1:]]
+
+
+def _register_one(one, v, u, depth_K, color_K, Hm, register, color):
+    """registerDepthMap of a map that holds the single pixel (v, u): only that row and column are handed over, with the
+    principal point moved accordingly, which leaves every term of the function's arithmetic as it was"""
+    K = depth_K.copy()
+    K[0, 2] -= u
+    K[1, 2] -= v
+    return register(one[v:v + 1, u:u + 1], color, K, color_K, Hm)
+
+
+def gen_rgbd(rng):
+    """The reference's RGB-D steps (scripts/ycb_generate_point_cloud.py:127-274) on two designed frames.
+    (a) filterDiscontinuities on a 480 x 640 uint16 map (the function hard-codes that size): a ramp 8000 + 2u + v, a
+    120 x 150 block at 5000, a 20 x 60 hole and 0.1 % single-pixel holes; no per-pixel noise, so that the array compresses.
+    Stored: the input and the flat indices of the pixels the filter newly zeroed.
+    (b) registerDepthMap + registeredDepthMapToPointCloud(organized=False, mask) of a 48 x 64 depth map (float64 metres,
+    two depth layers so that several depth pixels land on one colour pixel) into a 60 x 80 colour image, cameras 1.7 degrees
+    rotated and 25 mm apart; a 10 % mask.  Stored: every input, the registered map and the cloud."""
+    filt, register, to_cloud = _ycb_functions()
+    # ---- (a)
+    v, u = np.mgrid[0:480, 0:640]
+    depth = (8000 + 2 * u + v).astype(np.uint16)
+    depth[200:320, 300:450] = 5000
+    depth[60:80, 100:160] = 0
+    holes = rng.permutation(480 * 640)[: 480 * 640 // 1000]
+    depth.reshape(-1)[holes] = 0
+    out = np.asarray(filt(depth))
+    assert out.shape == depth.shape and np.all((out == depth) | (out == 0))
+    zeroed = np.nonzero((out.reshape(-1) == 0) & (depth.reshape(-1) != 0))[0]
+    data = dict(a_depth=depth, a_zeroed=zeroed.astype(np.int32), a_filter_size=np.int64(7), a_filter_thresh=np.int64(1000))
+    # ---- (b)
+    Hd, Wd, Hc, Wc = 48, 64, 60, 80
+    v, u = np.mgrid[0:Hd, 0:Wd]
+    raw = (900 + 3 * u + 2 * v).astype(np.uint16)  # millimetres: a tilted wall ...
+    raw[10:30, 15:40] = 450 + rng.integers(0, 20, size=(20, 25))  # ... and a box in front of it, which the baseline shifts
+    raw.reshape(-1)[rng.permutation(Hd * Wd)[:150]] = 0
+    depth_m = raw.astype(np.float64) * 0.001  # what the script hands to registerDepthMap
+    depth_K = np.array([[58.0, 0, 31.5], [0, 58.5, 23.5], [0, 0, 1]])
+    color_K = np.array([[52.0, 0, 40.2], [0, 52.5, 29.7], [0, 0, 1]])  # shorter than the depth camera: pixels collide
+    a = np.deg2rad(1.7)
+    Hm = np.eye(4)
+    Hm[:3, :3] = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    Hm[:3, 3] = (0.025, 0.001, -0.002)
+    color = rng.integers(0, 256, size=(Hc, Wc, 3), dtype=np.uint8)
+    mask = (rng.random((Hc, Wc)) < 0.10).astype(np.uint8)
+    registered = register(depth_m, color, depth_K, color_K, Hm)
+    cloud = to_cloud(registered, color, color_K, organized=False, mask=mask)
+    assert registered.dtype == np.float64 and cloud.dtype == np.float64 and cloud.shape[0] == 1
+    # how many depth pixels land on every colour pixel (the reference keeps no such count): each depth pixel registered
+    # alone marks the pixel it lands on; one call per depth row keeps this quick, the row's pixels told apart by their Z
+    hits = np.zeros((Hc, Wc), dtype=np.int32)
+    for vv in range(Hd):
+        for uu in range(Wd):
+            if depth_m[vv, uu] == 0:
+                continue
+            one = np.zeros_like(depth_m)
+            one[vv, uu] = depth_m[vv, uu]
+            hits += _register_one(one, vv, uu, depth_K, color_K, Hm, register, color) > 0
+    assert np.array_equal(hits > 0, registered > 0)
+    data.update(b_depth=raw, b_depth_scale=np.float64(0.001), b_depth_K=depth_K, b_color_K=color_K, b_H=Hm, b_color=color,
+                b_mask=mask, b_registered=registered, b_cloud=cloud[0], b_hits=hits)
+    return data
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
@@ -737,7 +819,7 @@ def main():
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
                            ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110),
                            ("pose_losses", gen_pose_losses, 111), ("augmentation", gen_augmentation, 112),
-                           ("labels", gen_labels, 113)]:
+                           ("labels", gen_labels, 113), ("rgbd_ycb", gen_rgbd, 114)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))

@@ -322,8 +322,9 @@ int sv_affine_act(const float* in, int64_t in_ld, int C, int64_t V, const float*
  *    :40-56 normalize_points; callers app/inference_engine.py:396-404,440-444,470-488)
  * ------------------------------------------------------------------------------------------- */
 /* Column statistics of x[N][C], C <= 4: col_min[C], col_max[C] (exact), col_sum[C] (float64, deterministic order) and,
- * when max_row_norm is given, max over rows of the float32 norm of (row - sub) in numpy's order
- * sqrt(((x0-s0)^2 + (x1-s1)^2) + (x2-s2)^2).  workspace: sv_col_stats_workspace_bytes(N). */
+ * when max_row_norm is given (it needs sub), max over rows of the float32 norm of (row - sub) over all C columns,
+ * 1 <= C <= 4, in numpy's order sqrt((((x0-s0)^2 + (x1-s1)^2) + (x2-s2)^2) + (x3-s3)^2), float32 without contraction.
+ * workspace: sv_col_stats_workspace_bytes(N). */
 size_t sv_col_stats_workspace_bytes(int64_t N);
 int sv_col_stats(const float* x, int64_t ld, int64_t N, int C, const float* sub, void* workspace, size_t workspace_bytes,
                  float* col_min, float* col_max, double* col_sum, float* max_row_norm, sv_stream_t stream);
@@ -369,9 +370,9 @@ int sv_key_point_predictions(const float* logits, int64_t ld, int C, int64_t N, 
 int sv_key_point_predictions_batched(const float* logits, int64_t ld, int C, const int64_t* seg_start_host, int G, float conf_th,
                                      void* workspace, size_t workspace_bytes, float* prob, int64_t* idx, int32_t* selected,
                                      sv_stream_t stream);
-/* idx[j] = row of the j-th largest x[i * ld], i < N, j < k <= 64 (ties: the lower row first; -1 when N < k; NaN orders
- * above +inf as in torch.sort) - the `out[:, 1].sort(descending=True)[1][:8]` of utils/output.py:45-64 get_pred_center
- * without sorting N votes.  workspace: sv_topk_workspace_bytes(N, k). */
+/* idx[j] = row of the j-th largest x[i * ld], i < N, j < k <= 64 (ties: the lower row first, -0.0 and +0.0 tie; -1 when
+ * N < k; every NaN, whatever its sign and payload, orders above +inf as in torch.sort, NaNs among themselves by row) - the
+ * `out[:, 1].sort(descending=True)[1][:8]` of utils/output.py:45-64 get_pred_center without sorting N votes.  workspace: sv_topk_workspace_bytes(N, k). */
 size_t sv_topk_workspace_bytes(int64_t N, int k);
 int sv_topk_indices(const float* x, int64_t ld, int64_t N, int k, void* workspace, size_t workspace_bytes, int64_t* idx,
                     sv_stream_t stream);

@@ -116,9 +116,17 @@ __device__ __forceinline__ int hash_find(const uint64_t* __restrict__ tkeys, con
 }
 
 // Packed top-k key of sv_topk_indices / sv_segment_topk: order-preserving value bits << 32 | ~index, so the largest key is
-// the largest value at the lowest index and keys of distinct indices are distinct.
+// the largest value at the lowest index and keys of distinct indices are distinct.  Values that compare equal share one
+// key class, so only the index orders them: every NaN, whatever its sign and payload, takes the class 0xffc00000 (the
+// canonical quiet NaN's) above +inf's 0xff800000 (torch.sort places NaN first), and -0.0 takes the class of +0.0.  Integer
+// tests only: the result does not depend on the denormal mode.  The lowest class is -inf's 0x007fffff and the highest is
+// the NaNs', so a real key is neither 0 ("nothing left") nor ~0 (the selection loops' "below this" start value).
 __device__ __forceinline__ unsigned long long topk_key(float v, unsigned idx) {
   unsigned u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u)
+    u = 0x7fc00000u;  // NaN
+  else if (u == 0x80000000u)
+    u = 0u;  // -0.0
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - idx);
 }

@@ -113,7 +113,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
 
 // ---- A11 preprocessing (utils/preprocess.py:8-56) on device rows -----------------------------------------------------
 // column statistics of x[N][C] (C <= 4): per column min, max (exact), sum (float64), and - when `sub` is given - the
-// maximum over rows of the float32 norm sqrt(((x0-s0)^2 + (x1-s1)^2) + (x2-s2)^2), numpy's np.linalg.norm order.
+// maximum over rows of the float32 norm of (row - sub) over all C columns, squares added in column order
+// sqrt((((x0-s0)^2 + (x1-s1)^2) + (x2-s2)^2) + (x3-s3)^2) without contraction: numpy's np.linalg.norm(axis=1) order.
 // Stage 1: every workgroup reduces a contiguous slab of rows to one record; stage 2: one workgroup reduces the records
 // in slab order (deterministic: no atomics).
 constexpr int STAT_REC = 16;  // doubles per record: min[4], max[4], sum[4], normmax, pad
@@ -140,8 +141,13 @@ __global__ __launch_bounds__(256) void col_stats_partial_kernel(const float* __r
       sm[c] += (double)v[c];
     }
     if (sub) {
-      const float a = v[0] - sub[0], b = v[1] - sub[1], d = (C > 2) ? v[2] - sub[2] : 0.0f;
-      nmax = nan_max(nmax, sqrtf((a * a + b * b) + d * d));
+      const float d0 = v[0] - sub[0];
+      float s = d0 * d0;
+      for (int c = 1; c < C; ++c) {
+        const float d = v[c] - sub[c];
+        s = s + d * d;
+      }
+      nmax = nan_max(nmax, sqrtf(s));
     }
   }
   // wave reduction by shuffles, then across the four waves through LDS
@@ -352,7 +358,7 @@ int sv_col_stats(const float* x, int64_t ld, int64_t N, int C, const float* sub,
   hipStream_t stream = (hipStream_t)stream_;
   SV_CHECK_ARG(N >= 1 && C >= 1 && C <= 4 && ld >= C, "bad shape (1 <= C <= 4, N >= 1)");
   SV_CHECK_ARG(x && workspace && col_min && col_max && col_sum, "null pointer");
-  SV_CHECK_ARG(!max_row_norm || (sub && C >= 2), "max_row_norm needs sub and at least two columns");
+  SV_CHECK_ARG(!max_row_norm || sub, "max_row_norm needs sub");
   int64_t blocks = (N + 4095) / 4096;
   if (blocks > 1024) blocks = 1024;
   const int64_t rows_per_block = (N + blocks - 1) / blocks;

@@ -45,3 +45,24 @@ def test_oracle_clusters_match_sklearn_single_linkage():
         u, c = np.unique(sk, return_counts=True)
         if (c == c.max()).sum() == 1:  # a unique largest cluster: the reference's answer is well defined
             assert np.array_equal(O.largest_cluster(pts, 0.06), np.where(sk == u[c.argmax()])[0])
+
+
+def test_oracle_leaves_rows_with_nan_or_infinity_as_singletons():
+    """d < dist is false for a NaN distance (NaN coordinates, inf - inf) and for an infinite one: a non-finite row joins
+    nothing, not even an identical row, and the finite points cluster as if it were absent - what the device path
+    (tests/test_gpu_cluster.py) is held to"""
+    import post_helpers as P
+    from oracle import sv_oracle as O
+
+    pts, bad = P.non_finite_scene()
+    with np.errstate(invalid="ignore"):
+        root = O.single_linkage_roots(pts, 0.5)
+    want = np.arange(len(pts))
+    want[[5, 9]], want[[30, 31]], want[39] = 0, 2, 12
+    assert np.array_equal(root, want)
+    assert all(root[r] == r and (root == r).sum() == 1 for r in bad)
+    finite = np.setdiff1d(np.arange(len(pts)), bad)
+    alone = O.single_linkage_roots(pts[finite], 0.5)
+    assert np.array_equal(finite[alone], root[finite])
+    with np.errstate(invalid="ignore"):
+        assert O.largest_cluster(pts, 0.5).tolist() == [0, 5, 9]

@@ -477,8 +477,8 @@ int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const floa
  *   shared == 0: P independent problems.  init_T double[P][16] (device) or NULL = identities; out_T double[P][16];
  *   out_stats double[P][3] = {fitness, rmse, updates} (or NULL).  Every problem has its own state and stops on its own;
  *   problem p's out_T and out_stats are, bit for bit, those of sv_icp_point2point / sv_icp_point2plane on
- *   (src, target p, init_T[p]) - the kernels share the single calls' device functions - whatever else is in the call
- *   and whatever its order.
+ *   (src, target p, init_T[p]) - the single calls are the P = 1 independent case - whatever else is in the call and
+ *   whatever its order.
  *
  *   shared == 1: one transform T for all problems, minimising the pooled objective.  init_T double[16] or NULL; out_T
  *   double[16]; out_stats double[3 + 2 P] = pooled {fitness, rmse, updates}, then {fitness_p, rmse_p} of the last

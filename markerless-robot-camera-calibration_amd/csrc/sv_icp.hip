@@ -9,16 +9,17 @@
 // The iteration loop runs on the device side of the stream: a `state` record carries the current transform, the
 // previous fitness / rmse and a converged flag that turns the remaining launches into no-ops (no host read-backs).
 //
-// sv_icp_point2plane shares the search, the state record and the loop; only step (2) differs (icp_plane_update_kernel:
-// the 6x6 normal equations of the linearised point-to-plane residual, Cholesky, T <- U T).  The target normals come from
-// sv_estimate_normals (sv_normals.hip) or from the caller.
+// sv_icp_point2plane shares the search, the state record and the loop; only step (2) differs (icp_plane_sums /
+// icp_plane_step: the 6x6 normal equations of the linearised point-to-plane residual, Cholesky, T <- U T).  The target
+// normals come from sv_estimate_normals (sv_normals.hip) or from the caller.
 //
 // N3c, sv_icp_batched: P problems (one source cloud, P target clouds) per launch - the search on a grid of
-// (ceil(S / 256), P), one update workgroup per problem.  The kernels of the single calls and of the batch are thin
-// wrappers round the same device functions (icp_nn_search, icp_p2p_sums / icp_p2p_step, icp_plane_sums /
-// icp_plane_step), so a problem of an independent batch runs the single call's arithmetic in the single call's order.
-// In shared mode (one transform for all problems) the update workgroups write their totals to the workspace and a
-// one-wave tail kernel adds them in ascending problem order and takes the step on the pooled sums.
+// (ceil(S / 256), P), one update workgroup per problem.  There is one host routine (icp_run) and one init, search and
+// finish kernel: the single calls are the P = 1 independent case (offsets {0, T}, no pre).  Only the update of that case
+// keeps kernels of its own (icp_update_kernel, icp_plane_update_kernel: thin wrappers, as the batch's, round
+// icp_p2p_sums / icp_p2p_step and icp_plane_sums / icp_plane_step, measurably faster without the problem index), so a
+// problem of an independent batch runs the single call's arithmetic in the single call's order.  In shared mode (one transform for all problems) the update workgroups write their totals to the
+// workspace and a one-wave tail kernel adds them in ascending problem order and takes the step on the pooled sums.
 #include "sv_common.h"
 #include "sv_dense_math.h"
 
@@ -84,13 +85,6 @@ __device__ __forceinline__ void icp_nn_search(const float* __restrict__ src, int
     nn[i] = ok ? bi : -1;
     d2out[i] = best;
   }
-}
-
-__global__ __launch_bounds__(256) void icp_nn_kernel(const float* __restrict__ src, int S, const float* __restrict__ tgt,
-                                                      int T, const IcpState* __restrict__ st, float max_d2,
-                                                      int32_t* __restrict__ nn, float* __restrict__ d2out) {
-  __shared__ float tile[NN_TILE * 3];
-  icp_nn_search(src, S, nullptr, tgt, T, st, max_d2, nn, d2out, tile);
 }
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -179,6 +173,7 @@ __device__ __forceinline__ void icp_p2p_step(IcpState* __restrict__ st, const do
   st->iterations += 1;
 }
 
+// the update of a single call (one problem, no pre); a batch goes through icp_batch_update_kernel
 __global__ __launch_bounds__(1024) void icp_update_kernel(const float* __restrict__ src, int S,
                                                            const float* __restrict__ tgt,
                                                            const int32_t* __restrict__ nn,
@@ -205,19 +200,8 @@ __device__ __forceinline__ void icp_init_state(IcpState* st, const double* init_
   }
 }
 
-__global__ void icp_init_kernel(IcpState* st, const double* init_T) { icp_init_state(st, init_T); }
-
-__global__ void icp_finish_kernel(const IcpState* st, double* out_T, double* out_stats) {
-  if (threadIdx.x < 16) out_T[threadIdx.x] = st->T[threadIdx.x];
-  if (threadIdx.x == 0 && out_stats) {
-    out_stats[0] = st->fitness;
-    out_stats[1] = st->rmse;
-    out_stats[2] = (double)st->iterations;
-  }
-}
-
 // ---- point-to-plane update (sv_icp_point2plane) -------------------------------------------------------------------
-// Same evaluation as icp_update_kernel (inliers of icp_nn_kernel, fitness, rmse, stop rule); the update linearises the
+// Same evaluation as icp_p2p_step (inliers of icp_nn_search, fitness, rmse, stop rule); the update linearises the
 // rotation: per inlier r = (p - q).n, J = [p x n, n], A = sum J J^T (upper triangle, 21 values), b = sum J r, solved by
 // a 6x6 Cholesky in float64.  PL_ACC values per thread are summed over the wave by shuffles, then over the 8 waves in
 // ascending order, one thread per sum, through LDS: a fixed order, so repeated runs give the same bits (and thread 0's
@@ -506,99 +490,16 @@ __global__ void icp_batch_finish_kernel(const IcpState* states, const double* ps
   }
 }
 
-}  // namespace sv
-
-using namespace sv;
-
-extern "C" {
-
-size_t sv_icp_workspace_bytes(int64_t S) { return align_up(sizeof(IcpState), 256) + align_up((size_t)S * 4, 256) * 2 + 1024; }
-
-int sv_icp_point2point(const float* src, int64_t S, const float* tgt, int64_t T, const double* init_T,
-                       double max_distance, int max_iterations, double rel_fitness, double rel_rmse, void* workspace,
-                       size_t workspace_bytes, double* out_T, double* out_stats, sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SV_CHECK_ARG(S >= 3 && T >= 1 && S < (1 << 24) && T < (1 << 24), "need at least 3 source points and 1 target point");
-  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0, "bad parameters");
-  SV_CHECK_ARG(src && tgt && out_T && workspace, "null pointer");
-  Workspace ws(workspace, workspace_bytes);
-  IcpState* st = ws.take<IcpState>(1);
-  int32_t* nn = ws.take<int32_t>(S);
-  float* d2 = ws.take<float>(S);
-  if (!ws.ok) {
-    set_error("sv_icp_point2point: workspace too small");
-    return SV_ERR_WORKSPACE;
-  }
-  hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, stream, st, init_T);
-  const float max_d2 = (float)(max_distance * max_distance);
-  const unsigned nb = (unsigned)((S + 255) / 256);
-  // evaluation 0 .. max_iterations: each update is followed by a re-evaluation, the last one only evaluates
-  for (int it = 0; it <= max_iterations; ++it) {
-    hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(256), 0, stream, src, (int)S, tgt, (int)T, st, max_d2, nn, d2);
-    hipLaunchKernelGGL(icp_update_kernel, dim3(1), dim3(1024), 0, stream, src, (int)S, tgt, nn, d2, st, rel_fitness,
-                       rel_rmse, it == max_iterations ? 1 : 0);
-  }
-  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, stream, st, out_T, out_stats);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-size_t sv_icp_point2plane_workspace_bytes(int64_t S) { return sv_icp_workspace_bytes(S); }
-
-int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const float* tgt_normals, int64_t T,
-                       const double* init_T, double max_distance, int max_iterations, double rel_fitness,
-                       double rel_rmse, void* workspace, size_t workspace_bytes, double* out_T, double* out_stats,
-                       sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SV_CHECK_ARG(S >= 3 && T >= 1 && S < (1 << 24) && T < (1 << 24), "need at least 3 source points and 1 target point");
-  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0, "bad parameters");
-  SV_CHECK_ARG(src && tgt && tgt_normals && out_T && workspace, "null pointer");
-  Workspace ws(workspace, workspace_bytes);
-  IcpState* st = ws.take<IcpState>(1);
-  int32_t* nn = ws.take<int32_t>(S);
-  float* d2 = ws.take<float>(S);
-  if (!ws.ok) {
-    set_error("sv_icp_point2plane: workspace too small");
-    return SV_ERR_WORKSPACE;
-  }
-  hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, stream, st, init_T);
-  const float max_d2 = (float)(max_distance * max_distance);
-  const unsigned nb = (unsigned)((S + 255) / 256);
-  for (int it = 0; it <= max_iterations; ++it) {
-    hipLaunchKernelGGL(icp_nn_kernel, dim3(nb), dim3(256), 0, stream, src, (int)S, tgt, (int)T, st, max_d2, nn, d2);
-    hipLaunchKernelGGL(icp_plane_update_kernel, dim3(1), dim3(PL_THREADS), 0, stream, src, (int)S, tgt, tgt_normals, nn, d2, st,
-                       rel_fitness, rel_rmse, it == max_iterations ? 1 : 0);
-  }
-  hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, stream, st, out_T, out_stats);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-size_t sv_icp_batched_workspace_bytes(int64_t S, int P) {
-  if (S < 0 || P < 0) return 0;
-  const size_t p = (size_t)P;
-  return align_up(p * sizeof(IcpState), 256) + align_up(p * (size_t)S * 4, 256) * 2 +
-         align_up(p * ICP_PART * sizeof(double), 256) + align_up(p * 2 * sizeof(double), 256) + 1024;
-}
-
-int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* tgt, const float* tgt_normals,
-                   const int64_t* tgt_offsets, int P, const double* init_T, int shared, double max_distance,
-                   int max_iterations, double rel_fitness, double rel_rmse, void* workspace, size_t workspace_bytes,
-                   double* out_T, double* out_stats, sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SV_CHECK_ARG(P >= 1 && P <= ICP_MAX_PROBLEMS, "need 1 to 64 problems");
-  SV_CHECK_ARG(S >= 3 && S < (1 << 24), "need 3 to 2^24 - 1 source points");
-  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0 && (shared == 0 || shared == 1), "bad parameters");
-  SV_CHECK_ARG(src && tgt && tgt_offsets && out_T && workspace, "null pointer");
-  SV_CHECK_ARG(tgt_offsets[0] == 0, "tgt_offsets must start at 0");
-  IcpOffsets off;
-  off.v[0] = 0;
-  for (int p = 0; p < P; ++p) {
-    const int64_t T = tgt_offsets[p + 1] - tgt_offsets[p];
-    SV_CHECK_ARG(T >= 1 && T < (1 << 24), "every problem needs 1 to 2^24 - 1 target points (ascending tgt_offsets)");
-    off.v[p + 1] = (int32_t)tgt_offsets[p + 1];  // <= 64 * 2^24
-  }
-  for (int p = P + 1; p <= ICP_MAX_PROBLEMS; ++p) off.v[p] = off.v[P];
+// The one launch sequence: init, (max_iterations + 1) rounds of search + update (+ the tail in shared mode), finish -
+// 2 + 2 (max_iterations + 1) launches, 3 per round in shared mode, no read-back and no host wait.  Evaluation
+// 0 .. max_iterations: each update is followed by a re-evaluation, the last round only evaluates.  The arguments are
+// checked by the entry point `who`, whose name the errors carry.  One independent problem without pre (the single calls)
+// takes its update through icp_update_kernel / icp_plane_update_kernel, which measure about 2 us per launch faster than
+// the batch update kernels at P = 1 and give the same bits; init, search and finish are the batch's.
+static int icp_run(const char* who, const float* src, int64_t S, const double* pre, const float* tgt,
+                   const float* tgt_normals, const IcpOffsets& off, int P, const double* init_T, int shared,
+                   double max_distance, int max_iterations, double rel_fitness, double rel_rmse, void* workspace,
+                   size_t workspace_bytes, double* out_T, double* out_stats, hipStream_t stream) {
   Workspace ws(workspace, workspace_bytes);
   IcpState* states = ws.take<IcpState>(P);
   int32_t* nn = ws.take<int32_t>((size_t)P * S);
@@ -606,19 +507,25 @@ int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* 
   double* part = ws.take<double>((size_t)P * ICP_PART);
   double* pstats = ws.take<double>((size_t)P * 2);
   if (!ws.ok) {
-    set_error("sv_icp_batched: workspace too small");
+    set_error("%s: workspace too small", who);
     return SV_ERR_WORKSPACE;
   }
   const unsigned nstates = shared ? 1u : (unsigned)P;
+  const bool single = P == 1 && !shared && !pre;
   hipLaunchKernelGGL(icp_batch_init_kernel, dim3(nstates), dim3(64), 0, stream, states, init_T);
   const float max_d2 = (float)(max_distance * max_distance);
   const dim3 grid_nn((unsigned)((S + 255) / 256), (unsigned)P);
-  // the single calls' loop; in shared mode a third launch per round takes the step on the pooled sums
   for (int it = 0; it <= max_iterations; ++it) {
     const int last = it == max_iterations ? 1 : 0;
     hipLaunchKernelGGL(icp_batch_nn_kernel, grid_nn, dim3(256), 0, stream, src, (int)S, pre, tgt, off, states, shared,
                        max_d2, nn, d2);
-    if (tgt_normals)
+    if (single && tgt_normals)
+      hipLaunchKernelGGL(icp_plane_update_kernel, dim3(1), dim3(PL_THREADS), 0, stream, src, (int)S, tgt, tgt_normals, nn,
+                         d2, states, rel_fitness, rel_rmse, last);
+    else if (single)
+      hipLaunchKernelGGL(icp_update_kernel, dim3(1), dim3(1024), 0, stream, src, (int)S, tgt, nn, d2, states, rel_fitness,
+                         rel_rmse, last);
+    else if (tgt_normals)
       hipLaunchKernelGGL(icp_batch_plane_update_kernel, dim3(P), dim3(PL_THREADS), 0, stream, src, (int)S, pre, tgt,
                          tgt_normals, off, nn, d2, states, shared, part, rel_fitness, rel_rmse, last);
     else
@@ -633,8 +540,81 @@ int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* 
   }
   hipLaunchKernelGGL(icp_batch_finish_kernel, dim3(nstates), dim3(64), 0, stream, states, pstats, P, shared, out_T,
                      out_stats);
-  SV_LAUNCH_CHECK();
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s: hipGetLastError() -> %s", who, hipGetErrorString(e));
+    return SV_ERR_HIP;
+  }
   return SV_OK;
+}
+
+// one problem with T target points: rows 0 .. T - 1 (the unused entries repeat the end, as sv_icp_batched's do)
+static IcpOffsets icp_single_offsets(int64_t T) {
+  IcpOffsets off;
+  off.v[0] = 0;
+  for (int p = 1; p <= ICP_MAX_PROBLEMS; ++p) off.v[p] = (int32_t)T;
+  return off;
+}
+
+}  // namespace sv
+
+using namespace sv;
+
+extern "C" {
+
+size_t sv_icp_workspace_bytes(int64_t S) { return align_up(sizeof(IcpState), 256) + align_up((size_t)S * 4, 256) * 2 + 1024; }
+
+int sv_icp_point2point(const float* src, int64_t S, const float* tgt, int64_t T, const double* init_T,
+                       double max_distance, int max_iterations, double rel_fitness, double rel_rmse, void* workspace,
+                       size_t workspace_bytes, double* out_T, double* out_stats, sv_stream_t stream_) {
+  SV_CHECK_ARG(S >= 3 && T >= 1 && S < (1 << 24) && T < (1 << 24), "need at least 3 source points and 1 target point");
+  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0, "bad parameters");
+  SV_CHECK_ARG(src && tgt && out_T && workspace, "null pointer");
+  return icp_run(__func__, src, S, nullptr, tgt, nullptr, icp_single_offsets(T), 1, init_T, 0, max_distance,
+                 max_iterations, rel_fitness, rel_rmse, workspace, workspace_bytes, out_T, out_stats,
+                 (hipStream_t)stream_);
+}
+
+size_t sv_icp_point2plane_workspace_bytes(int64_t S) { return sv_icp_workspace_bytes(S); }
+
+int sv_icp_point2plane(const float* src, int64_t S, const float* tgt, const float* tgt_normals, int64_t T,
+                       const double* init_T, double max_distance, int max_iterations, double rel_fitness,
+                       double rel_rmse, void* workspace, size_t workspace_bytes, double* out_T, double* out_stats,
+                       sv_stream_t stream_) {
+  SV_CHECK_ARG(S >= 3 && T >= 1 && S < (1 << 24) && T < (1 << 24), "need at least 3 source points and 1 target point");
+  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0, "bad parameters");
+  SV_CHECK_ARG(src && tgt && tgt_normals && out_T && workspace, "null pointer");
+  return icp_run(__func__, src, S, nullptr, tgt, tgt_normals, icp_single_offsets(T), 1, init_T, 0, max_distance,
+                 max_iterations, rel_fitness, rel_rmse, workspace, workspace_bytes, out_T, out_stats,
+                 (hipStream_t)stream_);
+}
+
+size_t sv_icp_batched_workspace_bytes(int64_t S, int P) {
+  if (S < 0 || P < 0) return 0;
+  const size_t p = (size_t)P;
+  return align_up(p * sizeof(IcpState), 256) + align_up(p * (size_t)S * 4, 256) * 2 +
+         align_up(p * ICP_PART * sizeof(double), 256) + align_up(p * 2 * sizeof(double), 256) + 1024;
+}
+
+int sv_icp_batched(const float* src, int64_t S, const double* pre, const float* tgt, const float* tgt_normals,
+                   const int64_t* tgt_offsets, int P, const double* init_T, int shared, double max_distance,
+                   int max_iterations, double rel_fitness, double rel_rmse, void* workspace, size_t workspace_bytes,
+                   double* out_T, double* out_stats, sv_stream_t stream_) {
+  SV_CHECK_ARG(P >= 1 && P <= ICP_MAX_PROBLEMS, "need 1 to 64 problems");
+  SV_CHECK_ARG(S >= 3 && S < (1 << 24), "need 3 to 2^24 - 1 source points");
+  SV_CHECK_ARG(max_iterations >= 0 && max_distance > 0 && (shared == 0 || shared == 1), "bad parameters");
+  SV_CHECK_ARG(src && tgt && tgt_offsets && out_T && workspace, "null pointer");
+  SV_CHECK_ARG(tgt_offsets[0] == 0, "tgt_offsets must start at 0");
+  IcpOffsets off;
+  off.v[0] = 0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t T = tgt_offsets[p + 1] - tgt_offsets[p];
+    SV_CHECK_ARG(T >= 1 && T < (1 << 24), "every problem needs 1 to 2^24 - 1 target points (ascending tgt_offsets)");
+    off.v[p + 1] = (int32_t)tgt_offsets[p + 1];  // <= 64 * 2^24
+  }
+  for (int p = P + 1; p <= ICP_MAX_PROBLEMS; ++p) off.v[p] = off.v[P];
+  return icp_run(__func__, src, S, pre, tgt, tgt_normals, off, P, init_T, shared, max_distance, max_iterations,
+                 rel_fitness, rel_rmse, workspace, workspace_bytes, out_T, out_stats, (hipStream_t)stream_);
 }
 
 }  // extern "C"

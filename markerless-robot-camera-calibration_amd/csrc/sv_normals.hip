@@ -2,7 +2,7 @@
 // KDTreeSearchParamHybrid(radius, max_nn); definitions in include/sv_hip.h).
 //
 // One wavefront per query point, four queries per 256-thread block.  The cloud is staged through LDS in tiles of 1024
-// points shared by the block's waves (brute force as icp_nn_kernel: crops have thousands of points, no grid).  Lanes
+// points shared by the block's waves (brute force as icp_nn_search: crops have thousands of points, no grid).  Lanes
 // stride over the tile; in-radius candidates are compacted in ascending index order (ballot + popcount prefix, no
 // atomics) into a per-wave LDS buffer of (distance bits, index).  Then, per wave and with no block-wide barrier:
 //   * at most max_nn candidates: the buffer is the neighbour set;

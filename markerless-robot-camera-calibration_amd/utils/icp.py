@@ -45,59 +45,13 @@ def _cad_model(cad_points, device):
     return load_cad_model(cad_points, device=device)[0] if is_path(cad_points) else cad_points
 
 
-def icp_point2point(src, tgt, init_T=None, max_distance=0.1, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
-                    device="cuda"):
-    """src [S,3], tgt [T,3] (numpy or tensors) -> (T 4x4 float64 numpy, fitness, inlier rmse, updates)."""
-    dev = torch.device(device)
-    s = torch.as_tensor(np.ascontiguousarray(src, dtype=np.float32) if not torch.is_tensor(src) else src).to(
-        device=dev, dtype=torch.float32).contiguous()
-    t = torch.as_tensor(np.ascontiguousarray(tgt, dtype=np.float32) if not torch.is_tensor(tgt) else tgt).to(
-        device=dev, dtype=torch.float32).contiguous()
-    S, T = s.shape[0], t.shape[0]
-    init = None if init_T is None else torch.as_tensor(np.ascontiguousarray(init_T, dtype=np.float64)).to(dev)
-    ws_bytes = _lib.load().sv_icp_workspace_bytes(c_int64(S))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    out_T = torch.empty(16, dtype=torch.float64, device=dev)
-    stats = torch.empty(3, dtype=torch.float64, device=dev)
-    call("sv_icp_point2point", ptr(s), c_int64(S), ptr(t), c_int64(T), ptr(init), c_double(max_distance),
-         c_int(max_iterations), c_double(rel_fitness), c_double(rel_rmse), ptr(ws), c_size_t(ws_bytes), ptr(out_T),
-         ptr(stats), stream_ptr())
-    st = stats.cpu().numpy()
-    return out_T.cpu().numpy().reshape(4, 4), float(st[0]), float(st[1]), int(st[2])
-
-
-class PointToPointMatcher:
-    """match = PointToPointMatcher(cad_points); match(ee_points, pose_initial) refines one pose (a None crop or pose
-    returns pose_initial); match.many(crops, poses) refines a list of them in one sv_icp_batched call."""
-
-    def __init__(self, cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
-        self.device = torch.device(device)
-        cad_points = _cad_model(cad_points, self.device)
-        self.cad = torch.as_tensor(np.ascontiguousarray(cad_points, dtype=np.float32)).to(device)
-        self.icp_threshold, self.max_iterations = icp_threshold, max_iterations
-
-    def __call__(self, ee_points, pose_initial):
-        if ee_points is None or pose_initial is None:
-            return pose_initial
-        T0 = get_transformation_matrix(np.asarray(pose_initial, dtype=np.float64), switch_w=False)
-        T, _, _, _ = icp_point2point(self.cad, ee_points, T0, self.icp_threshold, self.max_iterations,
-                                     device=self.device)
-        return get_pose_from_matrix(T)
-
-    def many(self, crops, poses, normals=None):
-        """[match(c, p) for c, p in zip(crops, poses)], bit for bit, with one read-back; normals are not read"""
-        return _refine_many(self.cad, crops, poses, None, float(self.icp_threshold), int(self.max_iterations),
-                            self.device)
-
-
-def get_point2point_matcher(cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
-    """-> match(ee_points, pose_initial), a PointToPointMatcher; cad_points: the model points or its file's path"""
-    return PointToPointMatcher(cad_points, icp_threshold, max_iterations, device)
+def _shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
 
 
 def _cloud(x, name, dev):
     """[N,3] numpy array or tensor -> contiguous float32 tensor on dev; the shape is checked before anything moves."""
-    shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    shape = _shape(x)
     if len(shape) != 2 or shape[1] != 3:
         raise ValueError(f"{name} must be [N, 3], got {shape}")
     if not torch.is_tensor(x):
@@ -131,7 +85,7 @@ def estimate_normals(points, radius=0.02, max_nn=30, device="cuda"):
     nearest) neighbours within radius, counts = neighbours used.  A numpy input gives numpy outputs; a CUDA tensor gives
     tensors on its device."""
     is_tensor = torch.is_tensor(points)
-    shape = tuple(points.shape) if hasattr(points, "shape") else np.shape(points)
+    shape = _shape(points)
     if len(shape) != 2 or shape[1] != 3:
         raise ValueError(f"points must be [N, 3], got {shape}")
     _check_normals_args(shape[0], radius, max_nn)
@@ -155,40 +109,92 @@ def _check_icp_args(S, T, n_normals, max_distance, max_iterations):
         raise ValueError(f"max_iterations must not be negative, got {max_iterations!r}")
 
 
-def _point2plane_enqueue(s, t, tn, init, max_distance, max_iterations, rel_fitness, rel_rmse):
-    """device tensors in, (out_T [16] float64, stats [3] float64) device tensors out, no read-back"""
+def _matrix(m, dev):
+    """None, or 4x4 matrices (numpy) -> float64 tensor on dev"""
+    return None if m is None else torch.as_tensor(np.ascontiguousarray(m, dtype=np.float64)).to(dev)
+
+
+def _icp_enqueue(s, t, tn, init, max_distance, max_iterations, rel_fitness, rel_rmse):
+    """One problem, device tensors in: tn None is sv_icp_point2point, target normals are sv_icp_point2plane.
+    -> float64 [19] device tensor (out_T 16, then fitness, rmse, updates), no read-back"""
     S, T = s.shape[0], t.shape[0]
-    ws_bytes = _lib.load().sv_icp_point2plane_workspace_bytes(c_int64(S))
+    lib = _lib.load()
+    ws_bytes = (lib.sv_icp_workspace_bytes if tn is None else lib.sv_icp_point2plane_workspace_bytes)(c_int64(S))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
-    out_T = torch.empty(16, dtype=torch.float64, device=s.device)
-    stats = torch.empty(3, dtype=torch.float64, device=s.device)
-    call("sv_icp_point2plane", ptr(s), c_int64(S), ptr(t), ptr(tn), c_int64(T), ptr(init), c_double(max_distance),
-         c_int(max_iterations), c_double(rel_fitness), c_double(rel_rmse), ptr(ws), c_size_t(ws_bytes), ptr(out_T),
-         ptr(stats), stream_ptr())
-    return out_T, stats
+    out = torch.empty(19, dtype=torch.float64, device=s.device)
+    normals = () if tn is None else (ptr(tn),)
+    call("sv_icp_point2point" if tn is None else "sv_icp_point2plane", ptr(s), c_int64(S), ptr(t), *normals, c_int64(T),
+         ptr(init), c_double(max_distance), c_int(max_iterations), c_double(rel_fitness), c_double(rel_rmse), ptr(ws),
+         c_size_t(ws_bytes), ptr(out[:16]), ptr(out[16:]), stream_ptr())
+    return out
+
+
+def _icp_single(src, tgt, tgt_normals, init_T, max_distance, max_iterations, rel_fitness, rel_rmse, device):
+    """what icp_point2point and icp_point2plane share: conversion, enqueue and the one read-back"""
+    dev = torch.device(device)
+    s, t = _cloud(src, "src", dev), _cloud(tgt, "tgt", dev)
+    tn = None if tgt_normals is None else _cloud(tgt_normals, "tgt_normals", dev)
+    out = _icp_enqueue(s, t, tn, _matrix(init_T, dev), max_distance, max_iterations, rel_fitness, rel_rmse).cpu().numpy()
+    return out[:16].reshape(4, 4), float(out[16]), float(out[17]), int(out[18])
+
+
+def icp_point2point(src, tgt, init_T=None, max_distance=0.1, max_iterations=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                    device="cuda"):
+    """src [S,3], tgt [T,3] (numpy or tensors) -> (T 4x4 float64 numpy, fitness, inlier rmse, updates)."""
+    return _icp_single(src, tgt, None, init_T, max_distance, max_iterations, rel_fitness, rel_rmse, device)
 
 
 def icp_point2plane(src, tgt, tgt_normals, init_T=None, max_distance=0.1, max_iterations=30, rel_fitness=1e-6,
                     rel_rmse=1e-6, device="cuda"):
     """src [S,3], tgt [T,3], tgt_normals [T,3] (numpy or tensors) -> (T 4x4 float64 numpy, fitness, inlier rmse,
     updates), as icp_point2point but minimising the distance to the target's tangent planes."""
-    dev = torch.device(device)
-    shapes = [tuple(x.shape) if hasattr(x, "shape") else np.shape(x) for x in (src, tgt, tgt_normals)]
+    shapes = [_shape(x) for x in (src, tgt, tgt_normals)]
     for name, shape in zip(("src", "tgt", "tgt_normals"), shapes):
         if len(shape) != 2 or shape[1] != 3:
             raise ValueError(f"{name} must be [N, 3], got {shape}")
     _check_icp_args(shapes[0][0], shapes[1][0], shapes[2][0], max_distance, max_iterations)
     if init_T is not None and np.shape(init_T) != (4, 4):
         raise ValueError(f"init_T must be 4x4, got {np.shape(init_T)}")
-    s, t, tn = _cloud(src, "src", dev), _cloud(tgt, "tgt", dev), _cloud(tgt_normals, "tgt_normals", dev)
-    init = None if init_T is None else torch.as_tensor(np.ascontiguousarray(init_T, dtype=np.float64)).to(dev)
-    out_T, stats = _point2plane_enqueue(s, t, tn, init, float(max_distance), int(max_iterations), float(rel_fitness),
-                                        float(rel_rmse))
-    st = stats.cpu().numpy()
-    return out_T.cpu().numpy().reshape(4, 4), float(st[0]), float(st[1]), int(st[2])
+    return _icp_single(src, tgt, tgt_normals, init_T, float(max_distance), int(max_iterations), float(rel_fitness),
+                       float(rel_rmse), device)
 
 
-class PointToPlaneMatcher:
+class _Matcher:
+    """What the two matchers share: the CAD model on the device, the threshold and the iteration cap."""
+
+    def __init__(self, cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
+        self.device = torch.device(device)
+        self.cad = _cloud(_cad_model(cad_points, self.device), "cad_points", self.device)
+        self.icp_threshold, self.max_iterations = icp_threshold, max_iterations
+
+    def _refine(self, tgt, pose_initial, tn):
+        """tgt, tn: device tensors (tn None: point-to-point) -> the refined pose, with one read-back"""
+        T0 = get_transformation_matrix(np.asarray(pose_initial, dtype=np.float64), switch_w=False)
+        T = _icp_enqueue(self.cad, tgt, tn, _matrix(T0, self.device), self.icp_threshold, self.max_iterations, 1e-6, 1e-6)
+        return get_pose_from_matrix(T[:16].cpu().numpy().reshape(4, 4))
+
+
+class PointToPointMatcher(_Matcher):
+    """match = PointToPointMatcher(cad_points); match(ee_points, pose_initial) refines one pose (a None crop or pose
+    returns pose_initial); match.many(crops, poses) refines a list of them in one sv_icp_batched call."""
+
+    def __call__(self, ee_points, pose_initial):
+        if ee_points is None or pose_initial is None:
+            return pose_initial
+        return self._refine(_cloud(ee_points, "tgt", self.device), pose_initial, None)
+
+    def many(self, crops, poses, normals=None):
+        """[match(c, p) for c, p in zip(crops, poses)], bit for bit, with one read-back; normals are not read"""
+        return _refine_many(self.cad, crops, poses, None, float(self.icp_threshold), int(self.max_iterations),
+                            self.device)
+
+
+def get_point2point_matcher(cad_points, icp_threshold=0.1, max_iterations=30, device="cuda"):
+    """-> match(ee_points, pose_initial), a PointToPointMatcher; cad_points: the model points or its file's path"""
+    return PointToPointMatcher(cad_points, icp_threshold, max_iterations, device)
+
+
+class PointToPlaneMatcher(_Matcher):
     """The point-to-plane counterpart of get_point2point_matcher's closure, for one CAD model.
 
         match = PointToPlaneMatcher(cad_points)
@@ -201,9 +207,7 @@ class PointToPlaneMatcher:
     def __init__(self, cad_points, icp_threshold=0.1, max_iterations=30, normal_radius=0.02, normal_max_nn=30,
                  device="cuda"):
         _check_normals_args(1, normal_radius, normal_max_nn)
-        self.device = torch.device(device)
-        self.cad = _cloud(_cad_model(cad_points, self.device), "cad_points", self.device)
-        self.icp_threshold, self.max_iterations = float(icp_threshold), int(max_iterations)
+        super().__init__(cad_points, float(icp_threshold), int(max_iterations), device)
         self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
 
     def crop_normals(self, ee_points):
@@ -217,17 +221,14 @@ class PointToPlaneMatcher:
         them.  A None crop or pose returns pose_initial, as the point-to-point matcher does."""
         if ee_points is None or pose_initial is None:
             return pose_initial
-        shape = tuple(ee_points.shape) if hasattr(ee_points, "shape") else np.shape(ee_points)
+        shape = _shape(ee_points)
         if len(shape) != 2 or shape[1] != 3:
             raise ValueError(f"ee_points must be [N, 3], got {shape}")
         n_normals = shape[0] if normals is None else len(normals)
         _check_icp_args(self.cad.shape[0], shape[0], n_normals, self.icp_threshold, self.max_iterations)
-        T0 = get_transformation_matrix(np.asarray(pose_initial, dtype=np.float64), switch_w=False)
         tgt = _cloud(ee_points, "ee_points", self.device)
         tn = self.crop_normals(tgt) if normals is None else _cloud(normals, "normals", self.device)
-        init = torch.as_tensor(np.ascontiguousarray(T0, dtype=np.float64)).to(self.device)
-        out_T, _ = _point2plane_enqueue(self.cad, tgt, tn, init, self.icp_threshold, self.max_iterations, 1e-6, 1e-6)
-        return get_pose_from_matrix(out_T.cpu().numpy().reshape(4, 4))
+        return self._refine(tgt, pose_initial, tn)
 
     def many(self, crops, poses, normals=None):
         """[self(c, p, n) for c, p, n in zip(crops, poses, normals)], bit for bit, in one sv_icp_batched call with one
@@ -254,10 +255,6 @@ def get_point2plane_matcher(cad_points, icp_threshold=0.1, max_iterations=30, no
 
 # ---- many registrations per call (sv_icp_batched, include/sv_hip.h block N3c) ----------------------------------------
 MAX_PROBLEMS = 64
-
-
-def _shape(x):
-    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
 
 
 def _check_batch_shapes(src, tgts, tgt_normals, init_Ts, pre, shared, max_distance, max_iterations):
@@ -323,8 +320,7 @@ def icp_batched(src, tgts, init_Ts=None, tgt_normals=None, pre=None, shared=Fals
     offsets = np.concatenate([[0], np.cumsum([_shape(t)[0] for t in tgts])]).astype(np.int64)
     s, t = _cloud(src, "src", dev), _concat(tgts, "tgts", dev)
     tn = None if tgt_normals is None else _concat(tgt_normals, "tgt_normals", dev)
-    init, pre = (None if m is None else torch.as_tensor(np.ascontiguousarray(m, dtype=np.float64)).to(dev)
-                 for m in (init_Ts, pre))
+    init, pre = _matrix(init_Ts, dev), _matrix(pre, dev)
     out_T, stats = _icp_batched_enqueue(s, t, tn, offsets, init, pre, shared, float(max_distance), int(max_iterations),
                                         float(rel_fitness), float(rel_rmse))
     host = torch.cat([out_T.reshape(-1), stats.reshape(-1)]).cpu().numpy()  # one read-back
@@ -363,8 +359,8 @@ def _refine_many(cad, crops, poses, crop_normals, icp_threshold, max_iterations,
                 raise ValueError(f"normals[{k}] must hold one normal per crop point {tuple(tgt.shape)}, "
                                  f"got {tuple(tn.shape)}")
             moved[id(crops[k])] = (tgt, tn)
-    init = np.stack([get_transformation_matrix(np.asarray(poses[k], dtype=np.float64), switch_w=False) for k in live])
-    init = torch.as_tensor(np.ascontiguousarray(init, dtype=np.float64)).to(dev)
+    init = _matrix(np.stack([get_transformation_matrix(np.asarray(poses[k], dtype=np.float64), switch_w=False)
+                             for k in live]), dev)
     Ts = []
     for a in range(0, len(live), MAX_PROBLEMS):
         part = [moved[id(crops[k])] for k in live[a:a + MAX_PROBLEMS]]

@@ -5,8 +5,19 @@ device functions, so nothing less than np.array_equal is asked.  Shared mode wit
 with several it is compared with the float64 loop icp_joint_ref, after asserting of the REFERENCE what
 tests/test_gpu_icp_point2plane.py asserts of its own: every inlier's nearest target beats the second nearest by more than
 1e-6 m^2, every stop decision is at least 1e-7 from its tolerance, cond(A) < 1e6.  Then: updates, pooled and per-problem
-fitness equal, |rmse - ref| < 1e-7, |T - T_ref| < 1e-9."""
+fitness equal, |rmse - ref| < 1e-7, |T - T_ref| < 1e-9.
+
+The single calls are themselves the P = 1 independent case of sv_icp_batched (one host routine; one independent problem
+without pre takes the single-problem update kernels, from either entry point), so the P = 1 rows of
+test_independent_problems_equal_the_single_calls_bit_for_bit hold by construction; the P = 3 and 5 rows and
+test_order_and_repetition_change_no_bits pin the batch update kernels to the single calls and that a problem's bits do not
+depend on its place in a batch.  What pins the single calls themselves is test_single_calls_give_the_recorded_bits: the
+60 calls of _single against tests/golden/icp_single_bits.json, recorded from the separate single-problem kernels and host
+loops before the host code was unified."""
 import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -40,6 +51,48 @@ def _single(gpu, objective, S, p, max_iterations):
     if objective == "point2plane":
         return I.icp_point2plane(src, tgt, nrm, init, MD, max_iterations, device=gpu)
     return I.icp_point2point(src, tgt, init, MD, max_iterations, device=gpu)
+
+
+SINGLE_BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "icp_single_bits.json")
+CAPS = (0, 1, 30)
+
+
+def _bits_key(objective, S, p, max_iterations):
+    return f"{objective}/S{S}/problem{p}/max_iterations{max_iterations}"
+
+
+def _input_sha256(S, p):
+    """SHA-256 of the bytes of problem p's src (float32), tgt, normals (float32) and init (float64), in this order"""
+    src, probs = _problems(S)
+    h = hashlib.sha256()
+    for a in (src,) + tuple(probs[p]):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _single_bits(gpu, objective, S, p, max_iterations):
+    """the single call's result as the golden file holds it: every double as float.hex()"""
+    T, fit, rmse, n = _single(gpu, objective, S, p, max_iterations)
+    return {"T": [float(v).hex() for v in np.asarray(T, np.float64).reshape(-1)],
+            "stats": [float(fit).hex(), float(rmse).hex(), float(n).hex()], "sha256": _input_sha256(S, p)}
+
+
+@pytest.mark.parametrize("max_iterations", CAPS)
+@pytest.mark.parametrize("S", [300, 1030])
+@pytest.mark.parametrize("objective", OBJECTIVES)
+def test_single_calls_give_the_recorded_bits(gpu, objective, S, max_iterations):
+    """A differing value is a bug in the code under test: the file is never re-recorded from it."""
+    with open(SINGLE_BITS) as f:
+        golden = json.load(f)
+    assert len(golden) == len(OBJECTIVES) * len(PROBLEMS) * 5 * len(CAPS)
+    for p in range(5):
+        want = golden[_bits_key(objective, S, p, max_iterations)]
+        assert _input_sha256(S, p) == want["sha256"], f"S={S} problem {p}: the generated INPUTS changed, not the kernels"
+    for p in range(5):
+        want = golden[_bits_key(objective, S, p, max_iterations)]
+        got = _single_bits(gpu, objective, S, p, max_iterations)
+        assert got["T"] == want["T"], f"{objective} S={S} problem {p}: out_T {got['T']} vs recorded {want['T']}"
+        assert got["stats"] == want["stats"], f"{objective} S={S} problem {p}: {got['stats']} vs recorded {want['stats']}"
 
 
 def _batched(gpu, objective, S, order, max_iterations, **kw):

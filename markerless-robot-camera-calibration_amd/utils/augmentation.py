@@ -382,7 +382,7 @@ def augment_quantize_batch(points, feats, labels, *, draws=None, scale=200, quan
     p_dtype = np.float32 if all(p.dtype == np.float32 for p in pts) else np.float64
     table, raw, dims = _table_and_fields(draws)
     cat = np.concatenate([p.astype(p_dtype, copy=False) for p in pts])
-    f_cat = np.concatenate([np.asarray(f, dtype=np.float32).reshape(len(f), -1) for f in feats])
+    f_cat = np.concatenate(_frame_rows(feats, np.float32))
     l_cat = np.concatenate([np.asarray(l).reshape(-1) for l in labels]).astype(np.int64)
     pts_d = torch.from_numpy(cat).to(dev, non_blocking=True)
     off_d = torch.from_numpy(off_np).to(dev, non_blocking=True)
@@ -429,6 +429,14 @@ def _augment_quantize_launch(pts_d, off_d, table_d, feats_d, labels_d, normals, 
     return res
 
 
+def _frame_rows(xs, dtype=None):
+    """per-frame host arrays [n_b, ...] -> [n_b, C] each; a frame without rows has no width of its own (reshape(0, -1)
+    is an error) and takes C from the frames that have rows"""
+    arrs = [np.asarray(x, dtype=dtype) for x in xs]
+    C = next((a.size // len(a) for a in arrs if len(a)), 1)
+    return [a.reshape(len(a), C) for a in arrs]
+
+
 def _rows_on_device(x, what, dev, dtype, N=None):
     """one CUDA tensor of concatenated rows, or a list of per-frame host arrays (concatenated and uploaded)"""
     if isinstance(x, torch.Tensor):
@@ -436,7 +444,7 @@ def _rows_on_device(x, what, dev, dtype, N=None):
             raise SvHipError(f"{what} must be a CUDA tensor or a list of host arrays (got a {x.device} tensor)")
         t = x if dtype is None else x.to(dtype)
     else:
-        a = np.concatenate([np.asarray(f).reshape(len(f), -1) for f in x])
+        a = np.concatenate(_frame_rows(x))
         t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         t = t if dtype is None else t.to(dtype)
     if N is not None and t.shape[0] != N:

@@ -90,6 +90,37 @@ def apply_draws(points, d):
     return p
 
 
+ORIGIN_NONE, ORIGIN_CENTER, ORIGIN_BASE = 0, 1, 2
+INT32_MIN = -2 ** 31
+
+
+def quantise_np(points, offsets, stats, origin, size):
+    """sv_quantise_points restated from include/sv_hip.h (N5): frame b's rows offsets[b] .. offsets[b + 1] - 1 minus
+    (max + min) / 2 (ORIGIN_CENTER), min (ORIGIN_BASE) or nothing (ORIGIN_NONE) of stats [B, 6] = (min xyz, max xyz), then
+    the float64 floor(p / size) of ME.utils.sparse_quantize; a NaN, an inf or a quotient outside int32 gives INT32_MIN.
+    -> (coords int32 [N, 4] = (b, qx, qy, qz), shifted float32 [N, 3], shift float64 [B, 3])"""
+    p = np.array(points, dtype=np.float64).reshape(-1, 3)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    B = len(offsets) - 1
+    stats = np.asarray(stats, dtype=np.float64).reshape(B, 6)
+    owner = np.repeat(np.arange(B), np.diff(offsets))
+    assert offsets[0] == 0 and len(owner) == len(p)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if origin == ORIGIN_CENTER:
+            shift = (stats[:, 3:] + stats[:, :3]) / 2.0
+        elif origin == ORIGIN_BASE:
+            shift = stats[:, :3].copy()
+        else:
+            shift = np.zeros((B, 3))
+        if origin != ORIGIN_NONE:
+            p = p - shift[owner]
+        q = np.floor(p / size)
+        inside = (q >= -2.0 ** 31) & (q <= 2.0 ** 31 - 1)  # False for a NaN
+        cells = np.where(inside, q, float(INT32_MIN)).astype(np.int64).astype(np.int32)
+        shifted = p.astype(np.float32)
+    return np.concatenate([owner[:, None].astype(np.int32), cells], axis=1), shifted, shift
+
+
 def _draw_raw(x, gran):
     bb = grid_shape(x, gran)
     return np.stack([np.random.randn(*bb).astype("float32") for _ in range(3)])

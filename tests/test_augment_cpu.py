@@ -200,6 +200,61 @@ def test_sparse_collate_against_batched_coordinates():
         ME.utils.sparse_collate(coords, feats, [l[:-1] for l in labels[:1]] + labels[1:])
 
 
+def test_quantise_restatement_against_the_per_frame_path():
+    """H.quantise_np (what tests/test_gpu_augment_edges.py holds sv_quantise_points to) against the path it restates,
+    frame by frame: centring as utils/preprocess.py (p - (max + min) / 2, p - min), then the float64 floor(p / size) of
+    ME.utils.sparse_quantize in torch; and against hand-written values at the int32 edges.  Integer results: equal."""
+    rng = np.random.default_rng(5)
+    lens = (0, 7, 0, 0, 300, 1, 0)
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    pts = rng.uniform(-150, 150, (sum(lens), 3))
+    frames = [pts[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+    stats = np.stack([np.concatenate([f.min(0), f.max(0)]) if len(f) else np.array([np.inf] * 3 + [-np.inf] * 3)
+                      for f in frames])
+    size = 40.0
+    for origin in (H.ORIGIN_NONE, H.ORIGIN_CENTER, H.ORIGIN_BASE):
+        coords, shifted, shift = H.quantise_np(pts, offsets, stats, origin, size)
+        assert coords.dtype == np.int32 and shifted.dtype == np.float32 and shift.shape == (len(lens), 3)
+        for b, f in enumerate(frames):
+            if not len(f):
+                want = {H.ORIGIN_NONE: 0.0, H.ORIGIN_BASE: np.inf}.get(origin)
+                assert np.isnan(shift[b]).all() if want is None else (shift[b] == want).all()
+                continue
+            o = {H.ORIGIN_NONE: np.zeros(3), H.ORIGIN_CENTER: (f.max(0) + f.min(0)) / 2, H.ORIGIN_BASE: f.min(0)}[origin]
+            s = f - o
+            want = torch.floor(torch.from_numpy(s).to(torch.float64) / size).to(torch.int32).numpy()
+            rows = slice(offsets[b], offsets[b + 1])
+            assert np.array_equal(shift[b], o) and (coords[rows, 0] == b).all()
+            assert np.array_equal(coords[rows, 1:], want) and np.array_equal(shifted[rows], s.astype(np.float32))
+    # the int32 edges, size 2^-3: the largest and smallest quotients are kept, one further is out, as are inf, NaN, 1e300
+    size, top = 0.125, 2.0 ** 31
+    col = np.array([-0.5, -1e-300, -0.0, 0.0, 0.125, -0.125, (top - 1) * size, -top * size, top * size, (-top - 1) * size,
+                    np.inf, -np.inf, np.nan, 1e300])
+    want = [-4, -1, 0, 0, 1, -1, 2 ** 31 - 1, -2 ** 31] + [H.INT32_MIN] * 6
+    p = np.stack([col, np.zeros_like(col), col[::-1]], axis=1)
+    coords, shifted, shift = H.quantise_np(p, [0, len(p)], np.zeros((1, 6)), H.ORIGIN_NONE, size)
+    assert coords[:, 1].tolist() == want and coords[:, 3].tolist() == want[::-1] and not coords[:, [0, 2]].any()
+    with np.errstate(over="ignore"):
+        assert np.array_equal(shifted, p.astype(np.float32), equal_nan=True) and not shift.any()
+    # a NaN in one frame's stats under CENTER: that frame's column only
+    st = np.array([[0, 0, 0, 2, 2, 2], [0, np.nan, 0, 2, 2, 2]], dtype=np.float64)
+    coords, _, shift = H.quantise_np(np.ones((4, 3)), [0, 2, 4], st, H.ORIGIN_CENTER, 1.0)
+    assert coords.tolist() == [[0, 0, 0, 0]] * 2 + [[1, 0, H.INT32_MIN, 0]] * 2 and np.isnan(shift[1, 1])
+
+
+def test_frames_without_rows_concatenate():
+    """the batch builder's per-frame feature arrays as [n_b, C]: a frame without rows, whatever its own shape, takes the
+    width of the frames that have rows (reshape(0, -1) is an error in numpy)"""
+    from mrcc_amd.utils.augmentation import _frame_rows
+
+    feats = [np.ones((5, 3), np.float64), np.zeros((0, 3), np.float32), np.zeros(0), np.arange(6.0).reshape(2, 3)]
+    rows = _frame_rows(feats, np.float32)
+    assert [r.shape for r in rows] == [(5, 3), (0, 3), (0, 3), (2, 3)] and all(r.dtype == np.float32 for r in rows)
+    assert np.concatenate(rows).shape == (7, 3) and np.array_equal(rows[3], feats[3])
+    assert [r.shape for r in _frame_rows([np.zeros(4), np.zeros(0)])] == [(4, 1), (0, 1)]
+    assert [r.shape for r in _frame_rows([np.zeros((0, 3))])] == [(0, 1)] and _frame_rows([np.zeros(2)])[0].dtype == np.float64
+
+
 def test_no_cpu_fallback():
     from mrcc_amd._lib import SvHipError
     from mrcc_amd.utils import augmentation as A

@@ -67,7 +67,8 @@ const char* sv_last_error(void);
  *    sv_frame_maps / sv_frame_plans (a frame's coordinate work as two host calls), sv_topk_indices (get_pred_center),
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
  *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
- *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e, the RGB-D ingest of N3f */
+ *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e, the RGB-D ingest of N3f
+ *    and its lens models of N3g */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -646,6 +647,68 @@ int sv_rgbd_cloud(const void* depth, int depth_type, int64_t Hd, int64_t Wd, int
                   const double* box_host, const float* lut, void* workspace, size_t workspace_bytes,
                   float* points, double* points64, float* rgb, int32_t* src, double* registered,
                   int64_t* count, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N3g  lens distortion for the RGB-D ingest: the plumb-bob (5 coefficients) and rational (8) models of OpenCV and of a ROS
+ *      CameraInfo.  Additive, the ABI version stays 4.  Every output equals a numpy restatement bit for bit; agreement with
+ *      cv2.projectPoints, cv2.undistortPoints and image_proc is by construction and unverified.
+ *
+ *   Coefficients D = (k1, k2, p1, p2, k3, k4, k5, k6), the OpenCV / ROS order; shorter sets are zero-padded by the caller.
+ *   ARITHMETIC: float64 throughout, every operation rounded on its own (no fused multiply-add) and in exactly the order
+ *   and bracketing written below.  This order is the contract.
+ *   Forward model F(a, b): a normalised direction (a, b) -> the distorted normalised point (xd, yd)
+ *     r2  = a*a + b*b
+ *     num = 1.0 + ((k3*r2 + k2)*r2 + k1)*r2
+ *     den = 1.0 + ((k6*r2 + k5)*r2 + k4)*r2
+ *     c   = num / den
+ *     dx  = (2.0*p1)*(a*b) + p2*(r2 + 2.0*(a*a))
+ *     dy  = p1*(r2 + 2.0*(b*b)) + (2.0*p2)*(a*b)
+ *     xd  = a*c + dx
+ *     yd  = b*c + dy
+ *   Ray table of a camera (fx, fy, cx, cy, D, H, W), the inverse model, per pixel (v, u):
+ *     x0 = (u - cx)*(1.0/fx), y0 = (v - cy)*(1.0/fy), x = x0, y = y0
+ *     exactly 64 rounds, no early exit, of
+ *       r2 = x*x + y*y
+ *       ic = (1.0 + ((k6*r2 + k5)*r2 + k4)*r2) / (1.0 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *       dx, dy as above, at (x, y)
+ *       x = (x0 - dx)*ic, y = (y0 - dy)*ic
+ *     (xd, yd) = F(x, y); the pixel is VALID iff |(fx*xd + cx) - u| <= 1e-6 and |(fy*yd + cy) - v| <= 1e-6 (a NaN fails).
+ *     A valid pixel stores (x, y), an invalid one (NaN, NaN).
+ *   (OpenCV's default inverse stops after 5 rounds: 1.7e-2 px off on the reference's Kinect 1 colour lens and 2 px off on
+ *   an Azure-Kinect-like rational depth lens; 64 rounds end below 1e-11 px on both.)
+ *   The table is double[H * W * 2 + 1], pixel j = v * W + u at [2j], [2j + 1]; the last element is r2_max, the largest
+ *   x*x + y*y over the valid pixels, 0 when none is valid.
+ *
+ *   sv_lens_rays: cam_host = HOST double[4] fx, fy, cx, cy; dist_host = HOST double[8]; rays = DEVICE double[H*W*2 + 1].
+ *   Two launches: r2_max cleared, then one thread per pixel; r2_max is reduced per wave and workgroup and then by a 64-bit
+ *   integer atomic max on the bit pattern (no float atomics): repeated calls give the same bits.  Checked before any HIP
+ *   call: H, W >= 1 and H * W <= 2^24, all twelve values finite, fx and fy non-zero, pointers non-null.
+ *
+ *   sv_rgbd_cloud_lens: sv_rgbd_cloud (N3f) with three more arguments, each of which may be NULL = "pinhole for that part,
+ *   with exactly sv_rgbd_cloud's arithmetic"; with all three NULL every output has sv_rgbd_cloud's bits.  The workspace is
+ *   sv_rgbd_cloud_workspace_bytes.
+ *     depth_rays  DEVICE table of the depth camera [Hd x Wd].  Stage 2: x = rx*d, y = ry*d, z = d with (rx, ry) the depth
+ *                 pixel's ray.  A NaN ray makes X, Y, Z NaN, which the existing rule drops.
+ *     color_rays  DEVICE table of the colour camera [Hc x Wc].  Stage 3: colour pixel j is kept only if its ray is valid
+ *                 (and the conditions of N3f hold); points64 = (rx*r, ry*r, r).
+ *     color_dist_host  HOST double[8] of the colour camera; needs color_rays.  Stage 2: a = X*iz, b = Y*iz,
+ *                 (xd, yd) = F(a, b), uu = fxc*xd + cxc, vv = fyc*yd + cyc; rounding and range rules as in N3f.  The
+ *                 candidate is dropped unless a*a + b*b <= r2_max of color_rays (a failed comparison, NaN included, drops
+ *                 it): a rational model is not monotonic, and a point far outside the field of view can fold back into
+ *                 the image.  LIMIT: the bound is radial, so a point beyond an image edge but inside the corner radius is
+ *                 not caught.
+ *   SV_RGBD_ALIGNED uses color_rays only; depth_rays and color_dist_host must be NULL.  Checked before any HIP call: N3f's
+ *   list, these two rules, and the color_dist_host values finite.  Five launches, no read-back; the pinhole kernels take the
+ *   arguments they took before and read no table.
+ * ------------------------------------------------------------------------------------------- */
+int sv_lens_rays(const double* cam_host, const double* dist_host, int64_t H, int64_t W, double* rays, sv_stream_t stream);
+int sv_rgbd_cloud_lens(const void* depth, int depth_type, int64_t Hd, int64_t Wd, int64_t depth_row_bytes,
+                       const uint8_t* color, int64_t Hc, int64_t Wc, int64_t color_row_bytes,
+                       const uint8_t* mask, const double* cam_host, int filter_size, int filter_thresh, int flags,
+                       const double* box_host, const float* lut, void* workspace, size_t workspace_bytes,
+                       float* points, double* points64, float* rgb, int32_t* src, double* registered,
+                       int64_t* count, const double* depth_rays, const double* color_rays,
+                       const double* color_dist_host, sv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4  point-matching pose losses with their gradients (replace the per-instance Python loops of utils/loss.py:166-188

@@ -130,6 +130,9 @@ SIGNATURES = {
     "sv_rgbd_cloud_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "sv_rgbd_cloud": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, c_int, c_int,
                               _P, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "sv_lens_rays": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
+    "sv_rgbd_cloud_lens": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int, c_int,
+                                   c_int, _P, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sv_pose_loss_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "sv_pose_match_loss": (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     "sv_elastic_field_workspace_bytes": (c_size_t, [_P, c_int]),

@@ -7,6 +7,11 @@ registers it into the colour camera through a z-buffer and back-projects the reg
 cloud with source indices (include/sv_hip.h N3f has the definitions and the order of the float64 arithmetic).
 `decode_host` and `registered_host` restate those definitions in numpy.
 
+Lens distortion (include/sv_hip.h N3g): a camera may carry the plumb-bob or rational coefficients of OpenCV and of a ROS
+CameraInfo, D = (k1, k2, p1, p2, k3, k4, k5, k6).  `sv_lens_rays` inverts the model once per camera into a table of rays on
+the device, which every frame of that camera shares, and `sv_rgbd_cloud_lens` back-projects along those rays and projects
+through the forward model.  A frame without coefficients, or with all of them zero, takes `sv_rgbd_cloud` as before.
+
 An RGBDFrame goes wherever a PackedFrame (utils/packed.py) goes: predict_segmentation_packed, the items of
 predict_segmentation_stream, PackedCloudDTO(packed=...).  Its "records" are the colour image's pixels, j = v * Wc + u.
 """
@@ -50,6 +55,87 @@ def _K(K, what):
     return K.reshape(3, 3)
 
 
+LENS_ROUNDS = 64  # rounds of the inverse model, no early exit (include/sv_hip.h N3g)
+LENS_TOL = 1e-6  # pixels: a ray is valid iff the forward model brings it back to its pixel within this
+DISTORTION_MODELS = ("plumb_bob", "rational_polynomial")
+CAMERAS = ("depth", "color")
+LENS_CACHE_SIZE = 8  # cameras whose tables are kept, on the host and on the device each
+_host_tables, _device_tables = {}, {}
+lens_table_builds = 0  # sv_lens_rays calls so far: a camera's frames share one table per device
+
+
+def _D(D, what):
+    """distortion coefficients -> float64 [8] (k1, k2, p1, p2, k3, k4, k5, k6), or None for a pinhole camera (no
+    coefficients, or all of them zero)"""
+    if D is None:
+        return None
+    D = np.asarray(D, dtype=np.float64).reshape(-1)
+    if len(D) == 0:
+        return None
+    if len(D) not in (4, 5, 8):
+        raise ValueError(f"{what} must hold 4, 5 or 8 coefficients (plumb-bob or rational), got {len(D)}: the thin-prism and "
+                         f"tilted-sensor models are not supported")
+    if not np.isfinite(D).all():
+        raise ValueError(f"{what} must be finite")
+    out = np.zeros(8)
+    out[:len(D)] = D
+    return out if out.any() else None
+
+
+def _info_D(info, what):
+    """D of a CameraInfo look-alike, read only when the attribute is there"""
+    D = getattr(info, "D", None)
+    if D is None or len(D) == 0 or not np.any(np.asarray(D, dtype=np.float64) != 0):
+        return None
+    model = getattr(info, "distortion_model", "plumb_bob")
+    if model not in DISTORTION_MODELS:
+        raise ValueError(f"{what}: distortion model {model!r} is not supported (only {', '.join(DISTORTION_MODELS)})")
+    return D
+
+
+def lens_forward(D, a, b):
+    """the forward model F of include/sv_hip.h N3g: normalised direction (a, b) -> distorted normalised point (xd, yd)"""
+    k1, k2, p1, p2, k3, k4, k5, k6 = (np.float64(x) for x in D)
+    r2 = a * a + b * b
+    num = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+    den = 1.0 + ((k6 * r2 + k5) * r2 + k4) * r2
+    c = num / den
+    dx = (2.0 * p1) * (a * b) + p2 * (r2 + 2.0 * (a * a))
+    dy = p1 * (r2 + 2.0 * (b * b)) + (2.0 * p2) * (a * b)
+    return a * c + dx, b * c + dy
+
+
+def lens_rays_host(cam4, D, H, W):
+    """the ray table sv_lens_rays writes, float64 [H * W * 2 + 1]: (x, y) per pixel, (NaN, NaN) where the inverse model
+    does not come back to the pixel, then r2_max"""
+    fx, fy, cx, cy = (np.float64(x) for x in cam4)
+    k1, k2, p1, p2, k3, k4, k5, k6 = (np.float64(x) for x in D)
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    with np.errstate(all="ignore"):
+        x0, y0 = (u - cx) * (1.0 / fx), (v - cy) * (1.0 / fy)
+        x, y = x0, y0
+        for _ in range(LENS_ROUNDS):
+            r2 = x * x + y * y
+            ic = (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+            dx = (2.0 * p1) * (x * y) + p2 * (r2 + 2.0 * (x * x))
+            dy = p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * (x * y)
+            x, y = (x0 - dx) * ic, (y0 - dy) * ic
+        xd, yd = lens_forward(D, x, y)
+        valid = (np.abs((fx * xd + cx) - u) <= LENS_TOL) & (np.abs((fy * yd + cy) - v) <= LENS_TOL)
+        r2 = (x * x + y * y)[valid]
+    table = np.empty(H * W * 2 + 1)
+    table[:-1] = np.stack((np.where(valid, x, np.nan), np.where(valid, y, np.nan)), axis=2).reshape(-1)
+    table[-1] = r2.max() if len(r2) else 0.0
+    return table
+
+
+def _remember(cache, key, value):
+    while len(cache) >= LENS_CACHE_SIZE:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
 class RGBDFrame:
     """One depth image ([Hd, Wd] uint16 or float32) with the colour image ([Hc, Wc, 3] uint8, or None) it belongs to.
 
@@ -58,10 +144,13 @@ class RGBDFrame:
     one size, and color_K defaults to depth_K).  depth_scale: metres (or whatever unit the cloud shall have) per depth
     unit.  mask: [Hc, Wc], a pixel with a non-zero value is dropped.  filter_size, filter_thresh: the discontinuity filter
     on raw uint16 depth (0 = off; the reference uses 7 and 1000).  keep: "far" keeps the largest depth where several
-    depth pixels land on one colour pixel, which is what the reference does; "near" keeps the smallest."""
+    depth pixels land on one colour pixel, which is what the reference does; "near" keeps the smallest.
+    depth_D, color_D: distortion coefficients of the two cameras in the OpenCV / ROS order, 4, 5 (plumb-bob) or 8
+    (rational) of them; None or all zeros = a pinhole camera.  In an aligned frame color_D defaults to depth_D as color_K
+    does to depth_K, and the colour camera is the one used."""
 
     def __init__(self, depth, color, depth_K, color_K=None, color_from_depth=None, depth_scale=0.001, mask=None,
-                 filter_size=0, filter_thresh=1000, keep="far", color_order="rgb"):
+                 filter_size=0, filter_thresh=1000, keep="far", color_order="rgb", depth_D=None, color_D=None):
         d = np.asarray(depth)
         self.depth = _rows(d, np.dtype("<f4") if d.dtype.kind == "f" else np.dtype("<u2"), 1, "depth")
         self.depth_type = _lib.SV_DEPTH_F32 if self.depth.dtype.kind == "f" else _lib.SV_DEPTH_U16
@@ -69,6 +158,8 @@ class RGBDFrame:
         self.aligned = color_from_depth is None
         self.depth_K = _K(depth_K, "depth_K")
         self.color_K = self.depth_K if color_K is None else _K(color_K, "color_K")
+        self.depth_D = _D(depth_D, "depth_D")
+        self.color_D = _D(color_D, "color_D") if (color_D is not None or not self.aligned) else self.depth_D
         if self.aligned:
             self.H = np.eye(4)[:3]
         else:
@@ -119,6 +210,63 @@ class RGBDFrame:
         return np.concatenate([[kd[0, 0], kd[1, 1], kd[0, 2], kd[1, 2], kc[0, 0], kc[1, 1], kc[0, 2], kc[1, 2]],
                                self.H.reshape(-1), [self.depth_scale]]).astype(np.float64)
 
+    @property
+    def has_lens(self):
+        """whether a camera this frame uses is distorted (an aligned frame uses the colour camera only)"""
+        return self.color_D is not None or (self.depth_D is not None and not self.aligned)
+
+    def _lens_camera(self, which):
+        """(fx, fy, cx, cy), D or None, H, W of the "depth" or the "color" camera"""
+        if which not in CAMERAS:
+            raise ValueError(f"which must be one of {CAMERAS}, got {which!r}")
+        K, D, H, W = ((self.depth_K, self.depth_D, self.Hd, self.Wd) if which == "depth" else
+                      (self.color_K, self.color_D, self.Hc, self.Wc))
+        return np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]]), D, H, W
+
+    @staticmethod
+    def _lens_key(cam4, D, H, W):
+        return np.concatenate([cam4, D, [H, W]]).astype(np.float64).tobytes()
+
+    def rays_host(self, which="color"):
+        """the ray table of the "depth" or the "color" camera as sv_lens_rays defines it (lens_rays_host; shared by the
+        frames of one camera), or None for a pinhole camera.  A lens without a single valid pixel is refused."""
+        cam4, D, H, W = self._lens_camera(which)
+        if D is None:
+            return None
+        key = self._lens_key(cam4, D, H, W)
+        table = _host_tables.get(key)
+        if table is None:
+            table = lens_rays_host(cam4, D, H, W)
+            if np.isnan(table[:-1]).all():
+                raise ValueError(f"the {which} camera's distortion model has no valid pixel: the inverse model comes back "
+                                 f"to no pixel of the {H} x {W} image within {LENS_TOL} px")
+            table.setflags(write=False)
+            _remember(_host_tables, key, table)
+        return table
+
+    def rays_device(self, which, device):
+        """the same table on `device`, built on first use by sv_lens_rays on the current stream and waited for: set-up
+        work, once per camera and device.  None for a pinhole camera."""
+        global lens_table_builds
+        cam4, D, H, W = self._lens_camera(which)
+        if D is None:
+            return None
+        device = torch.device(device)
+        index = torch.cuda.current_device() if device.index is None else device.index
+        key = (self._lens_key(cam4, D, H, W), device.type, index)
+        table = _device_tables.get(key)
+        if table is None:
+            table = torch.empty(H * W * 2 + 1, dtype=torch.float64, device=device)
+            call("sv_lens_rays", (c_double * 4)(*cam4), (c_double * 8)(*D), c_int64(H), c_int64(W), ptr(table), stream_ptr())
+            lens_table_builds += 1
+            torch.cuda.current_stream(device).synchronize()
+            valid, r2_max = int((table[:-1:2] == table[:-1:2]).sum().item()), float(table[-1].item())
+            if valid == 0:
+                raise ValueError(f"the {which} camera's distortion model has no valid pixel (r2_max {r2_max}): the inverse "
+                                 f"model comes back to no pixel of the {H} x {W} image within {LENS_TOL} px")
+            _remember(_device_tables, key, table)
+        return table
+
     def flags(self):
         return ((_lib.SV_RGBD_ALIGNED if self.aligned else 0) | (_lib.SV_RGBD_NEAREST if self.keep == "near" else 0) |
                 (_lib.SV_RGBD_BGR if self.color_order == "bgr" else 0))
@@ -129,7 +277,9 @@ class RGBDFrame:
                         **kw):
         """Any objects with the attributes of sensor_msgs/Image (height, width, encoding, is_bigendian, step, data) and of
         sensor_msgs/CameraInfo (K).  Depth encodings: 16UC1 (depth_scale 0.001: millimetres) and 32FC1 (1.0: metres);
-        colour encodings: rgb8 and bgr8.  `step` becomes the row bytes; the pixel data is not copied here."""
+        colour encodings: rgb8 and bgr8.  `step` becomes the row bytes; the pixel data is not copied here.  An info object
+        that also has D and distortion_model gives the camera its lens: "plumb_bob" and "rational_polynomial" are taken, an
+        empty or all-zero D is a pinhole camera, any other model with a non-zero D is refused."""
 
         def image(msg, dtype, channels, what):
             if msg.is_bigendian and dtype.itemsize > 1:
@@ -154,6 +304,10 @@ class RGBDFrame:
                 raise ValueError(f"colour encoding must be 'rgb8' or 'bgr8', got {color_msg.encoding!r}")
             color = image(color_msg, np.dtype("u1"), 3, "colour")
             kw.setdefault("color_order", color_msg.encoding[:3])
+        if "depth_D" not in kw:
+            kw["depth_D"] = _info_D(depth_info, "depth_info")
+        if "color_D" not in kw and color_info is not None:
+            kw["color_D"] = _info_D(color_info, "color_info")
         return cls(depth, color, depth_info.K, None if color_info is None else color_info.K, color_from_depth,
                    scale if depth_scale is None else depth_scale, **kw)
 
@@ -237,16 +391,28 @@ class RGBDFrame:
         v, u = np.nonzero(d != 0)
         d = d[v, u]
         with np.errstate(all="ignore"):
-            x = ((u - cam[2]) * d) * (1.0 / cam[0])
-            y = ((v - cam[3]) * d) * (1.0 / cam[1])
+            if self.depth_D is not None:
+                rays = self.rays_host("depth")[:-1].reshape(self.Hd, self.Wd, 2)
+                x, y = rays[v, u, 0] * d, rays[v, u, 1] * d
+            else:
+                x = ((u - cam[2]) * d) * (1.0 / cam[0])
+                y = ((v - cam[3]) * d) * (1.0 / cam[1])
             z = d
             X = ((H[0, 0] * x + H[0, 1] * y) + H[0, 2] * z) + H[0, 3]
             Y = ((H[1, 0] * x + H[1, 1] * y) + H[1, 2] * z) + H[1, 3]
             Z = ((H[2, 0] * x + H[2, 1] * y) + H[2, 2] * z) + H[2, 3]
             iz = 1.0 / Z
-            ui = np.trunc((cam[4] * X) * iz + cam[6] + 0.5)
-            vi = np.trunc((cam[5] * Y) * iz + cam[7] + 0.5)
-            ok = (ui >= 0) & (ui < self.Wc) & (vi >= 0) & (vi < self.Hc) & (Z > 0) & np.isfinite(Z)
+            if self.color_D is not None:
+                a, b = X * iz, Y * iz
+                xd, yd = lens_forward(self.color_D, a, b)
+                ui = np.trunc(cam[4] * xd + cam[6] + 0.5)
+                vi = np.trunc(cam[5] * yd + cam[7] + 0.5)
+                inside = a * a + b * b <= self.rays_host("color")[-1]  # the radial fold-back bound; False for a NaN
+            else:
+                ui = np.trunc((cam[4] * X) * iz + cam[6] + 0.5)
+                vi = np.trunc((cam[5] * Y) * iz + cam[7] + 0.5)
+                inside = True
+            ok = (ui >= 0) & (ui < self.Wc) & (vi >= 0) & (vi < self.Hc) & (Z > 0) & np.isfinite(Z) & inside
         idx = vi[ok].astype(np.int64) * self.Wc + ui[ok].astype(np.int64)
         if self.keep == "far":
             reg = np.zeros(self.Hc * self.Wc, dtype=np.float64)
@@ -266,11 +432,13 @@ class RGBDFrame:
         r = r[j]
         v, u = j // self.Wc, j % self.Wc
         with np.errstate(all="ignore"):
-            p64 = np.stack((((u - cam[6]) * r) * (1.0 / cam[4]), ((v - cam[7]) * r) * (1.0 / cam[5]), r), axis=1)
+            p64 = self._backproject_host(cam, u, v, j, r)
             p32 = p64.astype(np.float32)
             if idx is not None:
                 return p64, p32, j
             keep = r > 0
+            if self.color_D is not None:
+                keep &= ~np.isnan(self.rays_host("color")[:-1:2])  # the pixel's ray is valid
             if self.mask is not None:
                 keep &= self.mask.reshape(-1) == 0
             if box is not None:
@@ -278,6 +446,13 @@ class RGBDFrame:
                 keep &= np.all((box[:3] < w) & (w < box[3:]), axis=1)
         src = np.nonzero(keep)[0]
         return p64[src], p32[src], src
+
+    def _backproject_host(self, cam, u, v, j, r):
+        """stage 3's points64 of the colour pixels j = v * Wc + u with registered depth r"""
+        if self.color_D is not None:
+            rays = self.rays_host("color")[:-1].reshape(-1, 2)[j]
+            return np.stack((rays[:, 0] * r, rays[:, 1] * r, r), axis=1)
+        return np.stack((((u - cam[6]) * r) * (1.0 / cam[4]), ((v - cam[7]) * r) * (1.0 / cam[5]), r), axis=1)
 
     def _colors_host(self, src, color, lut):
         if self.color is None:
@@ -317,8 +492,7 @@ class RGBDFrame:
                 raw = np.where(np.isfinite(raw) & (raw > 0), raw, np.float32(0))
             r = raw.astype(np.float64) * np.float64(self.depth_scale)
             with np.errstate(all="ignore"):
-                p32 = np.stack((((u - cam[6]) * r) * (1.0 / cam[4]), ((v - cam[7]) * r) * (1.0 / cam[5]), r),
-                               axis=1).astype(np.float32)
+                p32 = self._backproject_host(cam, u, v, idx, r).astype(np.float32)
         else:
             _, p32, _ = self._cloud_host(None, idx)
         return p32, self._colors_host(idx, color, lut)
@@ -334,7 +508,9 @@ class RGBDFrame:
 
     # ---- device decoding --------------------------------------------------------------------------------------------
     def unpack(self, d_bytes, box=None, lut=None, want_src=True, want_points64=False, want_registered=False):
-        """sv_rgbd_cloud on this frame's bytes (_bytes()) already on the device (uint8 CUDA tensor), on the current stream.
+        """sv_rgbd_cloud (sv_rgbd_cloud_lens with the cameras' cached ray tables when the frame has a lens: the first frame
+        of a camera on a device builds them and waits, rays_device) on this frame's bytes (_bytes()) already on the device
+        (uint8 CUDA tensor), on the current stream.
         -> (points [n, 3], rgb [n, 3] or None, src int32 [n] or None, count int64 [1]), n = Hc * Wc, all on the device and
         NOT sliced: rows at or beyond count are unspecified.  Nothing is read back.  want_points64 / want_registered append
         the float64 points [n, 3] / the registered map [Hc, Wc] to the tuple."""
@@ -358,11 +534,18 @@ class RGBDFrame:
         base = d_bytes.data_ptr()
         d_color = c_void_p(base + self.depth_nbytes) if self.color is not None else None
         d_mask = c_void_p(base + self.depth_nbytes + self.color_nbytes) if self.mask is not None else None
-        call("sv_rgbd_cloud", c_void_p(base), c_int(self.depth_type), c_int64(self.Hd), c_int64(self.Wd),
-             c_int64(self.depth_row_bytes), d_color, c_int64(self.Hc), c_int64(self.Wc), c_int64(self.color_row_bytes),
-             d_mask, (c_double * 21)(*self.cam()), c_int(self.filter_size), c_int(self.filter_thresh), c_int(self.flags()),
-             None if box is None else (c_double * 6)(*box), ptr(lut), ptr(ws), c_size_t(ws_bytes), ptr(points),
-             ptr(points64), ptr(rgb), ptr(src), ptr(registered), ptr(count), stream_ptr())
+        args = (c_void_p(base), c_int(self.depth_type), c_int64(self.Hd), c_int64(self.Wd),
+                c_int64(self.depth_row_bytes), d_color, c_int64(self.Hc), c_int64(self.Wc), c_int64(self.color_row_bytes),
+                d_mask, (c_double * 21)(*self.cam()), c_int(self.filter_size), c_int(self.filter_thresh), c_int(self.flags()),
+                None if box is None else (c_double * 6)(*box), ptr(lut), ptr(ws), c_size_t(ws_bytes), ptr(points),
+                ptr(points64), ptr(rgb), ptr(src), ptr(registered), ptr(count))
+        if self.has_lens:
+            depth_rays = None if self.aligned else self.rays_device("depth", dev)
+            color_rays = self.rays_device("color", dev)
+            dist = None if (self.aligned or self.color_D is None) else (c_double * 8)(*self.color_D)
+            call("sv_rgbd_cloud_lens", *args, ptr(depth_rays), ptr(color_rays), dist, stream_ptr())
+        else:
+            call("sv_rgbd_cloud", *args, stream_ptr())
         out = (points, rgb, src, count)
         if want_points64:
             out += (points64,)

@@ -3,7 +3,7 @@ is the numpy restatement of the same run (RGBDFrame.decode_host: vectorised, alr
 per-pixel Python loops).  Each section runs in a child process of its own under `timeout`, one after the other; the first
 that fails ends the run.
 
-    python tools/rgbd_timing.py [--frames 32] [--sections decode,host,rgbd,take] [--group 1]
+    python tools/rgbd_timing.py [--frames 32] [--sections decode,host,rgbd,take,lens] [--group 1]
 
 decode:  RGBDFrame.decode_device (staging copy, upload, sv_rgbd_cloud, 8-byte read-back) against decode_host at 480 x 640
          and 720 x 1280, registered and aligned, the 7 x 7 filter on and off; and sv_rgbd_cloud alone on resident bytes
@@ -15,6 +15,8 @@ rgbd:    the same frames as RGBDFrame items through the packed stream: frames/s 
          small network run, so the frames/s of both sides show the host's share and are not comparable with bench.py's.
 take:    what the pose stages' crop costs on a registered frame: the first take() runs the host registration, later ones
          read the cached map.
+lens:    lens distortion (include/sv_hip.h N3g): sv_lens_rays at 480 x 640 and 720 x 1280; decode_device and the cloud entry
+         alone with and without a lens, registered and aligned; the packed stream's frames/s on lens frames.
 No figure is a pass condition."""
 import argparse
 import os
@@ -27,14 +29,17 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SECTIONS = ("decode", "host", "rgbd", "take")
-LIMIT_S = {"decode": 240, "host": 240, "rgbd": 240, "take": 120}
+SECTIONS = ("decode", "host", "rgbd", "take", "lens")
+LIMIT_S = {"decode": 240, "host": 240, "rgbd": 240, "take": 120, "lens": 240}
+KINECT1_D = (0.159, -0.284, -0.003, 0.003, 0.0)  # plumb-bob, the size of the reference's Kinect 1 colour lens
+RATIONAL_D = (5.6, 3.6, 3.2e-4, -1.1e-4, 0.18, 5.93, 5.44, 1.0)  # an Azure-Kinect-like depth lens
 SCALE = 50
 
 
-def make_frame(h, w, registered, filtered, seed=0):
+def make_frame(h, w, registered, filtered, seed=0, lens=False):
     """a wavy wall at 1.4 m with an end-effector blob at 0.8 m in the keyed colours of synth.gen_scene; the registered form has
-    a depth camera of 0.8 times the colour camera's size, 1.2 degrees rotated and 20 mm to the side"""
+    a depth camera of 0.8 times the colour camera's size, 1.2 degrees rotated and 20 mm to the side.  lens: the colour camera
+    carries KINECT1_D and the depth camera of the registered form RATIONAL_D"""
     from mrcc_amd.utils.rgbd import RGBDFrame
 
     rng = np.random.default_rng(seed)
@@ -52,6 +57,8 @@ def make_frame(h, w, registered, filtered, seed=0):
     f = w * 0.875
     K = np.array([[f, 0, (w - 1) / 2], [0, f, (h - 1) / 2], [0, 0, 1]])
     kw = dict(filter_size=7 if filtered else 0, filter_thresh=300)
+    if lens:
+        kw.update(color_D=KINECT1_D, depth_D=RATIONAL_D if registered else KINECT1_D)
     if not registered:
         return RGBDFrame(depth, color, K, **kw)
     Kd = np.array([[0.74 * w, 0, (wd - 1) / 2], [0, 0.74 * w, (hd - 1) / 2], [0, 0, 1]])
@@ -186,6 +193,78 @@ def rgbd(frames, group):
           f"upload, sv_rgbd_cloud launches, count read-back) (end-effector points in frame 0: {int((out[0][0] == 2).sum())})")
 
 
+def lens(frames, group):
+    import ctypes
+
+    import torch
+
+    from mrcc_amd._lib import call, ptr, stream_ptr
+    from mrcc_amd.utils import rgbd as R
+    from mrcc_amd.utils.packed import device_lut_values
+
+    dev = torch.device("cuda")
+    lut = torch.from_numpy(device_lut_values("float64")).to(dev)
+    header()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for h, w in ((480, 640), (720, 1280)):
+        f = w * 0.875
+        table = torch.empty(h * w * 2 + 1, dtype=torch.float64, device=dev)
+        cam4, dist = (ctypes.c_double * 4)(f, f, (w - 1) / 2, (h - 1) / 2), (ctypes.c_double * 8)(*RATIONAL_D)
+        for timed in (False, True):
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(10):
+                call("sv_lens_rays", cam4, dist, h, w, ptr(table), stream_ptr())
+            end.record()
+            torch.cuda.synchronize()
+        valid = int((table[:-1:2] == table[:-1:2]).sum().item())
+        print(f"lens:    sv_lens_rays {h} x {w} (rational, 64 rounds): {start.elapsed_time(end) / 10:.4f} ms per call, "
+              f"{valid} of {h * w} pixels valid, r2_max {float(table[-1].item()):.4f}")
+    for h, w in ((480, 640), (720, 1280)):
+        for registered in (True, False):
+            for with_lens in (False, True):
+                frame = make_frame(h, w, registered, filtered=False, lens=with_lens)
+                for _ in range(3):  # the first call of a lens frame builds the camera's tables
+                    got = fresh(frame).decode_device(dev, lut=lut)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    got = fresh(frame).decode_device(dev, lut=lut)
+                torch.cuda.synchronize()
+                dev_ms = (time.perf_counter() - t0) / 10 * 1e3
+                want = frame.decode_host()
+                assert np.array_equal(got[0].cpu().numpy().view(np.int32), want[0].view(np.int32))
+                assert np.array_equal(got[2].cpu().numpy(), want[2])
+                d_bytes = torch.from_numpy(frame._bytes()).to(dev)
+                torch.cuda.synchronize()
+                start.record()
+                for _ in range(20):
+                    frame.unpack(d_bytes, lut=lut)
+                end.record()
+                torch.cuda.synchronize()
+                print(f"lens:    {h} x {w} {'registered' if registered else 'aligned   '} {'lens   ' if with_lens else 'pinhole'}: "
+                      f"{len(want[2])} points; decode_device {dev_ms:.3f} ms, "
+                      f"{'sv_rgbd_cloud_lens' if with_lens else 'sv_rgbd_cloud'} alone {start.elapsed_time(end) / 20:.4f} ms per call")
+    eng = make_engine()
+    made = [make_frame(480, 640, registered=True, filtered=False, seed=s, lens=True) for s in range(4)]
+
+    def items(n):
+        for i in range(n):
+            yield fresh(made[i % len(made)]), None, "float64"
+
+    for _ in range(2):
+        out = list(eng.predict_segmentation_stream(items(8), group=group))
+    torch.cuda.synchronize()
+    builds = R.lens_table_builds
+    t0 = time.perf_counter()
+    out = list(eng.predict_segmentation_stream(items(frames), group=group))
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    print(f"lens:    packed stream(group={group}) on RGBDFrame items with a lens, {frames} registered 480 x 640 frames of "
+          f"{len(out[0][0])} points: {frames / wall:.2f} frames/s, {wall / frames * 1e3:.3f} ms per frame; tables built during "
+          f"the timed run: {R.lens_table_builds - builds}")
+
+
 def take():
     from mrcc_amd.utils.packed import normalized_color_table
 
@@ -219,6 +298,8 @@ def main():
         return rgbd(args.frames, args.group)
     if args.child == "take":
         return take()
+    if args.child == "lens":
+        return lens(args.frames, args.group)
     for section in args.sections.split(","):
         if section not in SECTIONS:
             raise SystemExit(f"unknown section {section!r}")

@@ -84,8 +84,9 @@ struct ConvCfg {
   static constexpr int PFD_RAW = MR * NT >= 6 ? 1 : (8 + MR * NT - 1) / (MR * NT);
   static constexpr int PFD = PFD_RAW > KC / 4 ? KC / 4 : PFD_RAW;
   // the FULL form (see the kernel) pays where a k-step is one or two matrix ops and the per-k-step bookkeeping of
-  // the general form dominates; on the 64-row tile it costs the 129th VGPR (3 instead of 4 waves per SIMD) and on
-  // 16x128 tiles it measured slower (profiles/r01_conv_full_form.txt)
+  // the general form dominates; on the 64-row tile it gained nothing and compiles to 107 VGPRs (four
+  // waves per SIMD) where the general form's WIDE step fits five (94-95 VGPRs, conv_tile_body); on 16x128 tiles it
+  // measured slower (profiles/r01_conv_full_form.txt)
   static constexpr bool USE_FULL = (MR * NT == 1) || (TM_ == 32 && WAVES_N == 4 && NT == 3) || (TM_ == 16 && NT == 3);
   static constexpr int F4_PER_ROW = KC / 4;      // float4 per gathered row and step
   static constexpr int ROWS_PER_PASS = 256 / F4_PER_ROW;
@@ -113,6 +114,11 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
   constexpr int PFD = RING ? Cfg::PFD : 1;  // RING: launches too small to fill the chip (see launch_conv)
   constexpr int ROWS_PER_PASS = Cfg::ROWS_PER_PASS;
   constexpr int SUBS = TM_ / 16;  // sub-tiles per tile
+  // WIDE: the 384-column form of the chip-filling layers (64-row tile and the 32-row tail body of the dual launch).  Its
+  // step keeps FOUR k-steps of weights and HALF a step's gathers in registers (see the step below), which is what lets
+  // five waves per SIMD be resident (96 VGPRs)
+  constexpr bool WIDE = FAST && !FULL && !RING && CPO == 0 && WAVES_N == 4 && NT == 3 && (TM_ == 64 || TM_ == 32);
+  static_assert(!WIDE || A_F4 == 2, "the WIDE step moves a step's gathers in two halves");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* As = lds;                             // [2][TM_][SA]
   int* idx_s = (int*)(lds + 2 * TM_ * SA);     // [K][TM_] gathered input row of every (offset, tile row)
@@ -262,7 +268,7 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
 
   // gathered rows in flight: the rows of step s + 1 are requested at the start of step s and written to LDS at its end.
   // (One step of look-ahead is enough: gather latency is not what a step waits for - two steps ahead cost the wide
-  // layers a wave per SIMD)
+  // layers a wave per SIMD)  The WIDE step moves them in two halves through ra[0] alone.
   float4 ra[A_F4];
   const int a_cc = (tid % Cfg::F4_PER_ROW) * 4;
   const int a_r = tid / Cfg::F4_PER_ROW;
@@ -272,78 +278,81 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
   const uint32_t col_bytes = (uint32_t)a_cc * 4u;
   const int cin_rem = Cin % KC;
   const uint32_t col_last = (cin_rem == 0 || a_cc < cin_rem) ? col_bytes : 0u - (uint32_t)(Cin - cin_rem) * 4u;
+  // gather_row: this thread's j-th float4 of step (k, c0)
+  auto gather_row = [&](int k, int c0, uint32_t sm, int j) -> float4 {
+    const int r = a_r + ROWS_PER_PASS * j;
+    if (FAST) {
+      // one ds_read (the row's byte offset), one add (this thread's column) and a buffer_load whose SGPR offset is the
+      // step's channel chunk: rows past the tile (clamped), sub-tiles without a neighbour at this offset (all their
+      // rows are absent) and absent neighbours need no test - the descriptor's range check returns zeros for them
+      const int rr = (A_F4 * ROWS_PER_PASS > TM_) ? min(r, TM_ - 1) : r;
+      if (CPO) {
+        // fused offsets: column a_cc of the step belongs to offset k + a_cc / CPO, channel a_cc % CPO
+        const int kk = k + a_cc / (CPO ? CPO : 1);
+        uint32_t off = (uint32_t)idx_s[min(kk, K - 1) * TM_ + rr];
+        if (kk >= K) off = BUF_ABSENT;
+        const f32x4 v = buffer_load_floats<4>(rsrc_in, off + (uint32_t)(a_cc % (CPO ? CPO : 1)) * 4u, 0u);
+        return make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        const uint32_t off = (uint32_t)idx_s[k * TM_ + rr];
+        // the last chunk of a layer whose Cin is not a multiple of KC: columns past Cin are never multiplied; their
+        // lanes re-read the row's first columns (col_last) so that no load reaches past a row
+        const uint32_t cb = (!FULL && c0 + KC > Cin) ? col_last : col_bytes;
+        const f32x4 v = buffer_load_floats<4>(rsrc_in, off + cb, (uint32_t)c0 * 4u);
+        return make_float4(v[0], v[1], v[2], v[3]);
+      }
+      (void)sm;
+    } else if (CPO) {
+      float e[4] = {0.f, 0.f, 0.f, 0.f};
+      if (r < TM_ && ((sm >> (r >> 4)) & 1u)) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = a_cc + q, kk = k + i / (CPO ? CPO : 1), c = i % (CPO ? CPO : 1);
+          if (i < GK * CPO && kk < K) {
+            const int n = idx_s[kk * TM_ + r];
+            if (n >= 0) e[q] = p.in[(int64_t)n * p.in_ld + c];
+          }
+        }
+      }
+      return make_float4(e[0], e[1], e[2], e[3]);
+    } else {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (r < TM_ && ((sm >> (r >> 4)) & 1u)) {
+        const int n = idx_s[k * TM_ + r];
+        const int c = c0 + a_cc;
+        if (n >= 0) {
+          const float* src = p.in + (int64_t)n * p.in_ld + c;
+          if (p.vec_a) {
+            if (c < Cin) v = *(const float4*)src;
+          } else {
+            if (c + 0 < Cin) v.x = src[0];
+            if (c + 1 < Cin) v.y = src[1];
+            if (c + 2 < Cin) v.z = src[2];
+            if (c + 3 < Cin) v.w = src[3];
+          }
+        }
+      }
+      return v;
+    }
+  };
   auto load_a = [&](int k, int c0, uint32_t sm) {
 #pragma unroll
-    for (int j = 0; j < A_F4; ++j) {
-      const int r = a_r + ROWS_PER_PASS * j;
-      if (FAST) {
-        // one ds_read (the row's byte offset), one add (this thread's column) and a buffer_load whose SGPR offset is the
-        // step's channel chunk: rows past the tile (clamped), sub-tiles without a neighbour at this offset (all their
-        // rows are absent) and absent neighbours need no test - the descriptor's range check returns zeros for them
-        const int rr = (A_F4 * ROWS_PER_PASS > TM_) ? min(r, TM_ - 1) : r;
-        if (CPO) {
-          // fused offsets: column a_cc of the step belongs to offset k + a_cc / CPO, channel a_cc % CPO
-          const int kk = k + a_cc / (CPO ? CPO : 1);
-          uint32_t off = (uint32_t)idx_s[min(kk, K - 1) * TM_ + rr];
-          if (kk >= K) off = BUF_ABSENT;
-          const f32x4 v = buffer_load_floats<4>(rsrc_in, off + (uint32_t)(a_cc % (CPO ? CPO : 1)) * 4u, 0u);
-          ra[j] = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-          const uint32_t off = (uint32_t)idx_s[k * TM_ + rr];
-          // the last chunk of a layer whose Cin is not a multiple of KC: columns past Cin are never multiplied; their
-          // lanes re-read the row's first columns (col_last) so that no load reaches past a row
-          const uint32_t cb = (!FULL && c0 + KC > Cin) ? col_last : col_bytes;
-          const f32x4 v = buffer_load_floats<4>(rsrc_in, off + cb, (uint32_t)c0 * 4u);
-          ra[j] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-        (void)sm;
-      } else if (CPO) {
-        float e[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r < TM_ && ((sm >> (r >> 4)) & 1u)) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int i = a_cc + q, kk = k + i / (CPO ? CPO : 1), c = i % (CPO ? CPO : 1);
-            if (i < GK * CPO && kk < K) {
-              const int n = idx_s[kk * TM_ + r];
-              if (n >= 0) e[q] = p.in[(int64_t)n * p.in_ld + c];
-            }
-          }
-        }
-        ra[j] = make_float4(e[0], e[1], e[2], e[3]);
-      } else {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < TM_ && ((sm >> (r >> 4)) & 1u)) {
-          const int n = idx_s[k * TM_ + r];
-          const int c = c0 + a_cc;
-          if (n >= 0) {
-            const float* src = p.in + (int64_t)n * p.in_ld + c;
-            if (p.vec_a) {
-              if (c < Cin) v = *(const float4*)src;
-            } else {
-              if (c + 0 < Cin) v.x = src[0];
-              if (c + 1 < Cin) v.y = src[1];
-              if (c + 2 < Cin) v.z = src[2];
-              if (c + 3 < Cin) v.w = src[3];
-            }
-          }
-        }
-        ra[j] = v;
-      }
+    for (int j = 0; j < A_F4; ++j) ra[j] = gather_row(k, c0, sm, j);
+  };
+  auto scatter_row = [&](float* dstbuf, uint32_t sm, int j, const float4& v) {
+    const int r = a_r + ROWS_PER_PASS * j;
+    // FAST: rows of sub-tiles that are inactive at this offset arrive as zeros and are stored like the others (their
+    // matrix ops are skipped anyway) - no per-row mask arithmetic in the loop (skipping their gathers and stores
+    // measured -2 %)
+    if (r < TM_ && (FAST || ((sm >> (r >> 4)) & 1u))) {
+      float2* dst = (float2*)(dstbuf + r * SA + a_cc);
+      dst[0] = make_float2(v.x, v.y);
+      dst[1] = make_float2(v.z, v.w);
     }
   };
   auto store_a = [&](float* dstbuf, uint32_t sm) {
 #pragma unroll
-    for (int j = 0; j < A_F4; ++j) {
-      const int r = a_r + ROWS_PER_PASS * j;
-      // FAST: rows of sub-tiles that are inactive at this offset arrive as zeros and are stored like the others (their
-      // matrix ops are skipped anyway) - no per-row mask arithmetic in the loop (skipping their gathers and stores
-      // measured -2 %)
-      if (r < TM_ && (FAST || ((sm >> (r >> 4)) & 1u))) {
-        float2* dst = (float2*)(dstbuf + r * SA + a_cc);
-        dst[0] = make_float2(ra[j].x, ra[j].y);
-        dst[1] = make_float2(ra[j].z, ra[j].w);
-      }
-    }
+    for (int j = 0; j < A_F4; ++j) scatter_row(dstbuf, sm, j, ra[j]);
   };
 
   // B operands of one k-step: rows c0 + 4 ks + lq of W[k], NT consecutive output channels starting at col0.  Each
@@ -352,7 +361,11 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
   // floats the tuple was copied element by element at the loop back-edge, behind an s_waitcnt vmcnt(0))
   typedef float bvec_t __attribute__((ext_vector_type(NT)));
   typedef float bvec_load_t __attribute__((ext_vector_type(NT), aligned(4)));
-  bvec_t b[KC / 4];
+  // WIDE: a ring of BR = 4 tuples - the reload after k-step ks fetches k-step ks + BR (of this step, or of the next one
+  // once ks + BR passes the chunk), the same prefetch distance in matrix ops with half the registers of a whole chunk
+  constexpr int KS = KC / 4;
+  constexpr int BR = WIDE ? 4 : KS;
+  bvec_t b[BR];
   // FAST: wstep = first weight row of the step (wave-uniform -> scalar registers), b_off = this lane's constant offset;
   // per k-step only a scalar add remains.  K-steps past the channel tail re-read row 0 of the step (never multiplied).
   const int b_off = lq * Cout + col0;
@@ -386,7 +399,7 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
     uint32_t sm_c = sm_n;
     load_a(k_c, c_c, sm_c);
 #pragma unroll
-    for (int ks = 0; ks < KC / 4; ++ks) load_b(step_weights(k_c, c_c), k_c, c_c, ksteps_of(k_c, c_c), ks, b[ks]);
+    for (int ks = 0; ks < BR; ++ks) load_b(step_weights(k_c, c_c), k_c, c_c, ksteps_of(k_c, c_c), ks, b[ks]);
     store_a(As, sm_c);
     advance();
     int k_x = k_n, c_x = c_n;
@@ -498,7 +511,78 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
       buf ^= 1;
       return true;
     };
-    while (step()) {
+    // WIDE form of a step.  Same operands, same order of matrix ops; what differs is how long operands sit in registers:
+    //   * weights: tuple ks % BR is refilled with k-step ks + BR right after the matrix ops of k-step ks;
+    //   * gathers of step x in two halves through ONE float4: half 0 is requested at the start and written to the other
+    //     LDS buffer after the first half of the k-steps, half 1 then takes its place and is written at the end.  Nobody
+    //     reads the other buffer during a step (the barrier at its end hands it over), so the early write needs no
+    //     synchronisation; in the last step of a tile it writes rows nobody will read.
+    auto step_wide = [&]() -> bool {
+      const int kb = have_x ? k_x : 0;
+      const int cb = have_x ? c_x : 0;
+      float* const a_next = As + (buf ^ 1) * (TM_ * SA);
+      ra[0] = gather_row(kb, cb, 0u, 0);
+      const float* a_base = As + buf * (TM_ * SA) + (wm * MR * 16 + li) * SA + lq;
+      const uint32_t smw = (sm_c >> (wm * MR)) & ((1u << MR) - 1u);
+      const int ksteps = ksteps_of(k_c, c_c);
+      const int ksteps_next = ksteps_of(kb, cb);
+      // first weight row of this step and of step x (k-steps past a channel tail re-read row 0 of their step)
+      const uint32_t wrow_c = (uint32_t)(k_c * Cin + c_c);
+      const uint32_t wrow_x = (uint32_t)(kb * Cin + cb);
+      float a_cur[MR];
+#pragma unroll
+      for (int s = 0; s < MR; ++s) a_cur[s] = a_base[s * 16 * SA];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        if (ks < ksteps) {
+          float a_nx[MR];
+          if (ks + 1 < KS) {
+#pragma unroll
+            for (int s = 0; s < MR; ++s) a_nx[s] = a_base[s * 16 * SA + (ks + 1) * 4];
+          }
+#pragma unroll
+          for (int s = 0; s < MR; ++s) {
+            if ((smw >> s) & 1u) {
+#pragma unroll
+              for (int n = 0; n < NT; ++n)
+                acc[s][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s], b[ks % BR][n], acc[s][n], 0, 0, 0);
+            }
+          }
+          if (ks + 1 < KS) {
+#pragma unroll
+            for (int s = 0; s < MR; ++s) a_cur[s] = a_nx[s];
+          }
+        }
+        const int kn = ks + BR < KS ? ks + BR : ks + BR - KS;  // the k-step the ring slot holds next
+        const uint32_t wrow = ks + BR < KS ? wrow_c + (uint32_t)(kn < ksteps ? 4 * kn : 0)
+                                           : wrow_x + (uint32_t)(kn < ksteps_next ? 4 * kn : 0);
+        b[ks % BR] = buffer_load_floats<NT>(rsrc_w, b_off_bytes, wrow * (uint32_t)Cout * 4u);
+        if (ks == KS / 2 - 1) {
+          scatter_row(a_next, 0u, 0, ra[0]);
+          ra[0] = gather_row(kb, cb, 0u, 1);
+        }
+      }
+      ++trace_steps;
+      if (!have_x) return false;
+      scatter_row(a_next, 0u, 1, ra[0]);
+      k_c = k_x;
+      c_c = c_x;
+      sm_c = sm_x;
+      advance();
+      k_x = k_n;
+      c_x = c_n;
+      sm_x = sm_n;
+      have_x = have_n;
+      __syncthreads();
+      buf ^= 1;
+      return true;
+    };
+    if constexpr (WIDE) {
+      while (step_wide()) {
+      }
+    } else {
+      while (step()) {
+      }
     }
   }
 
@@ -566,8 +650,15 @@ __device__ __forceinline__ void conv_tile_body(const ConvParams& p, const int bi
   }
 }
 
+// resident waves per SIMD an instance is compiled for: five for the 64-row WIDE tile (alone or as the main body of the
+// dual launch), no target of their own for the others
+constexpr unsigned wide_waves(int tm, int waves_n, int nt, bool fast, int cpo, bool ring, bool full) {
+  return (tm == 64 && waves_n == 4 && nt == 3 && fast && cpo == 0 && !ring && !full) ? 5u : 1u;
+}
+
 template <int TM_, int WAVES_N, int NT, bool FAST, int CPO = 0, bool RING = false, bool FULL = false>
-__global__ __launch_bounds__(256) void conv_fwd_kernel(ConvParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wide_waves(TM_, WAVES_N, NT, FAST, CPO, RING, FULL))))
+void conv_fwd_kernel(ConvParams p) {
   conv_tile_body<TM_, WAVES_N, NT, FAST, CPO, RING, FULL>(p, (int)blockIdx.x, 0);
 }
 
@@ -578,7 +669,8 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(ConvParams p) {
 // its slot-time idle).  Everything else about a tile - offsets visited, the (k, c) order of every output element's fma
 // chain, hence every result bit - is independent of the tile height.
 template <int TM_, int TAIL_TM, int WAVES_N, int NT, bool FAST>
-__global__ __launch_bounds__(256) void conv_fwd_dual_kernel(ConvParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wide_waves(TM_, WAVES_N, NT, FAST, 0, false, false))))
+void conv_fwd_dual_kernel(ConvParams p) {
   if ((int)blockIdx.x < p.main_blocks)
     conv_tile_body<TM_, WAVES_N, NT, FAST>(p, (int)blockIdx.x, 0);
   else

@@ -19,6 +19,8 @@ the Kabsch / averaging solves run through libsvhip.  Differences that are delibe
 import collections
 import dataclasses
 import os
+import queue
+import threading
 
 import numpy as np
 import torch
@@ -60,6 +62,80 @@ def checkpoint_restore(model, f=None, device="cuda"):
 
 
 ICP_METHODS = ("point2point", "point2plane")
+
+
+class _InlinePoseBackEnd:
+    """predict_stream's pose stages on the consumer's own thread: a group's work is enqueued when it is handed over and
+    collected once the next group's has been enqueued."""
+
+    def __init__(self, engine):
+        self.engine, self.pending = engine, collections.deque()
+
+    def hand_over(self, items):
+        self.pending.append(self.engine._pose_enqueue(items, one_frame=False))
+
+    def ready(self, block):
+        """results in order; block=False: of every group but the newest, block=True: of all"""
+        while len(self.pending) > (0 if block else 1):
+            yield from self.engine._pose_collect(self.pending.popleft())
+
+    def close(self):
+        pass
+
+
+class _ThreadedPoseBackEnd:
+    """predict_stream's pose stages on a second host thread: their launches, blocking size read-backs and result waits
+    never hold up the thread that feeds the segmentation pipeline."""
+
+    def __init__(self, engine):
+        self.engine, self.outstanding = engine, 0  # outstanding: groups handed over whose results have not come back
+        self.jobs, self.done = queue.Queue(), queue.Queue()
+        self.thread = threading.Thread(target=self._worker, name="mrcc-pose", daemon=True)
+        self.thread.start()
+
+    def _worker(self):
+        try:
+            if self.engine.device.index is not None:
+                torch.cuda.set_device(self.engine.device)
+            waiting = None  # one group enqueued ahead of the one being collected
+            while True:
+                items = self.jobs.get()
+                nxt = self.engine._pose_enqueue(items, one_frame=False) if items is not None else None
+                if waiting is not None:
+                    self.done.put(self.engine._pose_collect(waiting))
+                waiting = nxt
+                if items is None:
+                    return
+        except BaseException as e:  # whatever happens on this thread is handed to the consumer, which re-raises it
+            self.done.put(e)
+
+    def hand_over(self, items):
+        self.jobs.put(items)
+        self.outstanding += 1
+
+    def ready(self, block):
+        """results in order; block=False: of the groups the worker has finished, block=True: of all (nothing is handed
+        over after that: the worker collects its last group and ends)"""
+        if block:
+            self.jobs.put(None)
+        while self.outstanding:
+            try:
+                r = self.done.get(block=block, timeout=1.0 if block else None)
+            except queue.Empty:
+                if not block:
+                    return
+                if not self.thread.is_alive() and self.done.empty():  # never wait for a thread that is gone
+                    raise RuntimeError("the pose thread ended without delivering its results")
+                continue
+            if isinstance(r, BaseException):
+                raise r
+            self.outstanding -= 1
+            yield from r
+
+    def close(self):
+        if self.thread.is_alive():
+            self.jobs.put(None)
+        self.thread.join(timeout=60)
 
 
 class InferenceEngine:
@@ -133,10 +209,8 @@ class InferenceEngine:
             rot_cls(in_channels=cfg.DATA.input_channel, out_channels=(10 if compute_confidence else 7)), "ROTATION")
         kp = cfg.INFERENCE.KEY_POINTS
         if kp.backbone == "pointnet2":
-            in_ch = 6 if kp.use_coordinates_as_features else 9
             # the reference feeds cat(points, rgb) = 6 channels either way (app/inference_engine.py:523-528)
             self._key_points_model = restore(PointNet2SSG(num_classes=kp.num_of_keypoints, in_channels=6), "KEY_POINTS")
-            del in_ch
         else:
             head = _classification_head(minkunet.MinkUNet18D, lambda: kp.num_of_keypoints, "RobotNetKeyPoints")
             self._key_points_model = restore(
@@ -275,16 +349,27 @@ class InferenceEngine:
         return (k.backbone != "pointnet2" and r.scale == k.scale and bool(r.center_at_origin) == bool(k.center_at_origin)
                 and not k.use_coordinates_as_features)
 
+    @staticmethod
+    def _prepare_crops(crops_pts, crops_rgb, section):
+        """the crops as the pose network of `section` (INFERENCE.ROTATION / KEY_POINTS) takes them -> (pts, feats): points
+        copied - the caller's arrays are never modified - and centred where the section says so; features are the colours,
+        or the normalised coordinates where the section has use_coordinates_as_features"""
+        pts, feats = [], []
+        for p, f in zip(crops_pts, crops_rgb):
+            p = np.array(np.asarray(p), copy=True)
+            if section.center_at_origin:
+                p, _ = preprocess.center_at_origin(p)
+            if getattr(section, "use_coordinates_as_features", False):
+                f = preprocess.normalize_points(p)
+            pts.append(p)
+            feats.append(f)
+        return pts, feats
+
     def _pose_nets_enqueue(self, crops_pts, crops_rgb, conf_th, one_frame):
         """rotation network AND key-point network (+ its batched selection) on one voxelisation of G crops; returns
         ((rot host view, event, keep), (kp host views, event, keep))"""
         cfg = self._config
-        pts = []
-        for p in crops_pts:
-            p = np.asarray(p)
-            if cfg.INFERENCE.ROTATION.center_at_origin:
-                p, _ = preprocess.center_at_origin(p)
-            pts.append(p)
+        pts, feats = self._prepare_crops(crops_pts, crops_rgb, cfg.INFERENCE.ROTATION)
         G = len(pts)
         runner = self._crop_runner()
 
@@ -296,7 +381,7 @@ class InferenceEngine:
             runner.join()
             return rot, kp
 
-        rot, kp = runner.run(pts, crops_rgb, cfg.INFERENCE.ROTATION.scale, nets, one_frame=one_frame)
+        rot, kp = runner.run(pts, feats, cfg.INFERENCE.ROTATION.scale, nets, one_frame=one_frame)
         (host,), ev, keep = runner.download([rot])
         return (host, ev, keep), runner.download(list(kp))
 
@@ -323,14 +408,9 @@ class InferenceEngine:
         """the rotation network on G crops as one sparse tensor (batch column = crop): enqueued on the crop stream, its
         [G, 7 or 10] output on its way to pinned memory; returns (host view, event, keep-alive)"""
         cfg = self._config
-        pts = []
-        for p in crops_pts:
-            p = np.asarray(p)
-            if cfg.INFERENCE.ROTATION.center_at_origin:
-                p, _ = preprocess.center_at_origin(p)
-            pts.append(p)
+        pts, feats = self._prepare_crops(crops_pts, crops_rgb, cfg.INFERENCE.ROTATION)
         runner = self._crop_runner()
-        out = runner.run(pts, crops_rgb, cfg.INFERENCE.ROTATION.scale, lambda x, field, seg: self._rotation_model(x),
+        out = runner.run(pts, feats, cfg.INFERENCE.ROTATION.scale, lambda x, field, seg: self._rotation_model(x),
                          encoder_only=bool(cfg.INFERENCE.ROTATION.encode_only), one_frame=one_frame)
         (host,), ev, keep = runner.download([out])
         return host, ev, keep
@@ -364,17 +444,8 @@ class InferenceEngine:
         event, keep-alive)"""
         cfg = self._config
         kp = cfg.INFERENCE.KEY_POINTS
-        pts, feats = [], []
-        for p, f in zip(crops_pts, crops_rgb):
-            p = np.array(np.asarray(p), copy=True)
-            if kp.center_at_origin:
-                p, _ = preprocess.center_at_origin(p)
-            if kp.use_coordinates_as_features:
-                f = preprocess.normalize_points(p)
-            pts.append(p)
-            feats.append(f)
+        pts, feats = self._prepare_crops(crops_pts, crops_rgb, kp)
         G = len(pts)
-
         runner = self._crop_runner()
         outs = runner.run(pts, feats, kp.scale, lambda x, field, seg: self._kp_select(x, field, seg, G, conf_th),
                           one_frame=one_frame)
@@ -404,12 +475,7 @@ class InferenceEngine:
         G = len(crops_pts)
         rows, pts, feats, draws, starts = [], [], [], [], []
         with torch.cuda.stream(runner.stream):
-            for g, (p, f) in enumerate(zip(crops_pts, crops_rgb)):
-                points = np.array(np.asarray(p), copy=True)
-                if kp.center_at_origin:
-                    points, _ = preprocess.center_at_origin(points)
-                if kp.use_coordinates_as_features:
-                    f = preprocess.normalize_points(points)
+            for g, (points, f) in enumerate(zip(*self._prepare_crops(crops_pts, crops_rgb, kp))):
                 if len(points) < n_dense:
                     continue
                 if farthest:
@@ -491,11 +557,7 @@ class InferenceEngine:
             ev.synchronize()
             classes = np.where(sel[0].numpy() != 0)[0]
             return raw_points[idx[0].numpy()[classes]], classes, torch.from_numpy(np.array(prob[0].numpy()[classes]))
-        points = np.array(raw_points, copy=True)
-        if kp.center_at_origin:
-            points, _ = preprocess.center_at_origin(points)
-        if kp.use_coordinates_as_features:
-            rgb = preprocess.normalize_points(points)
+        (points,), (rgb,) = self._prepare_crops([raw_points], [rgb], kp)
         rgb_t = rgb if torch.is_tensor(rgb) else torch.from_numpy(np.asarray(rgb)).to(torch.float32)
         with torch.no_grad():
             n_dense = cfg.INFERENCE.num_of_dense_input_points
@@ -541,10 +603,11 @@ class InferenceEngine:
             return ResultDTO(segmentation=np.zeros(self._n_points(data), dtype=np.int64))
         if isinstance(data, PackedCloudDTO):
             # decoded on the device; the pose stages take their crop from the packed records (_pose_enqueue)
-            seg, src = self.predict_segmentation_packed(data.packed, box=data.box, color=data.color)
-            return self._pose_collect(self._pose_enqueue([(data, src, seg)], one_frame=True))[0]
-        rgb = preprocess.normalize_colors(data.rgb)
-        seg = self.predict_segmentation(data.points, rgb)
+            # (labels, src): the source indices travel in the colours' place
+            seg, rgb = self.predict_segmentation_packed(data.packed, box=data.box, color=data.color)
+        else:
+            rgb = preprocess.normalize_colors(data.rgb)
+            seg = self.predict_segmentation(data.points, rgb)
         return self._pose_collect(self._pose_enqueue([(data, rgb, seg)], one_frame=True))[0]
 
     def predict_stream(self, frames, compute_streams=3, group=4, pose_thread=True, seg_group=1):
@@ -574,89 +637,25 @@ class InferenceEngine:
                 window.append((data, rgb))
                 yield data.points, rgb
 
-        cur, pending = [], collections.deque()
         # seg_group > 1: the segmentation stage also runs groups of frames per sparse tensor (predict_segmentation_stream)
         seg_stream = self.predict_segmentation_stream(inputs(), compute_streams=compute_streams, group=seg_group)
-        if not pose_thread:
+        back = (_ThreadedPoseBackEnd if pose_thread else _InlinePoseBackEnd)(self)
+        cur = []
+        try:
             for seg in seg_stream:
                 data, rgb = window.popleft()
                 if isinstance(data, PackedCloudDTO):
                     seg, rgb = seg  # (labels, src): the source indices travel in the colours' place
                 cur.append((data, rgb, seg))
                 if len(cur) >= group:
-                    pending.append(self._pose_enqueue(cur, one_frame=False))
+                    back.hand_over(cur)
                     cur = []
-                    while len(pending) > 1:
-                        yield from self._pose_collect(pending.popleft())
+                yield from back.ready(block=False)
             if cur:
-                pending.append(self._pose_enqueue(cur, one_frame=False))
-            while pending:
-                yield from self._pose_collect(pending.popleft())
-            return
-        import queue
-        import threading
-
-        jobs, done = queue.Queue(), queue.Queue()
-
-        def worker():
-            try:
-                if self.device.index is not None:
-                    torch.cuda.set_device(self.device)
-                waiting = None  # one group enqueued ahead of the one being collected
-                while True:
-                    items = jobs.get()
-                    nxt = self._pose_enqueue(items, one_frame=False) if items is not None else None
-                    if waiting is not None:
-                        done.put(self._pose_collect(waiting))
-                    waiting = nxt
-                    if items is None:
-                        return
-            except BaseException as e:  # whatever happens on this thread is handed to the consumer, which re-raises it
-                done.put(e)
-
-        th = threading.Thread(target=worker, name="mrcc-pose", daemon=True)
-        th.start()
-        outstanding = 0
-
-        def ready(block):
-            nonlocal outstanding
-            while outstanding:
-                try:
-                    r = done.get(block=block, timeout=1.0 if block else None)
-                except queue.Empty:
-                    if not block:
-                        return
-                    if not th.is_alive() and done.empty():  # never wait for a thread that is gone
-                        raise RuntimeError("the pose thread ended without delivering its results")
-                    continue
-                if isinstance(r, BaseException):
-                    raise r
-                outstanding -= 1
-                yield from r
-
-        try:
-            for seg in seg_stream:
-                data, rgb = window.popleft()
-                if isinstance(data, PackedCloudDTO):
-                    seg, rgb = seg
-                cur.append((data, rgb, seg))
-                if len(cur) >= group:
-                    jobs.put(cur)
-                    outstanding += 1
-                    cur = []
-                yield from ready(block=False)
-            if cur:
-                jobs.put(cur)
-                outstanding += 1
-            jobs.put(None)
-            yield from ready(block=True)
+                back.hand_over(cur)
+            yield from back.ready(block=True)
         finally:
-            if th.is_alive():
-                jobs.put(None)
-            th.join(timeout=60)
-
-    def _predict_after_segmentation(self, data, rgb, seg):
-        return self._pose_collect(self._pose_enqueue([(data, rgb, seg)], one_frame=True))[0]
+            back.close()
 
     def _pose_enqueue(self, items, one_frame):
         """items: [(PointCloudDTO, normalised colours, labels)].  Crops the end effector of every frame (host: the labels
@@ -680,12 +679,11 @@ class InferenceEngine:
         handle = {"items": items, "crops": crops, "rot": None, "kp": None}
         if live:
             pts, cols = [c[0] for c in live], [c[1] for c in live]
+            th = cfg.INFERENCE.KEY_POINTS.conf_threshold
             if self._pose_nets_share_voxels():
-                handle["rot"], handle["kp"] = self._pose_nets_enqueue(pts, cols, cfg.INFERENCE.KEY_POINTS.conf_threshold,
-                                                                      one_frame)
+                handle["rot"], handle["kp"] = self._pose_nets_enqueue(pts, cols, th, one_frame)
             else:
                 handle["rot"] = self._rotation_enqueue(pts, cols, one_frame)
-                th = cfg.INFERENCE.KEY_POINTS.conf_threshold
                 if cfg.INFERENCE.KEY_POINTS.backbone == "pointnet2":
                     handle["kp"] = self._pointnet_kp_enqueue(pts, cols, th)
                 else:

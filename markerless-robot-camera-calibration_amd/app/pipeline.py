@@ -9,9 +9,11 @@ Prepared frames are kept alive until the compute stream has finished with them, 
 recycle their memory under a running kernel.
 """
 import collections
+import itertools
 import os
 import time
 
+import numpy as np
 import torch
 
 from .. import MinkowskiEngine as ME
@@ -43,14 +45,6 @@ class PreparedFrame:
         self.sizes = None  # prepare_group: points per frame of the group
         self.stream = None  # compute stream run() put the frame on
         self.result = None
-
-
-def build_unet_plans(cm, levels=4):
-    """Everything a MinkUNet-shaped graph will ask the coordinate manager for (model/backbone/minkunet.py:125-183):
-    3x3x3 maps at strides 1..2^levels, stride-2 down maps and transposed up maps between neighbouring levels, and the
-    offset-range plans of the wide decoder layers on big levels - one sv_frame_plans call (the stride maps it needs come
-    from TensorField.sparse(pyramid_levels=levels), or are built here one by one)."""
-    cm.build_plans(levels)
 
 
 class FramePipeline:
@@ -210,6 +204,14 @@ class _HostSlot:
             self.pts = buf[8 * cap:20 * cap].view(torch.float32).view(cap, 3)
             self.rgb = buf[20 * cap:].view(torch.float32).view(cap, channels)
 
+    def download(self, n, label):
+        """enqueue a frame's device -> host copies on the current stream"""
+        self.labels[:n].copy_(label, non_blocking=True)
+
+    def result(self, n):
+        """the downloaded frame as arrays of its own: the pinned buffer is free for the next frame"""
+        return np.array(self.labels.numpy()[:n])
+
 
 class HostFrameStream:
     """Host arrays in -> per-point labels out, frames overlapped (the reference's consumer is a per-frame loop over
@@ -222,7 +224,14 @@ class HostFrameStream:
     maps / plans there, `stage(x, field)` (the network + slice/argmax) runs on the next compute stream, and `finish`
     (whatever needs host decisions: the largest-cluster rule with its count read-back) plus the D2H copy of the labels
     into pinned memory run on that frame's stream while LATER frames compute.  Results come back in input order and are
-    bit-identical to the synchronous path: the same kernels run on the same data, only their interleaving changes."""
+    bit-identical to the synchronous path: the same kernels run on the same data, only their interleaving changes.
+
+    The unit of work is a GROUP of 1..`group` consecutive frames that go through `stage` as one sparse tensor: `_stage`
+    uploads a group, `_prepare` wraps it, `_finalize` returns the list of its frames' results; `run` takes `group` frames
+    at a time and `run_one` is a group of one.  What differs for other kinds of frame is the slot class (`_Slot`: the
+    pinned buffers and what is downloaded per frame) and `_stage` (PackedFrameStream)."""
+
+    _Slot = _HostSlot
 
     def __init__(self, device, scale, stage, finish=None, levels=4, compute_streams=3, depth=None, stagger_level0=None,
                  one_frame=False, group=1):
@@ -237,7 +246,7 @@ class HostFrameStream:
         # of its own pass) - launches `group` times longer, results delivered a group at a time; `finish` and the download
         # stay per frame
         self.group = max(1, int(group))
-        self._slots = [_HostSlot() for _ in range((self.depth + 2) * self.group)]
+        self._slots = [self._Slot() for _ in range((self.depth + 2) * self.group)]
         self._n = 0
         # host wall time per phase, summed over frames (perf_counter deltas; tools/engine_stream_phases.py prints them)
         self.host_s = {"stage": 0.0, "prepare": 0.0, "launch": 0.0, "finalize": 0.0, "frames": 0}
@@ -248,71 +257,41 @@ class HostFrameStream:
         for slot in self._slots:
             slot.reserve(int(n), channels)
 
-    def _upload_and_prepare(self, points, rgb):
-        import numpy as np
-
-        t0 = time.perf_counter()
+    def _take_slot(self):
+        """the next slot of the ring, once the upload that last used it has left its buffers"""
         slot = self._slots[self._n % len(self._slots)]
         self._n += 1
         if slot.uploaded is not None:
             slot.uploaded.synchronize()
-        n = len(points)
-        rgb_t = rgb if torch.is_tensor(rgb) else None
-        channels = (rgb_t.shape[1] if rgb_t is not None else np.asarray(rgb).shape[1])
-        slot.reserve(n, channels)
-        prep = self.pipe.prep_stream
-        np.copyto(slot.pts.numpy()[:n], np.asarray(points), casting="same_kind")  # float64 sources are rounded here
-        with torch.cuda.stream(prep):  # the points are on their way while the colours are staged
-            d_pts = slot.pts[:n].to(self.device, non_blocking=True)
-            coords4 = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
-            torch.mul(d_pts, self.scale, out=coords4[:, 1:])
-        if rgb_t is not None:
-            slot.rgb[:n].copy_(rgb_t)
-        else:
-            np.copyto(slot.rgb.numpy()[:n], np.asarray(rgb), casting="same_kind")
-        t1 = time.perf_counter()
-        with torch.cuda.stream(prep):
-            d_rgb = slot.rgb[:n].to(self.device, non_blocking=True)
-            slot.uploaded = torch.cuda.Event()
-            slot.uploaded.record(prep)
-        out = self.pipe.prepare(coords4, d_rgb, tag=(slot, d_pts, n))
-        t2 = time.perf_counter()
-        self.host_s["stage"] += t1 - t0
-        self.host_s["prepare"] += t2 - t1
-        self.host_s["frames"] += 1
-        return out
+        return slot
 
-    def _upload_and_prepare_group(self, members):
-        """members: [(points, rgb), ...] host arrays of consecutive frames -> one PreparedFrame over all of them; its tag is
-        the list of (slot, device points, n) per frame."""
-        import numpy as np
+    def _empty(self, rows, cols):
+        """float32 [rows, cols] of the prep stream's memory: a group's (batch, x, y, z) rows or features, filled frame by
+        frame"""
+        with torch.cuda.stream(self.pipe.prep_stream):
+            return torch.empty((rows, cols), dtype=torch.float32, device=self.device)
 
-        if len(members) == 1:
-            out = self._upload_and_prepare(*members[0])
-            out.tag = [out.tag]
-            return out
-        t0 = time.perf_counter()
+    def _fill_rows(self, rows, b, d_pts):
+        """rows of frame b of a group: its position in the batch column, `points * scale` as a float32 product"""
+        rows[:, 0] = float(b)
+        torch.mul(d_pts, self.scale, out=rows[:, 1:])
+
+    def _stage(self, members):
+        """members: [(points, rgb), ...] host arrays of consecutive frames -> (coords4, feats, tags): the group's rows on
+        the device, in flight on the prep stream, and (slot, device points, n) per frame."""
         prep = self.pipe.prep_stream
         sizes = [len(p) for p, _ in members]
         first_rgb = members[0][1]
         channels = first_rgb.shape[1] if torch.is_tensor(first_rgb) else np.asarray(first_rgb).shape[1]
-        with torch.cuda.stream(prep):
-            coords4 = torch.empty((sum(sizes), 4), dtype=torch.float32, device=self.device)
-            feats = torch.empty((sum(sizes), channels), dtype=torch.float32, device=self.device)
-        tags, off, t_stage = [], 0, 0.0
-        for b, (points, rgb) in enumerate(members):
-            slot = self._slots[self._n % len(self._slots)]
-            self._n += 1
-            if slot.uploaded is not None:
-                slot.uploaded.synchronize()
-            n = sizes[b]
+        coords4, feats = self._empty(sum(sizes), 4), self._empty(sum(sizes), channels)
+        tags, off = [], 0
+        for b, ((points, rgb), n) in enumerate(zip(members, sizes)):
+            slot = self._take_slot()
             slot.reserve(n, channels)
-            np.copyto(slot.pts.numpy()[:n], np.asarray(points), casting="same_kind")
+            np.copyto(slot.pts.numpy()[:n], np.asarray(points), casting="same_kind")  # float64 sources are rounded here
             with torch.cuda.stream(prep):  # the points are on their way while the colours are staged
                 d_pts = slot.pts[:n].to(self.device, non_blocking=True)
-                rows = coords4[off:off + n]
-                rows[:, 0] = float(b)
-                torch.mul(d_pts, self.scale, out=rows[:, 1:])
+                self._fill_rows(coords4[off:off + n], b, d_pts)
             if torch.is_tensor(rgb):
                 slot.rgb[:n].copy_(rgb)
             else:
@@ -323,36 +302,21 @@ class HostFrameStream:
                 slot.uploaded.record(prep)
             tags.append((slot, d_pts, n))
             off += n
+        return coords4, feats, tags
+
+    def _prepare(self, members):
+        """a group of 1..`group` consecutive frames -> one PreparedFrame over all of them; its tag is the list of
+        (slot, device points, n, ...) per frame"""
+        t0 = time.perf_counter()
+        coords4, feats, tags = self._stage(members)
         t1 = time.perf_counter()
         out = self.pipe.prepare(coords4, feats, tag=tags)
-        out.sizes = sizes
+        out.sizes = [tag[2] for tag in tags]
         t2 = time.perf_counter()
         self.host_s["stage"] += t1 - t0
         self.host_s["prepare"] += t2 - t1
         self.host_s["frames"] += len(members)
         return out
-
-    def _finalize_group(self, prepared):
-        """per frame of the group: `finish` on its slice of the labels, download; one wait for the whole group"""
-        import numpy as np
-
-        t0 = time.perf_counter()
-        stream = prepared.stream if prepared.stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(stream):
-            off = 0
-            for slot, d_pts, n in prepared.tag:
-                label = prepared.result[off:off + n]
-                if self.finish is not None:
-                    label = self.finish(label, d_pts)
-                slot.labels[:n].copy_(label, non_blocking=True)
-                off += n
-            done = torch.cuda.Event()
-            done.record(stream)
-        done.synchronize()
-        outs = [np.array(slot.labels.numpy()[:n]) for slot, _, n in prepared.tag]
-        prepared.result = prepared.tag = None
-        self.host_s["finalize"] += time.perf_counter() - t0
-        return outs
 
     def _launch(self, prepared):
         t0 = time.perf_counter()
@@ -360,75 +324,55 @@ class HostFrameStream:
         self.host_s["launch"] += time.perf_counter() - t0
 
     def _finalize(self, prepared):
-        import numpy as np
-
+        """per frame of the group: `finish` on its slice of the labels, download; one event and one wait for the whole
+        group -> the list of the frames' results"""
         t0 = time.perf_counter()
-        slot, d_pts, n = prepared.tag
         stream = prepared.stream if prepared.stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.stream(stream):
-            label = prepared.result
-            if self.finish is not None:
-                label = self.finish(label, d_pts)
-            slot.labels[:n].copy_(label, non_blocking=True)
+            off = 0
+            for slot, d_pts, n, *more in prepared.tag:
+                label = prepared.result[off:off + n]
+                if self.finish is not None:
+                    label = self.finish(label, d_pts)
+                slot.download(n, label, *more)
+                off += n
             done = torch.cuda.Event()
             done.record(stream)
         done.synchronize()
-        out = np.array(slot.labels.numpy()[:n])  # leave the pinned buffer free for the next frame
+        outs = [tag[0].result(tag[2]) for tag in prepared.tag]
         prepared.result = prepared.tag = None
         self.host_s["finalize"] += time.perf_counter() - t0
-        return out
+        return outs
 
     def run_one(self, points, rgb):
         """One frame, start to finish (the per-frame call of the reference's loop): staged, uploaded and prepared on the prep
         stream, the network on the compute stream behind it, labels downloaded - nothing is enqueued between a size
         read-back and the kernels it waits for except this frame's own coordinate work."""
         with torch.no_grad():
-            cur = self._upload_and_prepare(points, rgb)
+            cur = self._prepare([(points, rgb)])
             self._launch(cur)
-            return self._finalize(cur)
+            return self._finalize(cur)[0]
 
     def run(self, frames):
         """frames: iterable of (points [N,3], rgb [N,C]) host arrays -> generator of int64 label arrays, in order."""
         pending = collections.deque()
         it = iter(frames)
-        if self.group > 1:
-            import itertools
 
-            def take():
-                members = list(itertools.islice(it, self.group))
-                return self._upload_and_prepare_group(members) if members else None
+        def take():
+            members = list(itertools.islice(it, self.group))
+            return self._prepare(members) if members else None
 
-            with torch.no_grad():
-                nxt = take()
-                while nxt is not None:
-                    cur = nxt
-                    self._launch(cur)
-                    pending.append(cur)
-                    nxt = take()
-                    while len(pending) >= self.depth:
-                        yield from self._finalize_group(pending.popleft())
-                while pending:
-                    yield from self._finalize_group(pending.popleft())
-                self.pipe.drain()
-            return
-        try:
-            first = next(it)
-        except StopIteration:
-            return
         with torch.no_grad():
-            nxt = self._upload_and_prepare(*first)
+            nxt = take()
             while nxt is not None:
                 cur = nxt
-                self._launch(cur)  # asynchronous: the GPU works on `cur` while the host stages the next frame
+                self._launch(cur)  # asynchronous: the GPU works on `cur` while the host stages the next group
                 pending.append(cur)
-                try:
-                    nxt = self._upload_and_prepare(*next(it))
-                except StopIteration:
-                    nxt = None
+                nxt = take()
                 while len(pending) >= self.depth:
-                    yield self._finalize(pending.popleft())
+                    yield from self._finalize(pending.popleft())
             while pending:
-                yield self._finalize(pending.popleft())
+                yield from self._finalize(pending.popleft())
             self.pipe.drain()
 
 
@@ -450,16 +394,27 @@ class _PackedSlot:
             self.src = buf[8 * cap:12 * cap].view(torch.int32)
             self.raw = buf[12 * cap:]
 
+    def download(self, n, label, src):
+        self.labels[:n].copy_(label, non_blocking=True)
+        self.src[:n].copy_(src, non_blocking=True)
+
+    def result(self, n):
+        return np.array(self.labels.numpy()[:n]), np.array(self.src.numpy()[:n])
+
 
 class PackedFrameStream(HostFrameStream):
-    """HostFrameStream for frames that arrive as packed records (utils/packed.py PackedFrame): the same slots, streams,
-    grouping and finalisation, but a frame is never materialised on the host.  The upload step stages the raw bytes into the
-    slot's pinned buffer, copies them to the device on the prep stream and runs sv_unpack_points there (fields decoded,
-    non-finite and out-of-box records dropped in order, colours unpacked through the table of normalised colours), reads the
-    number kept (8 bytes) and forms the (batch, x, y, z) rows from the decoded points exactly as HostFrameStream does
-    (`points * scale` in float32).  Items are (PackedFrame, box or None[, color]); results are (labels int64 [k], src int32 [k]):
-    src[j] is the record the j-th point came from.  `color`: the convention the byte colours stand for ("float64" or
-    "float32", utils/packed.py); the network sees preprocess.normalize_colors of them."""
+    """HostFrameStream for frames that arrive as packed records (utils/packed.py PackedFrame): the same ring of slots,
+    streams, grouping, `run` loop and finalisation, but a frame is never materialised on the host.  Only the staging
+    differs: `_stage_and_unpack` puts a frame's raw bytes into its slot's pinned buffer, copies them to the device on the
+    prep stream and runs sv_unpack_points there (fields decoded, non-finite and out-of-box records dropped in order, colours
+    unpacked through the table of normalised colours); `_stage` does that for every frame of the group, reads the numbers
+    kept back once (8 bytes per frame) and forms the (batch, x, y, z) rows from the decoded points exactly as
+    HostFrameStream does (`points * scale` in float32); the slot (_PackedSlot) also downloads `src`.  Items are
+    (PackedFrame, box or None[, color]); results are (labels int64 [k], src int32 [k]): src[j] is the record the j-th point
+    came from.  `color`: the convention the byte colours stand for ("float64" or "float32", utils/packed.py); the network
+    sees preprocess.normalize_colors of them."""
+
+    _Slot = _PackedSlot
 
     def __init__(self, device, scale, stage, finish=None, color="float64", **kw):
         from ..utils.packed import device_lut_values
@@ -468,7 +423,6 @@ class PackedFrameStream(HostFrameStream):
         super().__init__(device, scale, stage, finish, **kw)
         self.color = color
         self._lut = None
-        self._slots = [_PackedSlot() for _ in self._slots]
 
     def preallocate(self, n, nbytes=None):
         """Pin every slot's buffers for frames of up to n records (nbytes: of raw data, default 32 per record)."""
@@ -484,10 +438,7 @@ class PackedFrameStream(HostFrameStream):
             raise ValueError("a packed frame needs at least one record")
         if frame.rgb_offset < 0:
             raise ValueError("the frame has no rgb field: the segmentation network takes colours")
-        slot = self._slots[self._n % len(self._slots)]
-        self._n += 1
-        if slot.uploaded is not None:
-            slot.uploaded.synchronize()
+        slot = self._take_slot()
         nbytes = frame.nbytes_used
         slot.reserve(frame.n_records, nbytes)
         slot.raw.numpy()[:nbytes] = frame._bytes()[:nbytes]
@@ -500,89 +451,29 @@ class PackedFrameStream(HostFrameStream):
             points, rgb, src, count = frame.unpack(d_raw, box=box, lut=self._lut)
         return slot, points, rgb, src, count
 
-    def _upload_and_prepare(self, frame, box=None, color=None):
-        t0 = time.perf_counter()
-        slot, points, rgb, src, count = self._stage_and_unpack(frame, box, color)
-        with torch.cuda.stream(self.pipe.prep_stream):
-            n = int(count.item())  # waits for this frame's copy and three kernels only
-            if n < 1:
-                raise ValueError("no record of the frame is finite and inside the box")
-            d_pts = points[:n]
-            coords4 = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
-            torch.mul(d_pts, self.scale, out=coords4[:, 1:])
-        t1 = time.perf_counter()
-        out = self.pipe.prepare(coords4, rgb[:n], tag=(slot, d_pts, n, src[:n]))
-        t2 = time.perf_counter()
-        self.host_s["stage"] += t1 - t0
-        self.host_s["prepare"] += t2 - t1
-        self.host_s["frames"] += 1
-        return out
-
-    def _upload_and_prepare_group(self, members):
-        """members: [(PackedFrame, box), ...] of consecutive frames -> one PreparedFrame over all of them (batch column =
-        position in the group); every frame is unpacked before the counts are read back, once for the group"""
-        if len(members) == 1:
-            out = self._upload_and_prepare(*members[0])
-            out.tag = [out.tag]
-            return out
-        t0 = time.perf_counter()
+    def _stage(self, members):
+        """members: [(PackedFrame, box[, color]), ...] of consecutive frames -> (coords4, feats, tags) as HostFrameStream,
+        the tags (slot, device points, n, device src); every frame is unpacked before the counts are read back, once for
+        the group"""
         staged = [self._stage_and_unpack(*m) for m in members]
         with torch.cuda.stream(self.pipe.prep_stream):
+            # the group's one read-back: waits for its frames' copies and three kernels each, nothing else
             sizes = [int(k) for k in torch.cat([s[4] for s in staged]).cpu()]
             if min(sizes) < 1:
                 raise ValueError("no record of a frame is finite and inside the box")
-            coords4 = torch.empty((sum(sizes), 4), dtype=torch.float32, device=self.device)
-            feats = torch.empty((sum(sizes), 3), dtype=torch.float32, device=self.device)
+            coords4 = self._empty(sum(sizes), 4)
             tags, off = [], 0
-            for b, ((slot, points, rgb, src, _), n) in enumerate(zip(staged, sizes)):
+            for b, ((slot, points, _, src, _), n) in enumerate(zip(staged, sizes)):
                 d_pts = points[:n]
-                rows = coords4[off:off + n]
-                rows[:, 0] = float(b)
-                torch.mul(d_pts, self.scale, out=rows[:, 1:])
-                feats[off:off + n].copy_(rgb[:n])
+                self._fill_rows(coords4[off:off + n], b, d_pts)
                 tags.append((slot, d_pts, n, src[:n]))
                 off += n
-        t1 = time.perf_counter()
-        out = self.pipe.prepare(coords4, feats, tag=tags)
-        out.sizes = sizes
-        t2 = time.perf_counter()
-        self.host_s["stage"] += t1 - t0
-        self.host_s["prepare"] += t2 - t1
-        self.host_s["frames"] += len(members)
-        return out
-
-    def _download(self, prepared, tags):
-        """`finish` on every frame's slice of the labels, labels and source indices to pinned memory, one wait"""
-        import numpy as np
-
-        stream = prepared.stream if prepared.stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(stream):
-            off = 0
-            for slot, d_pts, n, d_src in tags:
-                label = prepared.result[off:off + n]
-                if self.finish is not None:
-                    label = self.finish(label, d_pts)
-                slot.labels[:n].copy_(label, non_blocking=True)
-                slot.src[:n].copy_(d_src, non_blocking=True)
-                off += n
-            done = torch.cuda.Event()
-            done.record(stream)
-        done.synchronize()
-        outs = [(np.array(slot.labels.numpy()[:n]), np.array(slot.src.numpy()[:n])) for slot, _, n, _ in tags]
-        prepared.result = prepared.tag = None
-        return outs
-
-    def _finalize(self, prepared):
-        t0 = time.perf_counter()
-        out = self._download(prepared, [prepared.tag])[0]
-        self.host_s["finalize"] += time.perf_counter() - t0
-        return out
-
-    def _finalize_group(self, prepared):
-        t0 = time.perf_counter()
-        outs = self._download(prepared, prepared.tag)
-        self.host_s["finalize"] += time.perf_counter() - t0
-        return outs
+            colours = [s[2][:n] for s, n in zip(staged, sizes)]
+            # one frame hands its colours on as a view: copying them too took the packed stream of tools/ingest_timing.py from
+            # 14.367 to 14.479 ms per frame (spread of the runs 0.099), its host stage from 1.039 to 1.225 ms (profiles/
+            # frame_streams_unified_timing.txt, set A)
+            feats = colours[0] if len(colours) == 1 else torch.cat(colours)
+        return coords4, feats, tags
 
     def run_one(self, frame, box=None):
         """one packed frame, start to finish -> (labels, src)"""

@@ -246,6 +246,27 @@ const char* sv_conv_last_instance(void);
  * A negative value restores the library default (environment SV_CONV_WANT_SCALE / SV_CONV_TAIL).  Results never depend on
  * the instance (one fma chain per output element in every one of them). */
 int sv_conv_set_dispatch(double want_scale, double tail_fraction);
+/* Which instance an sv_conv_fwd_acc call of a shape would run on, asked without running it (host only: no stream, no
+ * device pointer, works on a machine without a GPU).  This is the function the launch itself consults, so the answer is
+ * the "name|fast=F,ring=R,full=U" string sv_conv_last_instance would report after that call.  n shapes per call (a sweep
+ * of every padded row count is millions of questions): shapes_host[n][5] = K, Cin, Cout, Vpad, flags; the answer to shape
+ * i is the NUL-terminated string at names_host + i * name_bytes.
+ * flags: what the rules otherwise read from the call's pointers - */
+#define SV_CONV_SEL_PLAN 1        /* perm / nbr_s / submask given */
+#define SV_CONV_SEL_TILE_ORDER 2  /* tile_order given */
+#define SV_CONV_SEL_VEC_A 4       /* `in` 16-byte aligned, in_ld % 4 == 0 (and Cin % 4 == 0): float4 gathers */
+#define SV_CONV_SEL_BUF_OK 8      /* every operand below the 2 GB buffer extent and `perm` 16-byte aligned */
+#define SV_CONV_SEL_ACC_INIT 16   /* acc_init given */
+#define SV_CONV_SEL_W_ALIGNED 32  /* W 16-byte aligned */
+/* want_scale / tail_fraction as in sv_conv_set_dispatch; a negative value means what a call on this thread would use now
+ * (its sv_conv_set_dispatch setting, else the environment, else the library default).  The SV_CONV_FORCE* experiment
+ * switches are ignored.  Shapes sv_conv_fwd_acc refuses (K outside 1..32, Vpad not a multiple of 128, K > 1 without a
+ * plan) return SV_ERR_INVALID. */
+int sv_conv_select(int64_t n, const int64_t* shapes_host, double want_scale, double tail_fraction, char* names_host,
+                   size_t name_bytes);
+/* Row `index` of the table of tile instances behind sv_conv_fwd: out_host[10] = TM, WAVES_N, NT, CPO (channels per fused
+ * offset, 0 = one offset per step), MR, TN, GK, KC, PFD, USE_FULL.  SV_ERR_INVALID past the end of the table. */
+int sv_conv_tile_info(int index, int* out_host);
 
 /* ---------------------------------------------------------------------------------------------
  * A3/A5 at reduced precision: the opt-in bf16 matrix-core path of the wide layers (the same ME.MinkowskiConvolution /

@@ -37,6 +37,8 @@ SV_FIELD_F32, SV_FIELD_F64 = 7, 8
 SV_UNPACK_BIGENDIAN, SV_UNPACK_KEEP_NONFINITE = 1, 2
 SV_DEPTH_U16, SV_DEPTH_F32 = 4, 7
 SV_RGBD_ALIGNED, SV_RGBD_NEAREST, SV_RGBD_BGR = 1, 2, 4
+SV_CONV_SEL_PLAN, SV_CONV_SEL_TILE_ORDER, SV_CONV_SEL_VEC_A, SV_CONV_SEL_BUF_OK, SV_CONV_SEL_ACC_INIT, SV_CONV_SEL_W_ALIGNED = (
+    1, 2, 4, 8, 16, 32)
 SV_FRAME_REC_HASH, SV_FRAME_REC_K3, SV_FRAME_REC_DOWN, SV_FRAME_REC_UP, SV_FRAME_REC_SPLIT = 1, 2, 3, 4, 5
 
 
@@ -88,6 +90,8 @@ SIGNATURES = {
     ),
     "sv_conv_last_instance": (c_char_p, []),
     "sv_conv_set_dispatch": (c_int, [c_double, c_double]),
+    "sv_conv_select": (c_int, [c_int64, _P, c_double, c_double, _P, c_size_t]),
+    "sv_conv_tile_info": (c_int, [c_int, _P]),
     "sv_frame_maps_arena_bytes": (c_size_t, [c_int64, c_int]),
     "sv_frame_maps_scratch_bytes": (c_size_t, [c_int64]),
     "sv_frame_maps": (c_int, [_P, c_int, c_int64, c_int, _P, c_size_t, _P, c_size_t, _P, _P, _P]),
@@ -218,11 +222,31 @@ def call(name, *args):
     _check(rc, name)
 
 
-def conv_last_instance():
-    """(kernel instance name, {"fast": 0/1, "ring": 0/1, "full": 0/1}) of this thread's last sv_conv_fwd launch."""
-    raw = load().sv_conv_last_instance().decode()
+def _parse_instance(raw):
     name, _, flags = raw.partition("|")
     return name, {k: int(v) for k, v in (kv.split("=") for kv in flags.split(",") if kv)}
+
+
+def conv_last_instance():
+    """(kernel instance name, {"fast": 0/1, "ring": 0/1, "full": 0/1}) of this thread's last sv_conv_fwd launch."""
+    return _parse_instance(load().sv_conv_last_instance().decode())
+
+
+def conv_instance(K, Cin, Cout, Vpad, flags, want_scale=-1.0, tail_fraction=-1.0):
+    """What sv_conv_last_instance would report after an sv_conv_fwd_acc call of this shape, as the raw string
+    "name|fast=F,ring=R,full=U" (sv_conv_select: the library's own dispatch rules, asked on the host; flags = SV_CONV_SEL_*;
+    negative scale / tail = this thread's current dispatch)"""
+    name = ctypes.create_string_buffer(128)
+    call("sv_conv_select", 1, (c_int64 * 5)(K, Cin, Cout, Vpad, flags), want_scale, tail_fraction, name, 128)
+    return name.value.decode()
+
+
+def conv_tiles():
+    """The library's table of tile instances (sv_conv_tile_info): [(TM, WAVES_N, NT, CPO, MR, TN, GK, KC, PFD, USE_FULL)]"""
+    rows, out = [], (c_int * 10)()
+    while load().sv_conv_tile_info(len(rows), out) == 0:
+        rows.append(tuple(out))
+    return rows
 
 
 class conv_dispatch:

@@ -4,8 +4,9 @@
 // MinkowskiBatchNorm(eval) (+ residual) (+ ReLU / LeakyReLU): model/backbone/minkunet.py:125-187,
 // model/backbone/resnet.py:95-127 (BasicBlock via ME), model/robotnet_segmentation.py:55-64.
 //
-// This file: the ABI entry points, the tiled kernel and its instance selection; the special-shape kernels (thin layers,
-// conv0, narrow linear) are in sv_conv_special.hip, what both share in sv_conv_params.h.
+// This file: the ABI entry points, the tiled kernel and its launchers; the special-shape kernels (thin layers, conv0, narrow
+// linear) are in sv_conv_special.hip, what both share in sv_conv_params.h.  WHICH instance a call runs on - the tile table,
+// the candidate lists, the rules - is in sv_conv_select.h and nowhere else.
 //
 // Work decomposition (details at ConvCfg / conv_fwd_kernel below, measurements in DESIGN.md 4.1)
 //   * a workgroup (4 waves) owns one tile of TM output rows (in the plan's mask-sorted order) x TN output channels;
@@ -18,52 +19,23 @@
 // Numerics: every output element is ONE f32 fma chain over (k ascending, c ascending) — the MFMA is a k-ordered
 // fmaf chain (MI355X guide §3) — so results are bitwise reproducible and match oracle/sv_oracle.c exactly.
 // A missing neighbour contributes fma(0, w, acc) = acc.
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <array>
+#include <utility>
 #include <vector>
 
 #include "sv_conv_params.h"
 
 namespace sv {
 
-// name of the kernel instance the last sv_conv_fwd call of this thread launched, "name|fast=F,ring=R,full=U" (the names
-// mrcc_amd/profiling.py predicts; sv_conv_last_instance(): tests and the bench's per-kernel records read it back)
+// name of the kernel instance the last sv_conv_fwd call of this thread launched, "name|fast=F,ring=R,full=U"
+// (conv_choice_name; sv_conv_last_instance(): tests and the bench's per-kernel records read it back)
 static thread_local char g_last_instance[128] = "";
 // per-thread override of the dispatch thresholds (sv_conv_set_dispatch): < 0 = the library default / environment
 static thread_local double g_want_scale_override = -1.0;
 static thread_local double g_tail_override = -1.0;
-void note_instance(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_last_instance, sizeof(g_last_instance), fmt, ap);
-  va_end(ap);
-}
-#ifndef SV_CONV_WANT_SCALE_DEFAULT
-#define SV_CONV_WANT_SCALE_DEFAULT 0.3  // see select_and_launch
-#endif
-#ifndef SV_CONV_TAIL_DEFAULT
-#define SV_CONV_TAIL_DEFAULT 0.15  // share of the plan tiles (the cheapest) that chip-filling launches run as half-height tiles
-#endif
-// input channels per pipeline step: short tiles (used on small pyramid levels, where a launch is bound by the latency
-// of a tile's sequential step chain) take wider chunks, i.e. fewer barriers / gather round trips per tile
-constexpr int chunk_for(int tm, int waves_n) {
-  if (waves_n == 1) return tm <= 64 ? 128 : 64;  // tall-narrow tiles (small levels): few, fat steps
-  if (waves_n == 2) return tm <= 32 ? 128 : (tm <= 64 ? 64 : 32);
-  return tm <= 16 ? 128 : (tm <= 32 ? 64 : 32);
-}
 
-// Workgroup = 4 waves.  Tile = TM_ output rows (mask-sorted plan order) x TN output channels.
-//   WAVES_N waves split the columns (NT 16-wide MFMA column tiles each), WAVES_M = 4 / WAVES_N split the rows.
-//   Column tiles are INTERLEAVED: MFMA column j of tile n is output channel n0 + wn*NT*16 + NT*j + n, so a lane's B
-//   operands for its NT tiles are NT consecutive floats of a weight row (one dwordxNT load straight from L2/HBM into
-//   registers — the weight slab is not shared between waves, an LDS round trip would be pure overhead) and the
-//   epilogue stores NT consecutive floats per lane.
-// Thin layers (Cin = 3 / 16 / 32 / 64) FUSE several kernel offsets into one pipeline step (CPO = channels per offset,
-// compile-time, = Cin): the A tile row of a step is the concatenation of GK neighbours' Cin channels, which is a
-// contiguous run of GK * Cin rows of W[K][Cin][Cout] - the same ascending (k, c) accumulation chain in 27 * Cin / 128
-// steps instead of 27.  CPO = 0 is the one-offset-per-step form used by the wide layers.
-constexpr int fused_offsets(int cpo) { return cpo == 0 ? 1 : (cpo < 8 ? 27 : (128 / cpo > 0 ? 128 / cpo : 1)); }
 constexpr int lds_row_stride(int kc) {
   // smallest stride >= kc + 2 for which the 16x16x4 operand read (lane = row li, k-offset lq: word li * SA + lq)
   // touches 64 distinct LDS banks: SA mod 64 = 34, or SA = 4 * odd
@@ -71,23 +43,19 @@ constexpr int lds_row_stride(int kc) {
     if (sa % 64 == 34 || (sa % 4 == 0 && (sa / 4) % 2 == 1)) return sa;
 }
 
+// Workgroup = 4 waves.  Tile = TM_ output rows (mask-sorted plan order) x TN output channels; the table of tiles and the
+// constants selection reads (MR .. USE_FULL) are in sv_conv_select.h, the ones only the kernel needs here.
+//   Column tiles are INTERLEAVED: MFMA column j of tile n is output channel n0 + wn*NT*16 + NT*j + n, so a lane's B
+//   operands for its NT tiles are NT consecutive floats of a weight row (one dwordxNT load straight from L2/HBM into
+//   registers — the weight slab is not shared between waves, an LDS round trip would be pure overhead) and the
+//   epilogue stores NT consecutive floats per lane.
 template <int TM_, int WAVES_N, int NT, int CPO = 0>
 struct ConvCfg {
+  static constexpr ConvTile T = conv_tile(TM_, WAVES_N, NT, CPO);
   static constexpr int WAVES_M = 4 / WAVES_N;
-  static constexpr int MR = TM_ / WAVES_M / 16;  // 16-row sub-tiles per wave
-  static constexpr int TN = WAVES_N * NT * 16;   // output channels per workgroup
-  static constexpr int GK = fused_offsets(CPO);  // kernel offsets per pipeline step
-  static constexpr int KC = CPO ? (GK * CPO + 3) / 4 * 4 : chunk_for(TM_, WAVES_N);  // A columns per step
+  static constexpr int MR = T.mr, TN = T.tn, GK = T.gk, KC = T.kc, PFD = T.pfd;
+  static constexpr bool USE_FULL = T.use_full;
   static constexpr int SA = lds_row_stride(KC);  // A row stride in floats
-  // A-operand prefetch distance in k-steps: enough matrix work (MR * NT ops of 32 cycles) to cover ~250 cycles
-  // (big tiles, MR * NT >= 6: one k-step, their waves hide the rest behind each other)
-  static constexpr int PFD_RAW = MR * NT >= 6 ? 1 : (8 + MR * NT - 1) / (MR * NT);
-  static constexpr int PFD = PFD_RAW > KC / 4 ? KC / 4 : PFD_RAW;
-  // the FULL form (see the kernel) pays where a k-step is one or two matrix ops and the per-k-step bookkeeping of
-  // the general form dominates; on the 64-row tile it gained nothing and compiles to 107 VGPRs (four
-  // waves per SIMD) where the general form's WIDE step fits five (94-95 VGPRs, conv_tile_body); on 16x128 tiles it
-  // measured slower (profiles/r01_conv_full_form.txt)
-  static constexpr bool USE_FULL = (MR * NT == 1) || (TM_ == 32 && WAVES_N == 4 && NT == 3) || (TM_ == 16 && NT == 3);
   static constexpr int F4_PER_ROW = KC / 4;      // float4 per gathered row and step
   static constexpr int ROWS_PER_PASS = 256 / F4_PER_ROW;
   static constexpr int A_F4 = (TM_ + ROWS_PER_PASS - 1) / ROWS_PER_PASS;  // float4 gathers per thread and step
@@ -702,211 +670,102 @@ static int launch_traced(ConvParams& q, unsigned grid, int tm, int wn, int nt, h
   return SV_OK;
 }
 
-template <int TM_, int WAVES_N, int NT, int CPO = 0>
-static int launch_conv(const ConvParams& p, hipStream_t stream) {
+// launches tile <TM_, WAVES_N, NT, CPO> in the form the choice names (conv_tile_form)
+template <int TM_, int WAVES_N, int NT, int CPO>
+static int launch_conv(const ConvParams& p, hipStream_t stream, const ConvChoice& c) {
   using Cfg = ConvCfg<TM_, WAVES_N, NT, CPO>;
   ConvParams q = p;
   q.ntiles = (int)(p.Vpad / TM_);
   q.ny = (p.Cout + Cfg::TN - 1) / Cfg::TN;
   dim3 grid((unsigned)(q.ntiles * q.ny));
-  const bool fast = p.vec_a && p.buf_ok && (p.Cout % Cfg::TN == 0);
-  // launches of at most ~4 workgroups per CU are bound by the latency of one wave's step chain, not by the matrix
-  // pipe: their waves read the A operands several k-steps ahead (register ring); fuller launches hide that latency
-  // behind co-resident waves and are a few % faster with the plain one-step-ahead read
-  const bool ring = Cfg::PFD > 1 && grid.x <= 1024;
   constexpr bool F = (CPO % 4 == 0);  // odd channel counts (Cin = 3) only exist in the guarded form
   const size_t lds = Cfg::lds_bytes(p.K);
-  // FULL: no partial channel chunk anywhere in the layer
-  const bool full = Cfg::USE_FULL && (CPO ? (p.K % Cfg::GK == 0) : (p.Cin % Cfg::KC == 0));
-  const int rc = launch_traced(q, grid.x, TM_, WAVES_N, NT, stream, [&] {
-    if (F && fast && full) {
-      if (ring)
+  return launch_traced(q, grid.x, TM_, WAVES_N, NT, stream, [&] {
+    if (c.full) {
+      if (c.ring)
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, F, CPO, (Cfg::PFD > 1), (F && Cfg::USE_FULL)>), grid, dim3(256), lds, stream, q);
       else
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, F, CPO, false, (F && Cfg::USE_FULL)>), grid, dim3(256), lds, stream, q);
-    } else if (F && fast) {
-      if (ring)
+    } else if (c.fast) {
+      if (c.ring)
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, F, CPO, (Cfg::PFD > 1)>), grid, dim3(256), lds, stream, q);
       else
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, F, CPO, false>), grid, dim3(256), lds, stream, q);
     } else {
-      if (ring)
+      if (c.ring)
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, false, CPO, (Cfg::PFD > 1)>), grid, dim3(256), lds, stream, q);
       else
         hipLaunchKernelGGL((conv_fwd_kernel<TM_, WAVES_N, NT, false, CPO, false>), grid, dim3(256), lds, stream, q);
     }
   });
-  if (rc != SV_OK) return rc;
-  {
-    const bool f = F && fast;
-    if (CPO)
-      note_instance("conv_fwd_kernel<%d, %d, %d, fused %d>|fast=%d,ring=%d,full=%d", TM_, WAVES_N, NT, CPO, (int)f, (int)ring,
-                    (int)(f && full));
-    else
-      note_instance("conv_fwd_kernel<%d, %d, %d>|fast=%d,ring=%d,full=%d", TM_, WAVES_N, NT, (int)f, (int)ring, (int)(f && full));
-  }
-  return SV_OK;
 }
 
 // dual-body launch (conv_fwd_dual_kernel): TM_-row tiles for the expensive plan tiles, TAIL_TM-row tiles for the cheapest
-// `tail_fraction` of them.  Returns SV_ERR_INVALID without launching when the layer does not qualify.
+// c.tail128 of them (conv_select says when a layer qualifies)
 template <int TM_, int TAIL_TM, int WAVES_N, int NT>
-static int launch_conv_dual(const ConvParams& p, hipStream_t stream, double tail_fraction) {
+static int launch_conv_dual(const ConvParams& p, hipStream_t stream, const ConvChoice& c) {
   using Main = ConvCfg<TM_, WAVES_N, NT, 0>;
   using Tail = ConvCfg<TAIL_TM, WAVES_N, NT, 0>;
-  const bool fast = p.vec_a && p.buf_ok && (p.Cout % Main::TN == 0);
-  const int n128 = (int)(p.Vpad / PLAN_TILE);
-  const int tail128 = (int)(n128 * tail_fraction);
-  if (!fast || !p.tile_order || tail128 < 1 || tail128 >= n128) return SV_ERR_INVALID;
   ConvParams q = p;
   q.ny = p.Cout / Main::TN;
-  q.main_tiles128 = n128 - tail128;
+  q.main_tiles128 = (int)(p.Vpad / PLAN_TILE) - c.tail128;
   q.main_blocks = q.main_tiles128 * (PLAN_TILE / TM_) * q.ny;
   q.ntiles = (int)(p.Vpad / TM_);
-  const unsigned grid = (unsigned)(q.main_blocks + tail128 * (PLAN_TILE / TAIL_TM) * q.ny);
+  const unsigned grid = (unsigned)(q.main_blocks + c.tail128 * (PLAN_TILE / TAIL_TM) * q.ny);
   const size_t lds = Main::lds_bytes(p.K) > Tail::lds_bytes(p.K) ? Main::lds_bytes(p.K) : Tail::lds_bytes(p.K);
-  const int rc = launch_traced(q, grid, TM_, WAVES_N, NT, stream, [&] {
+  return launch_traced(q, grid, TM_, WAVES_N, NT, stream, [&] {
     hipLaunchKernelGGL((conv_fwd_dual_kernel<TM_, TAIL_TM, WAVES_N, NT, true>), dim3(grid), dim3(256), lds, stream, q);
   });
-  if (rc != SV_OK) return rc;
-  note_instance("conv_fwd_dual_kernel<%d, %d, %d, %d>|fast=1,ring=0,full=0", TM_, TAIL_TM, WAVES_N, NT);
-  return SV_OK;
 }
 
-// ---- instance selection ------------------------------------------------------------------------------------------
-// A tile is processed sequentially (K * Cin / KC steps) and streams K*Cin*TN weights + its gathered rows through one CU,
-// so the choice trades per-CU cache bandwidth (tall tiles, few column slices) against parallelism / tail (many tiles).
-// Candidates are listed from least to most traffic; the first one that puts `want` workgroups on the chip wins,
-// otherwise the one with the most workgroups.
-struct Candidate {
-  int tm, wn, nt;
-  int64_t want;  // chosen when it yields at least this many workgroups (measured on the Cfg-2 pyramid, profiles/)
-  int cpo;       // fused-offset form for this Cin (0 = one offset per step)
-};
+// one launcher per row of CONV_TILES (sv_conv_select.h): the table IS the list of instantiations
+typedef int (*ConvLauncher)(const ConvParams&, hipStream_t, const ConvChoice&);
+template <size_t... I>
+static constexpr std::array<ConvLauncher, sizeof...(I)> conv_launchers(std::index_sequence<I...>) {
+  return {{&launch_conv<CONV_TILES[I].tm, CONV_TILES[I].wn, CONV_TILES[I].nt, CONV_TILES[I].cpo>...}};
+}
+static constexpr auto CONV_LAUNCHERS = conv_launchers(std::make_index_sequence<N_CONV_TILES>{});
 
-template <int TM_, int WAVES_N, int NT, int CPO = 0>
-static bool try_launch(const Candidate& c, const ConvParams& p, hipStream_t stream, int& rc) {
-  if (c.tm == TM_ && c.wn == WAVES_N && c.nt == NT && c.cpo == CPO) {
-    rc = launch_conv<TM_, WAVES_N, NT, CPO>(p, stream);
-    return true;
-  }
-  return false;
+// SV_CONV_FORCE* (experiments only) override WHICH tile a layer that reaches the lists runs on; its form stays
+// conv_tile_form's.  True when a switch applies to the shape: `tile` is then the row of CONV_TILES, or -1 (error set) when
+// the tile it names is not instantiated.
+static bool forced_tile(const ConvShape& s, int& tile) {
+  int tm = 0, wn = 0, nt = 0, cpo = 0, cout = 0;
+  long long vmin = 0, vmax = 0;
+  const char* f;
+  bool hit = false;
+  if ((f = getenv("SV_CONV_FORCE_RANGE")))  // "vmin:vmax:cout:tm,wn,nt": one level's layers only
+    hit = sscanf(f, "%lld:%lld:%d:%d,%d,%d", &vmin, &vmax, &cout, &tm, &wn, &nt) == 6 && s.Vpad >= vmin && s.Vpad <= vmax &&
+          s.Cout == cout && s.K > 1;
+  if (!hit && (f = getenv("SV_CONV_FORCE_DENSE")))  // "vmin:cout:tm,wn,nt": dense (K = 1) layers of one width
+    hit = sscanf(f, "%lld:%d:%d,%d,%d", &vmin, &cout, &tm, &wn, &nt) == 5 && s.Vpad >= vmin && s.Cout == cout && s.K == 1;
+  if (!hit && (f = getenv("SV_CONV_FORCE")))  // "tm,wn,nt[,cpo]"
+    hit = sscanf(f, "%d,%d,%d,%d", &tm, &wn, &nt, &cpo) >= 3;
+  if (!hit) return false;
+  tile = find_conv_tile(tm, wn, nt, cpo);
+  if (tile < 0) set_error("sv_conv_fwd: no kernel instance <%d,%d,%d> cpo %d", tm, wn, nt, cpo);
+  return true;
 }
 
-static int launch_candidate(const Candidate& c, const ConvParams& p, hipStream_t stream) {
-  int rc = SV_ERR_INVALID;
-  if (try_launch<128, 4, 3>(c, p, stream, rc) || try_launch<128, 2, 3>(c, p, stream, rc) ||
-      try_launch<128, 1, 3>(c, p, stream, rc) || try_launch<64, 4, 3>(c, p, stream, rc) ||
-      try_launch<64, 2, 3>(c, p, stream, rc) || try_launch<64, 1, 3>(c, p, stream, rc) ||
-      try_launch<32, 4, 3>(c, p, stream, rc) || try_launch<32, 2, 3>(c, p, stream, rc) ||
-      try_launch<16, 4, 3>(c, p, stream, rc) ||
-      try_launch<128, 4, 2>(c, p, stream, rc) || try_launch<128, 2, 2>(c, p, stream, rc) ||
-      try_launch<128, 1, 2>(c, p, stream, rc) || try_launch<64, 4, 2>(c, p, stream, rc) ||
-      try_launch<64, 2, 2>(c, p, stream, rc) || try_launch<64, 1, 2>(c, p, stream, rc) ||
-      try_launch<32, 4, 2>(c, p, stream, rc) || try_launch<32, 2, 2>(c, p, stream, rc) ||
-      try_launch<16, 4, 2>(c, p, stream, rc) ||
-      try_launch<64, 4, 1>(c, p, stream, rc) || try_launch<32, 4, 1>(c, p, stream, rc) ||
-      try_launch<16, 4, 1>(c, p, stream, rc) || try_launch<128, 2, 1>(c, p, stream, rc) ||
-      try_launch<64, 2, 1>(c, p, stream, rc) || try_launch<32, 2, 1>(c, p, stream, rc) ||
-      try_launch<128, 1, 1>(c, p, stream, rc) || try_launch<64, 1, 1>(c, p, stream, rc) ||
-      // fused-offset forms of the thin layers
-      try_launch<64, 2, 1, 3>(c, p, stream, rc) || try_launch<32, 2, 1, 3>(c, p, stream, rc) ||
-      try_launch<64, 2, 1, 32>(c, p, stream, rc) || try_launch<32, 2, 1, 32>(c, p, stream, rc) ||
-      try_launch<32, 4, 1, 32>(c, p, stream, rc) || try_launch<16, 4, 1, 32>(c, p, stream, rc) ||
-      try_launch<32, 4, 1, 64>(c, p, stream, rc) || try_launch<16, 4, 1, 64>(c, p, stream, rc))
-    return rc;
-  set_error("sv_conv_fwd: no kernel instance <%d,%d,%d> cpo %d", c.tm, c.wn, c.nt, c.cpo);
-  return SV_ERR_INVALID;
-}
-
-static int64_t candidate_wgs(const Candidate& c, const ConvParams& p) {
-  const int tn = c.wn * c.nt * 16;
-  return (p.Vpad / c.tm) * ((p.Cout + tn - 1) / tn);
-}
-
-static int select_and_launch(const ConvParams& p, hipStream_t stream) {
-  // The last entry of a list serves the small pyramid levels, where a layer is a few hundred short workgroups and its
-  // duration is the serial (offset, chunk) chain of one of them: 16-row tiles with 128-channel chunks are fastest
-  // there (tools/sweep_small.sh, profiles/r01_conv_small_level_sweep.txt).
-  static const Candidate wide3[] = {{64, 4, 3, 2500}, {32, 4, 3, 1500}, {32, 2, 3, 0}};
-  // Cout % 128 == 0 (384): settled-clock sweeps of every level, profiles/r02_conv_instance_sweep.txt.  Below the
-  // chip-filling size the 16-row tile in its FULL form (Cin a multiple of its 128-channel step: 384, 512) wins at every
-  // level (level 1: 96.4 TFLOP/s against 90.1 for 64x128, level 3: 41 against 34 for 16x128); with a partial last chunk
-  // (Cin 416 / 448, the first conv after a concatenation) it only wins once 64x128 tiles no longer fill the chip
-  // ({32,4,3} between them: inside the frame pipeline level 2 - 432 workgroups of 32 x 192 - is 0.8 % of a frame faster on
-  // 32-row tiles although they are 25 % slower than the 16-row tiles alone: half the weight traffic beside the chip-filling
-  // launches of the other frames; 64.3 against 63.8 frames/s, three alternating runs, tools/ab_env.sh)
-  static const Candidate wide3_128[] = {{64, 4, 3, 2500}, {64, 4, 2, 1200}, {32, 4, 3, 1200}, {16, 4, 3, 0}};
-  static const Candidate wide3_128_full[] = {{64, 4, 3, 2500}, {32, 4, 3, 1200}, {16, 4, 3, 0}};
-  static const Candidate wide2[] = {{128, 4, 2, 1300}, {64, 4, 2, 1500}, {32, 4, 2, 1500}, {32, 2, 2, 0}};
-  static const Candidate wide2_64[] = {{128, 4, 2, 1300}, {64, 4, 2, 1500}, {32, 4, 2, 1500}, {16, 4, 1, 0}};  // % 64
-  static const Candidate c64[] = {{64, 4, 1, 1500}, {32, 4, 1, 1500}, {16, 4, 1, 0}};
-  static const Candidate c32[] = {{128, 2, 1, 1500}, {64, 2, 1, 1500}, {32, 2, 1, 0}};
-  static const Candidate c16[] = {{128, 1, 1, 600}, {64, 1, 1, 0}};
-  const Candidate* list;
-  int n;
-  const int Cout = p.Cout;
-  if (Cout > 128 && (Cout % 192 == 0 || Cout % 96 == 0 || Cout > 2048)) {
-    if (Cout % 128 != 0) { list = wide3; n = 3; }
-    else if (p.Cin % 128 == 0 && p.vec_a) { list = wide3_128_full; n = 3; }
-    else { list = wide3_128; n = 4; }
-  }
-  else if (Cout > 64) { list = Cout % 64 == 0 ? wide2_64 : wide2; n = 4; }
-  else if (Cout > 32) { list = c64; n = 3; }
-  else if (Cout > 16) { list = c32; n = 3; }
-  else { list = c16; n = 2; }
-  // thin layers: fused-offset forms (the input row is at most 256 B, so one offset per step would be all overhead)
-  static const Candidate f3[] = {{64, 2, 1, 3000, 3}, {32, 2, 1, 0, 3}};
-  static const Candidate f32_32[] = {{64, 2, 1, 3000, 32}, {32, 2, 1, 0, 32}};
-  static const Candidate f32_64[] = {{32, 4, 1, 1500, 32}, {16, 4, 1, 0, 32}};
-  static const Candidate f64_64[] = {{32, 4, 1, 1500, 64}, {16, 4, 1, 0, 64}};
-  if (p.K > 1) {
-    if (p.Cin == 3 && Cout > 16 && Cout <= 32) { list = f3; n = 2; }
-    else if (p.Cin == 32 && p.vec_a && Cout == 32) { list = f32_32; n = 2; }
-    else if (p.Cin == 32 && p.vec_a && Cout == 64) { list = f32_64; n = 2; }
-    else if (p.Cin == 64 && p.vec_a && (Cout == 64 || Cout == 128)) { list = f64_64; n = 2; }
-  }
-  if (const char* f = getenv("SV_CONV_FORCE_RANGE")) {  // "vmin:vmax:cout:tm,wn,nt": one level's layers only (experiments)
-    long long vmin = 0, vmax = 0;
-    int cout = 0;
-    Candidate c = {0, 0, 0, 0, 0};
-    if (sscanf(f, "%lld:%lld:%d:%d,%d,%d", &vmin, &vmax, &cout, &c.tm, &c.wn, &c.nt) == 6 && p.Vpad >= vmin && p.Vpad <= vmax &&
-        p.Cout == cout && p.K > 1)
-      return launch_candidate(c, p, stream);
-  }
-  if (const char* f = getenv("SV_CONV_FORCE_DENSE")) {  // "vmin:cout:tm,wn,nt": dense (K = 1) layers of one width (experiments)
-    long long vmin = 0;
-    int cout = 0;
-    Candidate c = {0, 0, 0, 0, 0};
-    if (sscanf(f, "%lld:%d:%d,%d,%d", &vmin, &cout, &c.tm, &c.wn, &c.nt) == 5 && p.Vpad >= vmin && p.Cout == cout && p.K == 1)
-      return launch_candidate(c, p, stream);
-  }
-  if (const char* f = getenv("SV_CONV_FORCE")) {  // "tm,wn,nt[,cpo]": experiments only
-    Candidate c = {0, 0, 0, 0, 0};
-    if (sscanf(f, "%d,%d,%d,%d", &c.tm, &c.wn, &c.nt, &c.cpo) >= 3) return launch_candidate(c, p, stream);
-  }
-  // The `want` figures of the lists were measured one launch at a time (profiles/*_conv_instance_sweep.txt).  Inside the
-  // two-stream frame pipeline the taller tile wins earlier: its weight traffic per flop is lower (level 1, 384 -> 384:
-  // 64-row tiles read W once per 64 rows, 16-row tiles once per 16 - alone on the GPU both run at ~107 TFLOP/s, with
-  // perfect weight locality the 16-row tile would gain 7 %), and the launch tail that costs the short grid alone is
-  // filled by the neighbour frame's kernels.  Scaling every threshold by 0.3 moves level 1 (830 workgroups of 64 x 192)
-  // onto the dual-body launch and leaves levels 2-4 where they were: frames/s 60.9 -> 62.0 (0.15: 62.1, 0.08: 61.1,
-  // 0.03: 60.7; three alternating runs each).
-  static const double want_scale =
+// the dispatch knobs a call on this thread uses now: sv_conv_set_dispatch's override, else the environment, else the default
+static void effective_dispatch(double& want_scale, double& tail_fraction) {
+  static const double env_want_scale =
       getenv("SV_CONV_WANT_SCALE") ? atof(getenv("SV_CONV_WANT_SCALE")) : SV_CONV_WANT_SCALE_DEFAULT;
-  // chip-filling 384-wide layers: 64-row tiles, and 32-row tiles for the cheapest plan tiles at the end of the grid
-  static const double tail_fraction = getenv("SV_CONV_TAIL") ? atof(getenv("SV_CONV_TAIL")) : SV_CONV_TAIL_DEFAULT;
-  const double ws = g_want_scale_override >= 0.0 ? g_want_scale_override : want_scale;
-  const double tf = g_tail_override >= 0.0 ? g_tail_override : tail_fraction;
-  for (int i = 0; i < n; ++i)
-    if ((double)candidate_wgs(list[i], p) >= ws * (double)list[i].want) {
-      const Candidate& c = list[i];
-      if (c.tm == 64 && c.wn == 4 && c.nt == 3 && c.cpo == 0 && tf > 0.0 &&
-          launch_conv_dual<64, 32, 4, 3>(p, stream, tf) == SV_OK)
-        return SV_OK;
-      return launch_candidate(c, p, stream);
-    }
-  return launch_candidate(list[n - 1], p, stream);
+  static const double env_tail = getenv("SV_CONV_TAIL") ? atof(getenv("SV_CONV_TAIL")) : SV_CONV_TAIL_DEFAULT;
+  want_scale = g_want_scale_override >= 0.0 ? g_want_scale_override : env_want_scale;
+  tail_fraction = g_tail_override >= 0.0 ? g_tail_override : env_tail;
+}
+
+static int launch_choice(const ConvChoice& c, const ConvParams& p, hipStream_t stream) {
+  switch (c.kind) {
+    case CONV_FIRST_MFMA: return launch_conv_first_mfma(p, stream);
+    case CONV_FIRST_LAYER: return launch_conv_first_layer(p, stream);
+    case CONV_THIN: return launch_conv_thin(p, stream);
+    case CONV_THIN_LDS: return launch_conv_thin_lds(p, stream);
+    case CONV_NARROW: return launch_linear_narrow(p, stream);
+    case CONV_DUAL: return launch_conv_dual<64, 32, 4, 3>(p, stream, c);
+    default: return CONV_LAUNCHERS[find_conv_tile(c.tm, c.wn, c.nt, c.cpo)](p, stream, c);
+  }
 }
 
 }  // namespace sv
@@ -993,12 +852,50 @@ extern "C" int sv_conv_fwd_acc(const float* in, int64_t V_in, int64_t in_ld, int
   p.trace = nullptr;
   p.main_blocks = 0;
   p.main_tiles128 = 0;
-  if (has_plan && K > 1 && K <= 27 && Cin == 3 && Cout == 32 && !acc_init) {
-    if (p.buf_ok) return launch_conv_first_mfma(p, stream);
-    return launch_conv_first_layer(p, stream);  // the thread-per-voxel kernel with 64-bit addresses
+  const ConvShape shape = {K, Cin, Cout, Vpad, has_plan, tile_order != nullptr, p.vec_a != 0, p.buf_ok != 0, acc_init != nullptr,
+                           ((uintptr_t)W & 15) == 0, g_want_scale_override >= 1.0};
+  double want_scale, tail_fraction;
+  effective_dispatch(want_scale, tail_fraction);
+  ConvChoice c = conv_select(shape, want_scale, tail_fraction);
+  int forced;
+  if ((c.kind == CONV_TILE || c.kind == CONV_DUAL) && forced_tile(shape, forced)) {
+    if (forced < 0) return SV_ERR_INVALID;
+    c = conv_tile_form(CONV_TILES[forced], shape);
   }
-  if (has_plan && K > 1 && K <= 32 && Cin == 32 && Cout == 32 && p.vec_a && p.buf_ok && !acc_init)
-    return launch_conv_thin(p, stream, sv::g_want_scale_override >= 1.0);
-  if (!has_plan && K == 1 && Cout <= 4 && p.vec_a && Cin >= 64 && !acc_init) return launch_linear_narrow(p, stream);
-  return select_and_launch(p, stream);
+  const int rc = launch_choice(c, p, stream);
+  if (rc == SV_OK) conv_choice_name(c, g_last_instance, sizeof(g_last_instance));
+  return rc;
+}
+
+extern "C" int sv_conv_select(int64_t n, const int64_t* shapes_host, double want_scale, double tail_fraction, char* names_host,
+                              size_t name_bytes) {
+  SV_CHECK_ARG(n >= 0 && (n == 0 || (shapes_host && names_host)) && name_bytes > 0, "null pointer");
+  SV_CHECK_ARG(tail_fraction < 1.0, "tail_fraction must be below 1");
+  double ws, tf;
+  effective_dispatch(ws, tf);
+  const bool alone = want_scale >= 0.0 ? want_scale >= 1.0 : g_want_scale_override >= 1.0;
+  if (want_scale >= 0.0) ws = want_scale;
+  if (tail_fraction >= 0.0) tf = tail_fraction;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t* s = shapes_host + 5 * i;
+    const int64_t K = s[0], Cin = s[1], Cout = s[2], Vpad = s[3], flags = s[4];
+    SV_CHECK_ARG(Cin > 0 && Cin <= INT32_MAX && Cout > 0 && Cout <= INT32_MAX && K >= 1 && K <= 32, "bad channel / kernel volume");
+    SV_CHECK_ARG(Vpad > 0 && Vpad % PLAN_TILE == 0, "Vpad must be a positive multiple of 128");
+    SV_CHECK_ARG((flags & SV_CONV_SEL_PLAN) || K == 1, "K > 1 needs a plan");
+    SV_CHECK_ARG(!(flags & SV_CONV_SEL_VEC_A) || Cin % 4 == 0, "float4 gathers need Cin % 4 == 0");
+    const ConvShape shape = {(int)K, (int)Cin, (int)Cout, Vpad, (flags & SV_CONV_SEL_PLAN) != 0, (flags & SV_CONV_SEL_TILE_ORDER) != 0,
+                             (flags & SV_CONV_SEL_VEC_A) != 0, (flags & SV_CONV_SEL_BUF_OK) != 0, (flags & SV_CONV_SEL_ACC_INIT) != 0,
+                             (flags & SV_CONV_SEL_W_ALIGNED) != 0, alone};
+    conv_choice_name(conv_select(shape, ws, tf), names_host + (size_t)i * name_bytes, name_bytes);
+  }
+  return SV_OK;
+}
+
+extern "C" int sv_conv_tile_info(int index, int* out_host) {
+  SV_CHECK_ARG(index >= 0 && index < N_CONV_TILES, "no such row of the tile table");
+  SV_CHECK_ARG(out_host, "null pointer");
+  const ConvTile& t = CONV_TILES[index];
+  const int row[10] = {t.tm, t.wn, t.nt, t.cpo, t.mr, t.tn, t.gk, t.kc, t.pfd, (int)t.use_full};
+  for (int i = 0; i < 10; ++i) out_host[i] = row[i];
+  return SV_OK;
 }

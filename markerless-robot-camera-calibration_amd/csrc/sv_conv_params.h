@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "sv_common.h"
+#include "sv_conv_select.h"
 
 namespace sv {
 
@@ -48,13 +49,11 @@ struct ConvParams {
   int main_tiles128;          //   tile_order[0, main_tiles128), the rest the tail shape over tile_order[main_tiles128, ..)
 };
 
-constexpr int PLAN_TILE = SV_TILE_ROWS;  // plans (perm / nbr_s / submask) are laid out in 128-row tiles
-// records the name of the kernel instance a launch chose, "name|fast=F,ring=R,full=U" (sv_conv_last_instance)
-void note_instance(const char* fmt, ...);
-// launchers of the special-shape kernels (sv_conv_special.hip); `alone`: the caller said that the GPU holds one frame
+// launchers of the special-shape kernels (sv_conv_special.hip), one per ConvKind that conv_select() names
 int launch_conv_first_mfma(const ConvParams& p, hipStream_t stream);
 int launch_conv_first_layer(const ConvParams& p, hipStream_t stream);
-int launch_conv_thin(const ConvParams& p, hipStream_t stream, bool alone);
+int launch_conv_thin(const ConvParams& p, hipStream_t stream);
+int launch_conv_thin_lds(const ConvParams& p, hipStream_t stream);
 int launch_linear_narrow(const ConvParams& p, hipStream_t stream);
 
 // Buffer addressing of the FAST instances.  Measured with tools/mfma_probe.py on gfx950: a `global_load` with a 64-bit

@@ -484,7 +484,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_thin_lds_kernel(ConvParams p,
   }
 }
 
-static int launch_conv_thin_lds(const ConvParams& p, hipStream_t stream) {
+int launch_conv_thin_lds(const ConvParams& p, hipStream_t stream) {
   // <gathers in flight, waves per workgroup, next tile's table requested during the current tile>: measured at 88k / 26k voxels
   // (tools/hbm_layers_microbench.py, profiles/r04_thin_variants.txt): <2,16,no> 33.9 / 19.3 us (126 VGPRs, no spills),
   // <2,16,yes> 36.9 / 18.7, <4,16,no> 38.5 / 20.2 (14 registers spilled at the 128-VGPR limit of a 16-wave workgroup),
@@ -513,7 +513,6 @@ static int launch_conv_thin_lds(const ConvParams& p, hipStream_t stream) {
     SV_HIP(hipMemsetAsync(q.trace, 0, (size_t)grid * WAVES * 12 * sizeof(unsigned long long), stream));
   }
   hipLaunchKernelGGL((conv_thin_lds_kernel<32, 32, D, WAVES>), dim3((unsigned)grid), dim3(WAVES * 64), lds, stream, q, n_sub);
-  note_instance("conv_thin_lds_kernel<32, 32>|fast=1,ring=0,full=1");
   SV_LAUNCH_CHECK();
   if (trace) {
     std::vector<unsigned long long> h((size_t)grid * WAVES * 12);
@@ -550,20 +549,18 @@ static int launch_conv_thin_lds(const ConvParams& p, hipStream_t stream) {
   return SV_OK;
 }
 
-int launch_conv_thin(const ConvParams& p, hipStream_t stream, bool alone) {
+int launch_conv_thin(const ConvParams& p, hipStream_t stream) {
   // one 16-row sub-tile per wave, four offsets in flight: 24 us for block1's 32->32 at level 1 (26.5k voxels) against 35 us
   // on the LDS-staged fused-offset tile, 49 against 84 us at 88k voxels (2.65 TB/s on algorithmic gather-bytes).  Two
   // sub-tiles per wave (shared weight registers) 27-28 / 48 us, three or six offsets in flight 26 / 51-54 us.
   // Round 4: the layer's weights resident in LDS, one 16-wave workgroup per CU (conv_thin_lds_kernel) - for a GPU that holds
   // ONE frame (the caller said so: sv_conv_set_dispatch(want_scale >= 1), the per-frame InferenceEngine.predict path and
-  // every measurement of a layer alone).  Its workgroup needs a whole CU - 145 KB of LDS, sixteen wave slots at 126 VGPRs -
+  // every measurement of a layer alone; the rule itself is conv_select's).  Its workgroup needs a whole CU - 145 KB of LDS, sixteen wave slots at 126 VGPRs -
   // and beside the convolutions of other frames a CU only drains completely when a launch ends: inside the three-stream
   // pipeline its launches wait 0.2-3.6 ms for CUs (profiles/r04_bench_kernel_by_grid.txt, r04_cfg5_kernel_by_grid.txt) and
   // predict_stream loses 4 % (profiles/r04_ab_thin_in_pipeline.txt); there the four-wave workgroups of conv_thin_kernel,
   // which fit the slot any finishing convolution workgroup frees, stay the choice.  Same bits either way.
-  if (alone && p.K <= 27 && (((uintptr_t)p.W) & 15) == 0) return launch_conv_thin_lds(p, stream);
   hipLaunchKernelGGL((conv_thin_kernel<32, 32, 1, 4>), dim3((unsigned)(p.Vpad / 64)), dim3(256), 0, stream, p);
-  note_instance("conv_thin_kernel<32, 32>|fast=1,ring=0,full=1");
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -646,7 +643,6 @@ int launch_conv_first_mfma(const ConvParams& p, hipStream_t stream) {
   const unsigned groups = (unsigned)(p.Vpad / 64);
   hipLaunchKernelGGL((conv_first_mfma_kernel<32>), dim3(groups > cap ? cap : groups), dim3(256), 0, stream, p);
   SV_LAUNCH_CHECK();
-  note_instance("conv_first_mfma_kernel<3, 32>|fast=1,ring=0,full=1");
   return SV_OK;
 }
 
@@ -655,7 +651,6 @@ int launch_conv_first_layer(const ConvParams& p, hipStream_t stream) {
   // against 16 us: the gathers are repeated per slice)
   dim3 grid((unsigned)((p.Vpad + 255) / 256), 1);
   hipLaunchKernelGGL((conv_first_layer_kernel<3, 32, 1>), grid, dim3(256), 0, stream, p);
-  note_instance("conv_first_layer_kernel<3, 32>|fast=0,ring=0,full=0");
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
@@ -668,7 +663,6 @@ int launch_linear_narrow(const ConvParams& p, hipStream_t stream) {
     case 3: hipLaunchKernelGGL((linear_narrow_kernel<3>), grid, dim3(256), 0, stream, p); break;
     default: hipLaunchKernelGGL((linear_narrow_kernel<4>), grid, dim3(256), 0, stream, p); break;
   }
-  note_instance("linear_narrow_kernel<%d>|fast=0,ring=0,full=0", p.Cout < 4 ? p.Cout : 4);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

@@ -1,12 +1,16 @@
 """Live per-kernel timing with HIP events on the stream the kernels are launched on (torch's current stream).
 
 bench.py installs a KernelTimer; nn.conv_forward reports each sv_conv_fwd launch to it with the quantities the
-roofline needs (kernel offsets K, Cin, Cout, output rows, and the device-side pair count of the plan).  Nothing is
+roofline needs (kernel offsets K, Cin, Cout, output rows, and the device-side pair count of the plan).  Which launches a
+timer restricted to some kernels (`only`) times is decided by asking the library which instance it would launch
+(conv_kernel_config); the name a record carries is the one the library reports after the launch.  Nothing is
 read back inside the timed region: events and pair counts are resolved after the final synchronize.
 """
 import math
 
 import torch
+
+from . import _lib
 
 TIMER = None  # set by bench.py
 # Optional list: nn.conv_forward appends (instance name, {"fast", "ring", "full"}, K, Cin, Cout, rows) per launch, as
@@ -18,76 +22,18 @@ INSTANCE_LOG = None
 # for dw) - tests check which layers a training precision really put on the bf16 kernels.
 TRAIN_LOG = None
 
-_CANDIDATES = {
-    "wide3": [(64, 4, 3, 2500), (32, 4, 3, 1500), (32, 2, 3, 0)],
-    "wide3_128": [(64, 4, 3, 2500), (64, 4, 2, 1200), (32, 4, 3, 1200), (16, 4, 3, 0)],
-    "wide3_128_full": [(64, 4, 3, 2500), (32, 4, 3, 1200), (16, 4, 3, 0)],  # Cin a multiple of the 16-row tile's 128-channel step
-    "wide2": [(128, 4, 2, 1300), (64, 4, 2, 1500), (32, 4, 2, 1500), (32, 2, 2, 0)],
-    "wide2_64": [(128, 4, 2, 1300), (64, 4, 2, 1500), (32, 4, 2, 1500), (16, 4, 1, 0)],
-    "c64": [(64, 4, 1, 1500), (32, 4, 1, 1500), (16, 4, 1, 0)],
-    "c32": [(128, 2, 1, 1500), (64, 2, 1, 1500), (32, 2, 1, 0)],
-    "c16": [(128, 1, 1, 600), (64, 1, 1, 0)],
-}
 
-
-import os  # noqa: E402
-
-# the same experiment switches select_and_launch() reads (tools/sweep_pipeline.sh, tools/ab_env*.sh vary them); what a launch
-# really ran on is reported by the library itself: _lib.conv_last_instance()
-CONV_TAIL_FRACTION = float(os.environ.get("SV_CONV_TAIL", "0.15"))  # SV_CONV_TAIL_DEFAULT of csrc/sv_conv.hip
-CONV_WANT_SCALE = float(os.environ.get("SV_CONV_WANT_SCALE", "0.3"))  # SV_CONV_WANT_SCALE_DEFAULT of csrc/sv_conv.hip
-
-
-_FUSED = {  # (Cin, Cout) -> candidates of the fused-offset form (thin layers, K > 1)
-    (32, 32): [(64, 2, 1, 3000), (32, 2, 1, 0)],
-    (32, 64): [(32, 4, 1, 1500), (16, 4, 1, 0)],
-    (64, 64): [(32, 4, 1, 1500), (16, 4, 1, 0)],
-    (64, 128): [(32, 4, 1, 1500), (16, 4, 1, 0)],
-}
-
-
-def conv_kernel_config(Cout, Vpad, Cin=None, K=1):
-    """Mirror of select_and_launch() in csrc/sv_conv.hip -> kernel instance name: conv_fwd_kernel<TM, WAVES_N, NT>,
-    with ", fused Cin" appended for the fused-offset form of the thin layers."""
-    if K == 1 and Cout <= 4 and Cin is not None and Cin >= 64 and Cin % 4 == 0:
-        return f"linear_narrow_kernel<{Cout}>"  # dense rows only; every K = 1 layer of the path is dense
-    if K > 1 and Cin == 3 and Cout == 32:
-        return "conv_first_mfma_kernel<3, 32>"  # (conv_first_layer_kernel, thread per voxel, beyond the 2 GB buffer extent)
-    if K > 1 and Cin == 32 and Cout == 32:
-        # conv_thin_lds_kernel (weights resident in LDS, one 16-wave workgroup per CU) under sv_conv_set_dispatch(>= 1): one
-        # frame alone on the GPU; the recorded name is the library's (sv_conv_last_instance), this one only gates timing
-        return "conv_thin_kernel<32, 32>"
-    fused = None
-    if K > 1 and Cin is not None:
-        if Cin == 3 and 16 < Cout <= 32:
-            fused = [(64, 2, 1, 3000), (32, 2, 1, 0)]
-        else:
-            fused = _FUSED.get((Cin, Cout))
-    if fused is not None:
-        cands = fused
-    elif Cout > 128 and (Cout % 192 == 0 or Cout % 96 == 0 or Cout > 2048):
-        if Cout % 128 != 0:
-            cands = _CANDIDATES["wide3"]
-        else:
-            cands = _CANDIDATES["wide3_128_full" if (Cin is not None and Cin % 128 == 0) else "wide3_128"]
-    elif Cout > 64:
-        cands = _CANDIDATES["wide2_64" if Cout % 64 == 0 else "wide2"]
-    elif Cout > 32:
-        cands = _CANDIDATES["c64"]
-    elif Cout > 16:
-        cands = _CANDIDATES["c32"]
-    else:
-        cands = _CANDIDATES["c16"]
-    suffix = f", fused {Cin}>" if fused is not None else ">"
-    for tm, wn, nt, want in cands:
-        tn = wn * nt * 16
-        if (Vpad // tm) * ((Cout + tn - 1) // tn) >= want * CONV_WANT_SCALE:
-            if ((tm, wn, nt) == (64, 4, 3) and fused is None and K > 1 and Cin is not None and Cin % 4 == 0
-                    and Cout % tn == 0 and CONV_TAIL_FRACTION > 0 and int((Vpad // 128) * CONV_TAIL_FRACTION) >= 1):
-                return "conv_fwd_dual_kernel<64, 32, 4, 3>"  # chip-filling layer: half-height tiles at the end of the grid
-            return f"conv_fwd_kernel<{tm}, {wn}, {nt}{suffix}"
-    tm, wn, nt, _ = cands[-1]
-    return f"conv_fwd_kernel<{tm}, {wn}, {nt}{suffix}"
+def conv_kernel_config(Cout, Vpad, Cin, K=1):
+    """Name of the kernel instance the library would launch for a layer (sv_conv_select: the dispatch rules themselves,
+    asked on the host) as nn.conv_forward calls it: a kernel map has a plan with its tile order and dense rows (K = 1) have
+    none, the input allows float4 gathers iff Cin % 4 == 0, every operand is aligned and below the 2 GB buffer extent, the
+    launch is a first pass (no acc_init), and the dispatch is this thread's (_lib.conv_dispatch)."""
+    flags = _lib.SV_CONV_SEL_BUF_OK | _lib.SV_CONV_SEL_W_ALIGNED
+    if K > 1:
+        flags |= _lib.SV_CONV_SEL_PLAN | _lib.SV_CONV_SEL_TILE_ORDER
+    if Cin % 4 == 0:
+        flags |= _lib.SV_CONV_SEL_VEC_A
+    return _lib.conv_instance(K, Cin, Cout, Vpad, flags).partition("|")[0]
 
 
 class KernelTimer:

@@ -1,121 +1,39 @@
-"""Which kernel instance, in which form, a public fp32 sparse-convolution call runs on - restated from the C++ - and the
-table of cases that pins every reachable one (tests/test_conv_instances_cpu.py: completeness, tests/test_gpu_conv_instances.py:
-bit-exactness against the oracle).
+"""Which kernel instance, in which form, a public fp32 sparse-convolution call runs on - asked of the library itself - and
+the table of cases that pins every reachable one (tests/test_conv_instances_cpu.py: completeness,
+tests/test_gpu_conv_instances.py: bit-exactness against the oracle).
 
-The restatement follows sv_conv_fwd_acc (csrc/sv_conv.hip: the special-shape kernels), select_and_launch (the candidate
-lists and their thresholds), launch_conv (the FAST / RING / FULL form of a tile) and launch_conv_dual.  It is written from
-that code alone; profiling.conv_kernel_config is a second, older mirror of the names only, and the CPU test holds the two
-against each other.
+The rules live in csrc/sv_conv_select.h and nowhere else; sv_conv_select / sv_conv_tile_info answer on the host, so
+everything here works without a GPU.
 """
 from collections import namedtuple
-from functools import lru_cache
 
-PLAN_TILE = 128
+import numpy as np
+
+from mrcc_amd import _lib
+
+PLAN_TILE = _lib.SV_TILE_ROWS
 WANT_SCALE_DEFAULT = 0.3   # SV_CONV_WANT_SCALE_DEFAULT
 TAIL_DEFAULT = 0.15        # SV_CONV_TAIL_DEFAULT
 
-
-# ---- ConvCfg<TM, WAVES_N, NT, CPO> -------------------------------------------------------------------------------
-def chunk_for(tm, waves_n):
-    if waves_n == 1:
-        return 128 if tm <= 64 else 64
-    if waves_n == 2:
-        return 128 if tm <= 32 else (64 if tm <= 64 else 32)
-    return 128 if tm <= 16 else (64 if tm <= 32 else 32)
-
-
-def fused_offsets(cpo):
-    if cpo == 0:
-        return 1
-    if cpo < 8:
-        return 27
-    return 128 // cpo if 128 // cpo > 0 else 1
-
-
 TileCfg = namedtuple("TileCfg", "MR TN GK KC PFD USE_FULL")
+_TILES = {row[:4]: TileCfg(*row[4:9], bool(row[9])) for row in _lib.conv_tiles()}
+# the instantiations of the tiled kernel, (TM, WAVES_N, NT, CPO): the rows of the library's tile table
+INSTANTIATED = list(_TILES)
 
 
-@lru_cache(maxsize=None)
 def tile_cfg(tm, wn, nt, cpo=0):
     """the per-tile constants of ConvCfg that decide a launch's form"""
-    waves_m = 4 // wn
-    mr = tm // waves_m // 16
-    tn = wn * nt * 16
-    gk = fused_offsets(cpo)
-    kc = (gk * cpo + 3) // 4 * 4 if cpo else chunk_for(tm, wn)
-    pfd_raw = 1 if mr * nt >= 6 else (8 + mr * nt - 1) // (mr * nt)
-    pfd = min(pfd_raw, kc // 4)
-    use_full = (mr * nt == 1) or (tm == 32 and wn == 4 and nt == 3) or (tm == 16 and nt == 3)
-    return TileCfg(mr, tn, gk, kc, pfd, use_full)
+    return _TILES[(tm, wn, nt, cpo)]
 
 
-# the 34 instantiations of launch_candidate(), (TM, WAVES_N, NT, CPO)
-INSTANTIATED = (
-    [(tm, wn, 3, 0) for tm, wn in ((128, 4), (128, 2), (128, 1), (64, 4), (64, 2), (64, 1), (32, 4), (32, 2), (16, 4))] +
-    [(tm, wn, 2, 0) for tm, wn in ((128, 4), (128, 2), (128, 1), (64, 4), (64, 2), (64, 1), (32, 4), (32, 2), (16, 4))] +
-    [(tm, wn, 1, 0) for tm, wn in ((64, 4), (32, 4), (16, 4), (128, 2), (64, 2), (32, 2), (128, 1), (64, 1))] +
-    [(64, 2, 1, 3), (32, 2, 1, 3), (64, 2, 1, 32), (32, 2, 1, 32), (32, 4, 1, 32), (16, 4, 1, 32), (32, 4, 1, 64),
-     (16, 4, 1, 64)])
-
-# ---- select_and_launch: candidate lists (tm, wn, nt, want, cpo) ----------------------------------------------------
-WIDE3 = [(64, 4, 3, 2500, 0), (32, 4, 3, 1500, 0), (32, 2, 3, 0, 0)]
-WIDE3_128 = [(64, 4, 3, 2500, 0), (64, 4, 2, 1200, 0), (32, 4, 3, 1200, 0), (16, 4, 3, 0, 0)]
-WIDE3_128_FULL = [(64, 4, 3, 2500, 0), (32, 4, 3, 1200, 0), (16, 4, 3, 0, 0)]
-WIDE2 = [(128, 4, 2, 1300, 0), (64, 4, 2, 1500, 0), (32, 4, 2, 1500, 0), (32, 2, 2, 0, 0)]
-WIDE2_64 = [(128, 4, 2, 1300, 0), (64, 4, 2, 1500, 0), (32, 4, 2, 1500, 0), (16, 4, 1, 0, 0)]
-C64 = [(64, 4, 1, 1500, 0), (32, 4, 1, 1500, 0), (16, 4, 1, 0, 0)]
-C32 = [(128, 2, 1, 1500, 0), (64, 2, 1, 1500, 0), (32, 2, 1, 0, 0)]
-C16 = [(128, 1, 1, 600, 0), (64, 1, 1, 0, 0)]
-F3 = [(64, 2, 1, 3000, 3), (32, 2, 1, 0, 3)]
-F32_32 = [(64, 2, 1, 3000, 32), (32, 2, 1, 0, 32)]
-F32_64 = [(32, 4, 1, 1500, 32), (16, 4, 1, 0, 32)]
-F64_64 = [(32, 4, 1, 1500, 64), (16, 4, 1, 0, 64)]
-ALL_LISTS = (WIDE3, WIDE3_128, WIDE3_128_FULL, WIDE2, WIDE2_64, C64, C32, C16, F3, F32_32, F32_64, F64_64)
+def _flags(has_plan, vec_a, buf_ok, acc_init, w_aligned=True):
+    return ((_lib.SV_CONV_SEL_PLAN | _lib.SV_CONV_SEL_TILE_ORDER if has_plan else 0) | (_lib.SV_CONV_SEL_VEC_A if vec_a else 0) |
+            (_lib.SV_CONV_SEL_BUF_OK if buf_ok else 0) | (_lib.SV_CONV_SEL_ACC_INIT if acc_init else 0) |
+            (_lib.SV_CONV_SEL_W_ALIGNED if w_aligned else 0))
 
 
-@lru_cache(maxsize=None)
-def candidate_list(K, Cin, Cout, vec_a):
-    if Cout > 128 and (Cout % 192 == 0 or Cout % 96 == 0 or Cout > 2048):
-        if Cout % 128 != 0:
-            cands = WIDE3
-        elif Cin % 128 == 0 and vec_a:
-            cands = WIDE3_128_FULL
-        else:
-            cands = WIDE3_128
-    elif Cout > 64:
-        cands = WIDE2_64 if Cout % 64 == 0 else WIDE2
-    elif Cout > 32:
-        cands = C64
-    elif Cout > 16:
-        cands = C32
-    else:
-        cands = C16
-    if K > 1:
-        if Cin == 3 and 16 < Cout <= 32:
-            cands = F3
-        elif Cin == 32 and vec_a and Cout == 32:
-            cands = F32_32
-        elif Cin == 32 and vec_a and Cout == 64:
-            cands = F32_64
-        elif Cin == 64 and vec_a and Cout in (64, 128):
-            cands = F64_64
-    return cands
-
-
-@lru_cache(maxsize=None)
-def _tile_name(tm, wn, nt, cpo):
-    return f"conv_fwd_kernel<{tm}, {wn}, {nt}, fused {cpo}>" if cpo else f"conv_fwd_kernel<{tm}, {wn}, {nt}>"
-
-
-def _tile_launch(tm, wn, nt, cpo, K, Cin, Cout, Vpad, vec_a, buf_ok):
-    """launch_conv<TM, WAVES_N, NT, CPO>: (name, fast, ring, full) as note_instance() writes them"""
-    cfg = tile_cfg(tm, wn, nt, cpo)
-    grid = (Vpad // tm) * ((Cout + cfg.TN - 1) // cfg.TN)
-    fast = vec_a and buf_ok and Cout % cfg.TN == 0
-    ring = cfg.PFD > 1 and grid <= 1024
-    f = (cpo % 4 == 0) and fast
-    full = cfg.USE_FULL and ((K % cfg.GK == 0) if cpo else (Cin % cfg.KC == 0))
-    return _tile_name(tm, wn, nt, cpo), int(f), int(ring), int(f and full)
+def _key(raw):
+    return key(*_lib._parse_instance(raw))
 
 
 def dispatch_key(K, Cin, Cout, Vpad, has_plan, vec_a, buf_ok, acc_init, want_scale=WANT_SCALE_DEFAULT,
@@ -123,35 +41,9 @@ def dispatch_key(K, Cin, Cout, Vpad, has_plan, vec_a, buf_ok, acc_init, want_sca
     """(name, fast, ring, full) of sv_conv_last_instance() after the call.  vec_a: the input view allows float4 gathers
     (Cin and its row stride multiples of 4, 16-byte aligned start); buf_ok: every operand inside the 2 GB buffer extent
     and `perm` 16-byte aligned; want_scale >= 1 stands for conv_dispatch(1.0) - one frame alone on the GPU, which also
-    moves the thin layers onto the LDS-weights kernel (w_aligned: the weight pointer is 16-byte aligned)."""
-    assert Vpad % PLAN_TILE == 0 and Vpad > 0 and 1 <= K <= 32 and (has_plan or K == 1)
-    assert not vec_a or Cin % 4 == 0
-    if has_plan and 1 < K <= 27 and Cin == 3 and Cout == 32 and not acc_init:
-        if buf_ok:
-            return "conv_first_mfma_kernel<3, 32>", 1, 0, 1
-        return "conv_first_layer_kernel<3, 32>", 0, 0, 0
-    if has_plan and K > 1 and Cin == 32 and Cout == 32 and vec_a and buf_ok and not acc_init:
-        if want_scale >= 1.0 and K <= 27 and w_aligned:
-            return "conv_thin_lds_kernel<32, 32>", 1, 0, 1
-        return "conv_thin_kernel<32, 32>", 1, 0, 1
-    if not has_plan and K == 1 and Cout <= 4 and vec_a and Cin >= 64 and not acc_init:
-        return f"linear_narrow_kernel<{min(Cout, 4)}>", 0, 0, 0
-    cands = candidate_list(K, Cin, Cout, vec_a)
-    chosen = cands[-1]
-    for c in cands:
-        tm, wn, nt, want, cpo = c
-        tn = wn * nt * 16
-        if float((Vpad // tm) * ((Cout + tn - 1) // tn)) >= want_scale * float(want):
-            chosen = c
-            if tm == 64 and wn == 4 and nt == 3 and cpo == 0 and tail_fraction > 0.0:
-                # launch_conv_dual<64, 32, 4, 3>: needs the FAST form, a plan's tile_order and a tail of 1 .. n128 - 1 tiles
-                n128 = Vpad // PLAN_TILE
-                tail128 = int(n128 * tail_fraction)
-                if vec_a and buf_ok and Cout % tile_cfg(64, 4, 3).TN == 0 and has_plan and 1 <= tail128 < n128:
-                    return "conv_fwd_dual_kernel<64, 32, 4, 3>", 1, 0, 0
-            break
-    tm, wn, nt, _, cpo = chosen
-    return _tile_launch(tm, wn, nt, cpo, K, Cin, Cout, Vpad, vec_a, buf_ok)
+    moves the thin layers onto the LDS-weights kernel (w_aligned: the weight pointer is 16-byte aligned).  A plan comes
+    with its tile order, as every plan nn.conv_forward passes does."""
+    return _key(_lib.conv_instance(K, Cin, Cout, Vpad, _flags(has_plan, vec_a, buf_ok, acc_init, w_aligned), want_scale, tail_fraction))
 
 
 def dispatch(*args, **kw):
@@ -169,9 +61,10 @@ SWEEP_SCALES = (WANT_SCALE_DEFAULT, 1.0)
 SWEEP_K = (1, 8, 27)
 # 3; not a multiple of 4 (7); a multiple of 4 but not of 32 (20); 32; 64; a multiple of 128; 416 = 3 * 128 + 32
 SWEEP_CIN = (3, 7, 20, 32, 64, 128, 416)
-# every list, Cout % TN == 0 and not: c16 (5, 16), c32 (20, 32), c64 (48, 64), wide2 (80), wide2_64 (128), wide3 (192, 288),
-# wide3_128 (384), beyond 2048 (2052: the only kind of width the wide3 list takes that leaves <32, 2, 3> a partial column
-# tile, 2176: the same for the 192-column tiles of the wide3_128 lists), and the widths the narrow kernel takes (1, 3, 4)
+# every candidate list of csrc/sv_conv_select.h, Cout % TN == 0 and not: at most 16 outputs (5, 16), at most 32 (20, 32), at
+# most 64 (48, 64), the 128-column tiles (80; 128: a multiple of 64), the 192-column tiles (192, 288; 384: a multiple of
+# 128), beyond 2048 (2052: the only kind of width the 192-column lists take that leaves <32, 2, 3> a partial column tile,
+# 2176: the same for a multiple of 128), and the widths the narrow kernel takes (1, 3, 4)
 SWEEP_COUT = (1, 3, 4, 5, 16, 20, 32, 48, 64, 80, 128, 192, 288, 384, 2052, 2176)
 # every padded row count up to 136k: the last new combination appears at 131200 rows (more than 1024 workgroups of a 128-row
 # tile), none between there and 300k
@@ -179,11 +72,14 @@ SWEEP_VPAD = tuple(range(128, 136 * 1024 + 1, 128))
 
 
 def sweep():
-    """{(name, fast, ring, full)} of every combination the public call reaches.  has_plan = (K > 1): nn.conv_forward gives
-    dense rows no plan and every kernel map one.  vec_a is swept over both values where Cin allows it (a view whose row
-    stride or start is not 16-byte aligned); buf_ok = False only with a plan (a `perm` off a 16-byte boundary; without a
-    plan it takes a tensor beyond 2 GB, which sv_conv_fwd_acc splits into row ranges that fit)."""
+    """{(name, fast, ring, full)} of every combination the public call reaches, each with the first shape that reaches it.
+    has_plan = (K > 1): nn.conv_forward gives dense rows no plan and every kernel map one.  vec_a is swept over both values
+    where Cin allows it (a view whose row stride or start is not 16-byte aligned); buf_ok = False only with a plan (a `perm`
+    off a 16-byte boundary; without a plan it takes a tensor beyond 2 GB, which sv_conv_fwd_acc splits into row ranges that
+    fit).  One library call per (scale, K, Cin, vec_a, Cout, buf_ok, acc_init) answers all its row counts."""
     seen = {}
+    shapes = np.zeros((len(SWEEP_VPAD), 5), np.int64)
+    shapes[:, 3] = SWEEP_VPAD
     for ws in SWEEP_SCALES:
         for K in SWEEP_K:
             has_plan = K > 1
@@ -192,10 +88,13 @@ def sweep():
                     for Cout in SWEEP_COUT:
                         for buf_ok in ((True, False) if has_plan else (True,)):
                             for acc_init in (False, True):
-                                for Vpad in SWEEP_VPAD:
-                                    k = dispatch_key(K, Cin, Cout, Vpad, has_plan, vec_a, buf_ok, acc_init, ws)
-                                    if k not in seen:
-                                        seen[k] = (K, Cin, Cout, Vpad, has_plan, vec_a, buf_ok, acc_init, ws)
+                                shapes[:, (0, 1, 2, 4)] = (K, Cin, Cout, _flags(has_plan, vec_a, buf_ok, acc_init))
+                                raw = np.zeros(len(shapes), "S128")
+                                _lib.call("sv_conv_select", len(shapes), shapes.ctypes.data, ws, TAIL_DEFAULT, raw.ctypes.data, 128)
+                                names, first = np.unique(raw, return_index=True)
+                                for i in np.argsort(first):
+                                    seen.setdefault(_key(names[i].decode()), (K, Cin, Cout, SWEEP_VPAD[first[i]], has_plan, vec_a,
+                                                                              buf_ok, acc_init, ws))
     return seen
 
 

@@ -1,18 +1,18 @@
 """Completeness of the fp32 sparse-convolution instance table (tests/conv_instance_helpers.py), without a GPU.
 
-The restatement of the dispatch (sv_conv_fwd_acc -> select_and_launch -> launch_conv / launch_conv_dual) is swept over
-both dispatch scales, K = 1 / 8 / 27, input and output widths from every list, every padded row count up to 136k, an
+The library's own dispatch (conv_select of csrc/sv_conv_select.h, the function sv_conv_fwd_acc launches by, asked through
+sv_conv_select) is swept over both dispatch scales, K = 1 / 8 / 27, input and output widths from every list, every padded row count up to 136k, an
 aligned and a misaligned `perm`, a first and a later pass.  The set of (instance, fast, ring, full) it can produce must be
 exactly the set CASES pins on the GPU (tests/test_gpu_conv_instances.py): a candidate added to a list, or a moved
 threshold, fails here until a row covers it.
 
-Instantiations of launch_candidate() that NO dispatch rule reaches - only SV_CONV_FORCE / SV_CONV_FORCE_RANGE /
+Rows of the tile table (sv_conv_tile_info) that NO dispatch rule reaches - only SV_CONV_FORCE / SV_CONV_FORCE_RANGE /
 SV_CONV_FORCE_DENSE select them, so they are out of scope here (whether to keep them is a separate question):
 
     <128, 4, 3>  <128, 2, 3>  <128, 1, 3>  <64, 2, 3>  <64, 1, 3>
     <128, 2, 2>  <128, 1, 2>  <64, 2, 2>   <64, 1, 2>  <16, 4, 2>
 
-Forms the rules cannot produce on a reachable tile (the restatement never yields them): FAST on <32, 2, 2> (its list holds
+Forms the rules cannot produce on a reachable tile (the sweep never yields them): FAST on <32, 2, 2> (its list holds
 no width that is a multiple of its 64 columns) and on the fused-3 tiles (Cin = 3); FULL on the tiles whose USE_FULL is
 false; ring = 1 on <64, 4, 3>, <64, 4, 2>, <32, 4, 3> and <128, 4, 2> (PFD = 1: they have no ring form).
 """
@@ -53,8 +53,8 @@ def test_tile_constants_as_convcfg_computes_them():
     assert H.tile_cfg(32, 2, 1, 32) == H.TileCfg(MR=1, TN=32, GK=4, KC=128, PFD=8, USE_FULL=True)
     assert H.tile_cfg(32, 4, 1, 64) == H.TileCfg(MR=2, TN=64, GK=2, KC=128, PFD=4, USE_FULL=False)
     assert len(H.INSTANTIATED) == 34 and len(set(H.INSTANTIATED)) == 34
-    for lst in H.ALL_LISTS:  # every candidate of every list is an instantiation, and the last one takes whatever is left
-        assert all((tm, wn, nt, cpo) in H.INSTANTIATED for tm, wn, nt, _, cpo in lst) and lst[-1][3] == 0
+    # (that every candidate of every list is a row of the table, and that a list's last entry takes whatever is left, is a
+    #  static_assert beside the lists)
 
 
 def test_every_reachable_combination_has_a_row_and_no_row_is_unreachable(reachable):
@@ -68,6 +68,7 @@ def test_every_reachable_combination_has_a_row_and_no_row_is_unreachable(reachab
 
 
 def test_every_row_expects_what_the_restatement_says():
+    """(the name is from when a Python restatement of the rules answered; H.dispatch now asks the library)"""
     for c in H.CASES:
         assert c.V % H.PLAN_TILE == 67, c  # the partial last plan tile the GPU test relies on
         assert (c.kind, c.K) in (("dense", 1), ("up", 8), ("k3", 27)), c
@@ -89,9 +90,8 @@ def test_every_row_expects_what_the_restatement_says():
 
 
 def test_every_listed_tile_has_a_row_with_a_real_plan_and_every_guard_reason_it_allows(reachable):
-    tiles = {(tm, wn, nt, cpo) for lst in H.ALL_LISTS for tm, wn, nt, _, cpo in lst}
+    tiles = {_tile_of(k[0]) for k in reachable if _tile_of(k[0])}  # the tiles the sweep reaches
     assert tiles == set(H.INSTANTIATED) - UNREACHABLE
-    assert {_tile_of(k[0]) for k in reachable if _tile_of(k[0])} == tiles
     for tile in tiles:
         rows = [c for c in H.CASES if _tile_of(c.name) == tile]
         assert any(c.K > 1 for c in rows), f"{tile}: no row with a kernel map"
@@ -105,21 +105,3 @@ def test_every_listed_tile_has_a_row_with_a_real_plan_and_every_guard_reason_it_
         else:
             want = {"odd_cin", "cout_tail", "perm_misaligned"}
         assert reasons == want, (tile, reasons)
-
-
-def test_restatement_agrees_with_the_profiling_mirror():
-    """profiling.conv_kernel_config names the instance of a first pass with aligned operands at the default scale (and
-    names the thin layer's kernel of the default dispatch, the narrow kernel by Cout); wherever it is defined the two
-    must give the same name"""
-    from mrcc_amd import profiling
-
-    assert (profiling.CONV_WANT_SCALE, profiling.CONV_TAIL_FRACTION) == (H.WANT_SCALE_DEFAULT, H.TAIL_DEFAULT)
-    n = 0
-    for K in H.SWEEP_K:
-        for Cin in H.SWEEP_CIN:
-            for Cout in H.SWEEP_COUT:
-                for Vpad in H.SWEEP_VPAD[::6] + (8320, 16512, 32896, 48000, 57600, 65664):
-                    name, _ = H.dispatch(K, Cin, Cout, Vpad, K > 1, Cin % 4 == 0, True, False)
-                    assert profiling.conv_kernel_config(Cout, Vpad, Cin, K) == name, (K, Cin, Cout, Vpad)
-                    n += 1
-    assert n > 30000

@@ -102,11 +102,13 @@ def test_config_override_and_backbone_selection():
 
 
 def test_kernel_dispatch_mirror():
+    """profiling.conv_kernel_config asks the library's own dispatch rules (sv_conv_select), so this needs the built library
+    but no GPU.  148 input channels and K = 1: dense rows of a width that is no multiple of any channel chunk."""
     from mrcc_amd.profiling import conv_kernel_config as c
 
-    assert c(384, 88192) == "conv_fwd_kernel<64, 4, 3>"
-    # level 1 (thresholds x CONV_WANT_SCALE = 0.3: the taller tile wins earlier inside the two-stream pipeline)
-    assert c(384, 26624) == "conv_fwd_kernel<64, 4, 3>"        # Cin unknown: plain launch of the 64-row tile
+    assert c(384, 88192, 148, 1) == "conv_fwd_kernel<64, 4, 3>"
+    # level 1 (thresholds x the default scale 0.3: the taller tile wins earlier inside the two-stream pipeline)
+    assert c(384, 26624, 148, 1) == "conv_fwd_kernel<64, 4, 3>"        # dense rows: plain launch of the 64-row tile
     assert c(384, 26624, 416, 27) == "conv_fwd_dual_kernel<64, 32, 4, 3>"
     assert c(384, 26624, 384, 27) == "conv_fwd_dual_kernel<64, 32, 4, 3>"
     assert c(384, 6912, 384, 27) == "conv_fwd_kernel<32, 4, 3>"  # level 2: 32-row tiles (chosen inside the pipeline)
@@ -115,14 +117,14 @@ def test_kernel_dispatch_mirror():
     assert c(384, 88192, 384, 27) == "conv_fwd_dual_kernel<64, 32, 4, 3>"  # chip-filling: 64-row + 32-row tail tiles
     assert c(384, 88192, 416, 27) == "conv_fwd_dual_kernel<64, 32, 4, 3>"
     assert c(384, 88192, 416, 1) == "conv_fwd_kernel<64, 4, 3>"   # dense rows (no plan): plain launch
-    assert c(384, 6912) == "conv_fwd_kernel<32, 4, 3>"
-    assert c(192, 26624) == "conv_fwd_kernel<32, 4, 3>"
-    assert c(384, 1792) == "conv_fwd_kernel<16, 4, 3>"
+    assert c(384, 6912, 148, 1) == "conv_fwd_kernel<32, 4, 3>"
+    assert c(192, 26624, 148, 1) == "conv_fwd_kernel<32, 4, 3>"
+    assert c(384, 1792, 148, 1) == "conv_fwd_kernel<16, 4, 3>"
     assert c(384, 1792, 512, 27) == "conv_fwd_kernel<16, 4, 3>"
-    assert c(192, 1792) == "conv_fwd_kernel<32, 2, 3>"
-    assert c(256, 512) == "conv_fwd_kernel<16, 4, 1>"
-    assert c(32, 26624) == "conv_fwd_kernel<32, 2, 1>"
-    assert c(1024, 88192) == "conv_fwd_kernel<128, 4, 2>"
+    assert c(192, 1792, 148, 1) == "conv_fwd_kernel<32, 2, 3>"
+    assert c(256, 512, 148, 1) == "conv_fwd_kernel<16, 4, 1>"
+    assert c(32, 26624, 148, 1) == "conv_fwd_kernel<32, 2, 1>"
+    assert c(1024, 88192, 148, 1) == "conv_fwd_kernel<128, 4, 2>"
 
 
 def test_segmentation_metrics_and_synth():

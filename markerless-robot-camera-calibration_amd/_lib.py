@@ -5,6 +5,7 @@ only to own device memory and streams; every computation on the hot path is a ca
 """
 import ctypes
 import os
+import threading
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch
@@ -251,16 +252,24 @@ def conv_tiles():
 
 class conv_dispatch:
     """`with conv_dispatch(want_scale):` - dispatch thresholds of this thread's sv_conv_fwd calls inside the block
-    (sv_conv_set_dispatch; 1.0 = one frame alone on the GPU), library defaults restored afterwards."""
+    (sv_conv_set_dispatch; 1.0 = one frame alone on the GPU); afterwards the setting in force on entry is back: the
+    enclosing block's pair (blocks nest; the open ones are a per-thread stack), or the library defaults at the bottom."""
+
+    _open = threading.local()  # .stack: the (want_scale, tail_fraction) pairs of this thread's open blocks, innermost last
 
     def __init__(self, want_scale, tail_fraction=-1.0):
-        self.args = (c_double(want_scale), c_double(tail_fraction))
+        self.args = (float(want_scale), float(tail_fraction))
 
     def __enter__(self):
-        call("sv_conv_set_dispatch", *self.args)
+        stack = self._open.__dict__.setdefault("stack", [])
+        call("sv_conv_set_dispatch", c_double(self.args[0]), c_double(self.args[1]))
+        stack.append(self.args)
 
     def __exit__(self, *exc):
-        call("sv_conv_set_dispatch", c_double(-1.0), c_double(-1.0))
+        stack = self._open.stack
+        stack.pop()
+        want_scale, tail_fraction = stack[-1] if stack else (-1.0, -1.0)
+        call("sv_conv_set_dispatch", c_double(want_scale), c_double(tail_fraction))
 
 
 def require_cuda(t, what="tensor"):

@@ -350,7 +350,9 @@ class CoordinateManager:
         arena = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         sbytes = lib.sv_frame_plans_scratch_bytes(V, c_int(L))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
-        max_rec = 8 * (L + 1) + 8
+        # every record sv_frame_plans can emit: a hash table, the 27-offset plan and up to SV_FRAME_MAX_CUTS + 1 offset ranges
+        # on each of the L + 1 levels, a down and an up plan on all but the top one
+        max_rec = (2 + (_lib.SV_FRAME_MAX_CUTS + 1)) * (L + 1) + 2 * L
         layout = (c_int64 * (_lib.SV_FRAME_RECORD * (1 + max_rec)))()
         call("sv_frame_plans", keys, coords, parent, V, c_int(L), c_int(flags), cuts_arr, k3n, k3m, ptr(arena), c_size_t(nbytes),
              ptr(scratch), c_size_t(sbytes), layout, c_int(max_rec), stream_ptr())

@@ -105,3 +105,60 @@ def test_every_listed_tile_has_a_row_with_a_real_plan_and_every_guard_reason_it_
         else:
             want = {"odd_cin", "cout_tail", "perm_misaligned"}
         assert reasons == want, (tile, reasons)
+
+
+def test_conv_dispatch_restores_the_setting_it_found():
+    """conv_dispatch blocks nest: leaving one re-applies the enclosing block's thresholds (the library default at the
+    bottom), also when the block ends in an exception, and one thread's blocks leave another thread's answer alone.  Read
+    through sv_conv_select with this thread's current dispatch on the 32 -> 32 3x3x3 layer at 8192 padded rows, which the
+    default sends to conv_thin_kernel and conv_dispatch(1.0) to conv_thin_lds_kernel."""
+    import threading
+
+    from mrcc_amd import _lib
+
+    flags = (_lib.SV_CONV_SEL_BUF_OK | _lib.SV_CONV_SEL_PLAN | _lib.SV_CONV_SEL_TILE_ORDER | _lib.SV_CONV_SEL_VEC_A |
+             _lib.SV_CONV_SEL_W_ALIGNED)
+    now = lambda: _lib._parse_instance(_lib.conv_instance(27, 32, 32, 8192, flags))[0]  # noqa: E731
+    THIN, LDS = "conv_thin_kernel<32, 32>", "conv_thin_lds_kernel<32, 32>"
+    assert now() == THIN
+    with _lib.conv_dispatch(1.0):
+        assert now() == LDS
+        with _lib.conv_dispatch(0.25):
+            assert now() == THIN
+        assert now() == LDS, "leaving the inner block must bring the outer block's setting back"
+        with pytest.raises(RuntimeError):
+            with _lib.conv_dispatch(0.25):
+                assert now() == THIN
+                raise RuntimeError("the block ends in an exception")
+        assert now() == LDS
+        # a second thread starts from the default, sets its own dispatch and leaves this thread's untouched
+        seen, inside, leave = {}, threading.Event(), threading.Event()
+
+        def other():
+            seen["before"] = now()
+            with _lib.conv_dispatch(0.25):
+                seen["inside"] = now()
+                inside.set()
+                leave.wait(30)
+            seen["after"] = now()
+
+        t = threading.Thread(target=other)
+        t.start()
+        assert inside.wait(30)
+        assert now() == LDS
+        leave.set()
+        t.join(30)
+        assert not t.is_alive() and seen == {"before": THIN, "inside": THIN, "after": THIN}
+        assert now() == LDS
+
+        def other_alone():
+            with _lib.conv_dispatch(1.0):
+                seen["alone"] = now()
+
+        with _lib.conv_dispatch(0.25):
+            t = threading.Thread(target=other_alone)
+            t.start()
+            t.join(30)
+            assert seen["alone"] == LDS and now() == THIN
+        assert now() == LDS
+    assert now() == THIN

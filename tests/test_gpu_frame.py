@@ -87,6 +87,83 @@ def check_composites_equal_piecewise(gpu, c, f, levels, rules):
                     _same_plan(pa[2], pb[2])
                 n_split += 1
     assert (n_split > 0) == bool(rules)
+    return cma, staged, cmb
+
+
+# ---- the limits of the composite: SV_FRAME_MAX_LEVELS = 8 levels, SV_FRAME_MAX_CUTS = 4 cuts per level -----------------
+LIMIT_LEVELS, LIMIT_RULES, LIMIT_CUTS = 8, "1:5,11,16,22", (5, 11, 16, 22)
+
+
+def _limit_cloud(kind):
+    """coordinates [N, 4] (batch, x, y, z in voxels) and features [N, 3]"""
+    if kind == "one_point":  # V = 1 on all nine levels
+        c = np.array([[0, 3, -7, 12]], np.float32)
+    elif kind == "two_points":  # 1000 voxels apart: two voxels on every level up to stride 256
+        c = np.array([[0, 0, 0, 0], [0, 1000, 0, 0]], np.float32)
+    elif kind == "blob_129":  # 129 voxels: one row into a second 128-row plan tile
+        g = np.stack(np.meshgrid(np.arange(6), np.arange(6), np.arange(4), indexing="ij"), -1).reshape(-1, 3)[:129]
+        c = np.concatenate([np.zeros((129, 1)), g - 2], axis=1).astype(np.float32)
+    else:  # two frames of about 1500 points each
+        return _frame(1500, 5, 2)
+    f = np.random.default_rng(len(c)).uniform(-0.5, 0.5, (len(c), 3)).astype(np.float32)
+    return torch.from_numpy(c), torch.from_numpy(f)
+
+
+@pytest.mark.parametrize("kind", ["one_point", "two_points", "blob_129", "two_frames"])
+def test_frame_composites_at_eight_levels_and_four_cuts(gpu, kind):
+    """Every record sv_frame_plans can emit in one call: a hash table, the 27-offset plan and five offset ranges on each
+    of the nine levels, a down and an up plan on the lower eight - 9 L + 7 = 79 at L = 8, which is the size build_plans
+    gives its layout table.  A record kind more in the library, or a fifth cut, fails here (SV_ERR_WORKSPACE) first."""
+    from mrcc_amd import _lib
+
+    L = LIMIT_LEVELS
+    assert L == _lib.SV_FRAME_MAX_LEVELS and len(LIMIT_CUTS) == _lib.SV_FRAME_MAX_CUTS
+    c, f = _limit_cloud(kind)
+    cma, staged, cmb = check_composites_equal_piecewise(gpu, c, f, L, LIMIT_RULES)
+    want_V = {"one_point": [1] * 9, "two_points": [2] * 9, "blob_129": [129]}.get(kind)
+    if want_V:
+        assert [cma.stride_map(1 << l).V for l in range(len(want_V))] == want_V
+    else:
+        assert 2000 < cma.stride_map(1).V <= len(c)
+    for cm in (cma, staged):
+        built = 0
+        for l in range(L + 1):
+            assert cm.stride_map(1 << l).V >= 1
+            split = cm.plans.get(("k3split", 1 << l, LIMIT_CUTS))
+            assert split is not None and [(p[0], p[1]) for p in split.parts] == [(0, 5), (5, 11), (11, 16), (16, 22), (22, 27)]
+        for key, plan in cm.plans.items():
+            assert key[0] in ("k3", "down", "up", "k3split"), key
+            built += len(plan.parts) if key[0] == "k3split" else 1
+        # by hand: 9 plans of 27 offsets, 8 down, 8 up, 9 * 5 offset ranges = 9 L + 7 records less the L + 1 hash tables
+        assert built == 9 + 8 + 8 + 45 == (9 * L + 7) - (L + 1), built
+
+
+def test_a_rule_with_five_cuts_is_left_to_plan_k3_split(gpu):
+    """one cut more than SV_FRAME_MAX_CUTS: the composite builds everything but that rule's offset ranges, and
+    plan_k3_split builds them on demand - the parts of a piecewise manager"""
+    from mrcc_amd import MinkowskiEngine as ME
+    from mrcc_amd import _lib
+    from mrcc_amd import nn as svnn
+
+    cuts = (5, 9, 14, 18, 22)
+    assert len(cuts) == _lib.SV_FRAME_MAX_CUTS + 1
+    rules = svnn._parse_split_rules("1:" + ",".join(str(v) for v in cuts))
+    c, f = _frame(1500, 5, 2)
+    levels = 2
+    cma = ME.TensorField(f, c, device=gpu).sparse(pyramid_levels=levels).coordinate_manager
+    cmb = ME.TensorField(f, c, device=gpu).sparse().coordinate_manager
+    cma.split_rules = cmb.split_rules = rules
+    cma.build_plans(levels)
+    assert not any(k[0] == "k3split" for k in cma.plans)
+    assert sum(k[0] in ("k3", "down", "up") for k in cma.plans) == 3 * levels + 1
+    for l in range(levels + 1):
+        ts = 1 << l
+        assert cma.split_cuts_for(cma.stride_map(ts).V) == cuts
+        sa, sb = cma.plan_k3_split(ts, cuts), cmb.plan_k3_split(ts, cuts)
+        assert [(p[0], p[1]) for p in sa.parts] == [(p[0], p[1]) for p in sb.parts] == list(zip((0,) + cuts, cuts + (27,)))
+        for pa, pb in zip(sa.parts, sb.parts):
+            _same_plan(pa[2], pb[2])
+        _same_plan(sa.whole, sb.whole)
 
 
 def test_frame_composite_network_bits_and_encoder_only(gpu):

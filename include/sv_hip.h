@@ -1105,6 +1105,85 @@ int sv_single_linkage_roots(const void* xyz, int elem_bytes, int64_t ld, const i
 int sv_select_equal(const void* v, int elem_bytes, int64_t n, int64_t value, const int32_t* value_dev, int64_t* out,
                     int64_t* count, sv_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N8  strided kernel maps, local pooling, instance normalisation: what the classification ResNets need beyond the
+ *      U-Nets (ME.MinkowskiConvolution(kernel_size=3 / 1, stride=2 / 3), ME.MinkowskiMaxPooling(kernel_size=2, stride=2),
+ *      ME.MinkowskiInstanceNorm; model/backbone/resnet.py:48-84,95-127).  Additions of ABI 4.
+ *
+ * Semantics (MinkowskiEngine 0.5.4, restated from memory - ME is not installed; tests/test_gpu_resnet_dense.py pins the
+ * definition itself against dense conv3d / max_pool3d): a convolution of stride st on a tensor of tensor stride ts writes
+ * the map at tensor stride ts * st, whose voxels are floor(c / (ts st)) * ts st of the input voxels c; an ODD kernel is
+ * centred on the output coordinate (inputs at o + d * ts * dilation, d in {-1,0,1}^3), an EVEN kernel starts at it.
+ *
+ * sv_stride_map_general: the map at tensor stride s_out of a map at s_in, s_out a positive multiple of s_in (any multiple;
+ *   powers of two stay on sv_stride_map, which only clears key bits).  Output coordinate = floor(c / s_out) * s_out per axis
+ *   on the SIGNED coordinate (negative coordinates floor towards minus infinity).  The interleaved key does not keep its order
+ *   under that, so the voxels are re-keyed, sorted (stable radix sort) and uniqued.  keys_out / vcoords_out: canonical sorted
+ *   unique keys and (batch,x,y,z) rows, first V_out entries (arrays of V_in); parent int32[V_in]: row of every input voxel in
+ *   the output map; counters int32[4]: [0] = V_out, [1] = input voxels whose output coordinate leaves the key range (a
+ *   coordinate below -2^17 after flooring; must be 0 - as sv_voxelize's counters[1]: such a voxel is keyed as (batch 0, 0,0,0)
+ *   and gets parent -1, the map is then not the input's).
+ * sv_kernel_map_probe: kernel map between TWO maps - sv_kernel_map_k3 with the query rows (vcoords_q, V_q) taken from one
+ *   map and the hash table (and vcoords_t / V_t, its canonical rows: the SV_EMPTY_KEY voxel is found as their last row) from
+ *   another.  kernel_size 1 (K = 1, offset 0) or 3 (K = 27, x fastest as everywhere).  step: SIGNED, input tensor stride *
+ *   dilation.  nbr[k*ld + o] = row in the table's map of coords_q[o] + d_k * step, or -1 (also when that coordinate leaves
+ *   the key range); mask[o] bit k = present.  Forward map of a strided conv: queries = output map, table = input map, +step;
+ *   map of its input gradient (and of pooling's backward): queries = input map, table = output map, -step - the transpose:
+ *   nbr[k][o] = i exactly when nbr_t[k][i] = o.
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_stride_map_general_workspace_bytes(int64_t V_in);
+int sv_stride_map_general(const uint64_t* keys_in, int64_t V_in, int s_in, int s_out, void* workspace, size_t workspace_bytes,
+                          uint64_t* keys_out, int32_t* vcoords_out, int32_t* parent, int32_t* counters, sv_stream_t stream);
+int sv_kernel_map_probe(const int32_t* vcoords_q, int64_t V_q, int kernel_size, int step, const int32_t* vcoords_t, int64_t V_t,
+                        const uint64_t* table_keys, const int32_t* table_vals, int64_t capacity, int32_t* nbr, int64_t ld,
+                        uint32_t* mask, sv_stream_t stream);
+
+/* Local pooling over any kernel-map neighbour table nbr int32[K][ld] (the raw map, not a conv plan):
+ *   SV_POOL_SUM: out[o][c] = sum over k ascending of in[nbr[k][o]][c], fp32, starting from 0;
+ *   SV_POOL_AVG: that sum / number of present neighbours of o;
+ *   SV_POOL_MAX: the maximum, arg[o][c] (int32[V_out][C], dense) = the input row that won; torch's max(dim) rule as
+ *     sv_group_max: the first NaN (lowest k) wins and stays, a tie goes to the lowest k.
+ *   A row without neighbours (no kernel map produces one) gives 0, and arg = -1.
+ * One wavefront per output row, lanes along C (float4 when C % 4 == 0 and rows are 16-byte aligned).  arg may be NULL unless
+ * mode is SV_POOL_MAX.
+ * Backward: one thread per (input row, channel) over the TRANSPOSED table nbr_t int32[K][ld_t] (kernel_size 2 stride 2: the
+ * up map; else sv_kernel_map_probe with -step):
+ *   dx[i][c] = sum over k ascending with o = nbr_t[k][i] >= 0 of  dy[o][c]                       (sum)
+ *                                                                 dy[o][c] / popcount(mask_fwd[o]) (avg; the forward map's mask)
+ *                                                                 dy[o][c] if arg[o][c] == i       (max)
+ * no float atomics: the same bits on every run.  Every dx element is written. */
+#define SV_POOL_SUM 2
+int sv_pool_local(const float* in, int64_t V_in, int64_t in_ld, int C, const int32_t* nbr, int64_t ld, int K, int64_t V_out,
+                  int mode, float* out, int64_t out_ld, int32_t* arg, sv_stream_t stream);
+int sv_pool_local_backward(const float* dy, int64_t V_out, int64_t dy_ld, int C, const int32_t* nbr_t, int64_t ld_t, int K,
+                           int64_t V_in, int mode, const int32_t* arg, const uint32_t* mask_fwd, float* dx, int64_t dx_ld,
+                           sv_stream_t stream);
+
+/* Instance normalisation over the frames of a batched tensor (rows batch_start[b] .. batch_start[b+1], sv_batch_offsets;
+ * V = rows of x, batch_start[B] <= V), per (frame b, channel c) over the frame's n rows, all in float64:
+ *   mean = sum x / n;  var = sum (x - mean)^2 / n  (second pass, biased);  inv_std = 1 / sqrt(var + eps)
+ *   y = (float) act((x - mean) * inv_std * weight[c] + bias[c])      act: SV_ACT_NONE, SV_ACT_RELU or SV_ACT_GELU
+ *       (GELU in the exact erf form, evaluated in float64 before the one rounding to float32)
+ * eps = 1e-8 and weight / bias of shape [1, C] are ME 0.5.4's MinkowskiInstanceNorm from memory (unverified).
+ * Summation tree: chunks of SV_NORM_CHUNK_ROWS rows; a chunk's four quarters are each summed sequentially in ascending row
+ * order and added in ascending order; a frame's chunks are added in ascending order.  No atomics.
+ * A frame with n = 0 writes no row (its mean / inv_std entries are 0); n = 1 gives act(bias).  mean / inv_std: double[B][C],
+ * written for the backward.
+ * Backward (dy' = dy * act'(pre-activation), the pre-activation recomputed; g = dy' * weight):
+ *   dx = inv_std * (g - mean_b(g) - xhat * mean_b(g * xhat)),  xhat = (x - mean) * inv_std
+ *   dweight[c] = sum over frames ascending of sum_rows dy' * xhat;  dbias[c] = ... of sum_rows dy'   (float32[C], may be NULL)
+ * the frame sums through the same tree.  One workspace size serves both calls. */
+#define SV_ACT_GELU 3
+#define SV_NORM_CHUNK_ROWS 256
+size_t sv_instance_norm_workspace_bytes(int64_t V, int B, int C);
+int sv_instance_norm(const float* x, int64_t V, int64_t ld, int C, const int32_t* batch_start, int B, const float* weight,
+                     const float* bias, double eps, int act, void* workspace, size_t workspace_bytes, float* y, int64_t y_ld,
+                     double* mean, double* inv_std, sv_stream_t stream);
+int sv_instance_norm_backward(const float* x, int64_t V, int64_t ld, int C, const int32_t* batch_start, int B, const float* weight,
+                              const float* bias, const double* mean, const double* inv_std, int act, const float* dy,
+                              int64_t dy_ld, void* workspace, size_t workspace_bytes, float* dx, int64_t dx_ld, float* dweight,
+                              float* dbias, sv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

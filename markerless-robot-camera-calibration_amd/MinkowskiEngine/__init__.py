@@ -4,9 +4,10 @@ The reference does `import MinkowskiEngine as ME` and `from MinkowskiEngine.modu
 (model/backbone/minkunet.py:28-30).  `mrcc_amd.install_as_minkowski_engine()` registers this package under that
 name so reference-shaped model files import unchanged; the build's own model mirror imports it directly.
 """
-from ..nn import (BasicBlock, Bottleneck, MinkowskiBatchNorm, MinkowskiConvolution, MinkowskiConvolutionTranspose,
-                  MinkowskiGlobalAvgPooling, MinkowskiGlobalMaxPooling, MinkowskiLeakyReLU, MinkowskiLinear,
-                  MinkowskiReLU, MinkowskiSigmoid)
+from ..nn import (BasicBlock, Bottleneck, MinkowskiAvgPooling, MinkowskiBatchNorm, MinkowskiConvolution,
+                  MinkowskiConvolutionTranspose, MinkowskiDropout, MinkowskiGELU, MinkowskiGlobalAvgPooling,
+                  MinkowskiGlobalMaxPooling, MinkowskiInstanceNorm, MinkowskiLeakyReLU, MinkowskiLinear, MinkowskiMaxPooling,
+                  MinkowskiReLU, MinkowskiSigmoid, MinkowskiSumPooling)
 from ..sparse import (CoordinateManager, MinkowskiAlgorithm, SparseTensor, SparseTensorQuantizationMode, TensorField,
                       cat)
 from . import MinkowskiOps, modules, utils  # noqa: F401

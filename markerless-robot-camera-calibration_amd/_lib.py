@@ -14,8 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 4  # SV_ABI_VERSION of include/sv_hip.h
 LIB_PATH = os.environ.get("SVHIP_LIB") or os.path.join(_HERE, "libsvhip.so")  # SVHIP_LIB: kernel A/B experiments
 
-SV_ACT_NONE, SV_ACT_RELU, SV_ACT_LEAKY_RELU = 0, 1, 2
-SV_POOL_MAX, SV_POOL_AVG = 0, 1
+SV_ACT_NONE, SV_ACT_RELU, SV_ACT_LEAKY_RELU, SV_ACT_GELU = 0, 1, 2, 3
+SV_POOL_MAX, SV_POOL_AVG, SV_POOL_SUM = 0, 1, 2
+SV_NORM_CHUNK_ROWS = 256
 SV_REDUCE_MEAN, SV_REDUCE_FIRST = 0, 1
 SV_TILE_ROWS = 128
 SV_ERR_UNSUPPORTED = -5
@@ -172,6 +173,16 @@ SIGNATURES = {
     "sv_group_max_backward": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),
     "sv_three_nn": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "sv_three_nn_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "sv_stride_map_general_workspace_bytes": (c_size_t, [c_int64]),
+    "sv_stride_map_general": (c_int, [_P, c_int64, c_int, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "sv_kernel_map_probe": (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),
+    "sv_pool_local": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, c_int64, c_int, _P, c_int64, _P, _P]),
+    "sv_pool_local_backward": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int64, c_int, c_int64, c_int, _P, _P, _P, c_int64, _P]),
+    "sv_instance_norm_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "sv_instance_norm": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P, _P, c_double, c_int, _P, c_size_t, _P, c_int64, _P,
+                                 _P, _P]),
+    "sv_instance_norm_backward": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int64, _P,
+                                          c_size_t, _P, c_int64, _P, _P, _P]),
 }
 
 _lib = None

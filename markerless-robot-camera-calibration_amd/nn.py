@@ -9,11 +9,12 @@ state_dict keys match ME 0.5.4 so utils/utils.py:87-126 checkpoint_restore-style
   MinkowskiConvolution(.Transpose): `kernel` [K, Cin, Cout] ([Cin, Cout] when K == 1), `bias` [1, Cout]
   MinkowskiBatchNorm: `bn.weight bn.bias bn.running_mean bn.running_var bn.num_batches_tracked`
   MinkowskiLinear: `linear.weight` [Cout, Cin], `linear.bias` [Cout]
+  MinkowskiInstanceNorm: `weight` [1, C], `bias` [1, C] (from memory, unverified against ME)
 Kernel-offset order inside `kernel` is this build's definition (include/sv_hip.h); `KERNEL_OFFSET_PERMUTATION` is the
 single hook for adapting a real ME checkpoint if its order turns out to differ.
 """
 import math
-from ctypes import c_float, c_int, c_int64, c_size_t
+from ctypes import c_double, c_float, c_int, c_int64, c_size_t
 
 import numpy as np
 import torch
@@ -529,6 +530,9 @@ class _ConvBase(_Bf16Weights, nn.Module):
                 return cm.plan_k3(ts, self.dilation), ts
             if ks == 2 and st == 2:
                 return cm.plan_down(ts), ts * 2
+            if ks in (1, 3) and isinstance(st, int) and st >= 2:
+                # the strided convs of the classification ResNets (model/backbone/resnet.py:53,76,99-105)
+                return cm.plan_strided(ts, ks, st, self.dilation), ts * st
         else:
             if ks == 2 and st == 2:
                 return cm.plan_up(ts), ts // 2
@@ -541,6 +545,8 @@ class _ConvBase(_Bf16Weights, nn.Module):
         cm, ts = x.coordinate_manager, x.tensor_stride
         if self.kernel_size == 2 and self.stride == 2:
             return lambda: cm.plan_down(ts // 2) if self.transposed else cm.plan_up(ts * 2)
+        if not self.transposed and self.stride >= 2:  # strided k3 / k1: the transposed probe map, W[k]^T (mirror=False)
+            return lambda: cm.plan_strided_t(ts, self.kernel_size, self.stride, self.dilation)
         return lambda: plan
 
     def forward_train(self, x, bn=None, residual=None, act=SV_ACT_NONE, slope=0.01, cat_with=None):
@@ -548,7 +554,7 @@ class _ConvBase(_Bf16Weights, nn.Module):
         running statistics in eval()), + residual, activation, ME.cat"""
         plan, out_stride = self._plan(x)
         V_out = x.coordinate_manager.stride_map(out_stride).V
-        mirror = self.kernel_size == 3
+        mirror = self.kernel_size == 3 and self.stride == 1
         out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, self._grad_plan(x, plan), mirror, layer=self)
         if bn is not None:
             out = bn.bn(out)
@@ -724,6 +730,172 @@ class MinkowskiGlobalAvgPooling(nn.Module):
         if self.training:
             return PooledTensor(global_pool_train(x, _lib.SV_POOL_AVG))
         return PooledTensor(global_pool(x, _lib.SV_POOL_AVG))
+
+
+class LocalPoolFunction(torch.autograd.Function):
+    """out = pool(feats) over a kernel map's raw table (sv_pool_local); backward sv_pool_local_backward over the
+    transposed table (t_plan: a callable, built only when the input needs a gradient) - a gather, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, feats, plan, mode, t_plan):
+        nbr, ld, mask = plan.raw
+        f = feats.detach()
+        if f.stride(1) != 1:
+            f = f.contiguous()
+        V_out, C = plan.V_out, f.shape[1]
+        out = torch.empty((V_out, C), dtype=torch.float32, device=f.device)
+        arg = torch.empty((V_out, C), dtype=torch.int32, device=f.device) if mode == _lib.SV_POOL_MAX else None
+        call("sv_pool_local", ptr(f), c_int64(f.shape[0]), c_int64(f.stride(0)), c_int(C), ptr(nbr), c_int64(ld),
+             c_int(plan.K), c_int64(V_out), c_int(mode), ptr(out), c_int64(C), ptr(arg), stream_ptr())
+        ctx.plan, ctx.mode, ctx.t_plan, ctx.arg, ctx.V_in = plan, mode, t_plan, arg, f.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        if dy.stride(1) != 1:
+            dy = dy.contiguous()
+        nbr_t, ld_t, _ = ctx.t_plan().raw
+        C = dy.shape[1]
+        dx = torch.empty((ctx.V_in, C), dtype=torch.float32, device=dy.device)
+        call("sv_pool_local_backward", ptr(dy), c_int64(dy.shape[0]), c_int64(dy.stride(0)), c_int(C), ptr(nbr_t),
+             c_int64(ld_t), c_int(ctx.plan.K), c_int64(ctx.V_in), c_int(ctx.mode), ptr(ctx.arg), ptr(ctx.plan.raw[2]), ptr(dx),
+             c_int64(C), stream_ptr())
+        return dx, None, None, None
+
+
+class _LocalPoolBase(nn.Module):
+    """ME.MinkowskiMaxPooling / AvgPooling / SumPooling(kernel_size, stride, dilation, dimension) on the kernel maps the
+    convolutions use: kernel_size 2 stride 2 on the down map, kernel_size 3 / 1 with any stride on the strided (stride 1: the
+    3x3x3) maps.  An even kernel starts at the output coordinate, an odd one is centred on it."""
+    MODE = None
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__()
+        if dimension != 3:
+            raise NotImplementedError("only dimension=3 (the reference passes D=3 everywhere)")
+        self.kernel_size, self.stride, self.dilation, self.dimension = kernel_size, stride, dilation, dimension
+
+    def _plans(self, x):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        ks, st, dil = self.kernel_size, self.stride, self.dilation
+        if ks == 2 and st == 2 and dil == 1:
+            return cm.plan_down(ts), ts * 2, lambda: cm.plan_up(ts * 2)
+        if ks in (1, 3) and isinstance(st, int) and st >= 1:
+            plan = cm.plan_k3(ts, dil) if (ks, st) == (3, 1) else cm.plan_strided(ts, ks, st, dil)
+            return plan, ts * st, lambda: cm.plan_strided_t(ts, ks, st, dil)
+        raise NotImplementedError(f"pooling kernel_size={ks} stride={st} dilation={dil}: no kernel map of that shape")
+
+    def forward(self, x):
+        plan, out_stride, t_plan = self._plans(x)
+        return x.new(LocalPoolFunction.apply(x.F, plan, self.MODE, t_plan), tensor_stride=out_stride)
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+
+
+class MinkowskiMaxPooling(_LocalPoolBase):
+    MODE = _lib.SV_POOL_MAX
+
+
+class MinkowskiAvgPooling(_LocalPoolBase):
+    MODE = _lib.SV_POOL_AVG
+
+
+class MinkowskiSumPooling(_LocalPoolBase):
+    MODE = _lib.SV_POOL_SUM
+
+
+def _frame_offsets(x):
+    """(batch_start int32[B + 1] on the device, B) of a sparse tensor's map"""
+    cm = x.coordinate_manager
+    if cm.num_batches is None:
+        m1 = cm.stride_map(1)
+        cm.num_batches = int(m1.coords[:, 0].max().item()) + 1 if m1.V else 1
+    return cm.batch_offsets(x.tensor_stride, cm.num_batches), cm.num_batches
+
+
+class InstanceNormFunction(torch.autograd.Function):
+    """y = act(instance_norm(x) * weight + bias) per (frame, channel) in float64 (sv_instance_norm); backward
+    sv_instance_norm_backward (dx, dweight, dbias through the same fixed summation tree)."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, bias, batch_start, B, eps, act):
+        f = feats.detach()
+        if f.stride(1) != 1:
+            f = f.contiguous()
+        V, C = f.shape
+        w, b = weight.detach().reshape(-1).contiguous(), bias.detach().reshape(-1).contiguous()
+        nbytes = _lib.load().sv_instance_norm_workspace_bytes(c_int64(V), c_int(B), c_int(C))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        y = torch.empty((V, C), dtype=torch.float32, device=f.device)
+        mean = torch.empty((B, C), dtype=torch.float64, device=f.device)
+        inv_std = torch.empty((B, C), dtype=torch.float64, device=f.device)
+        call("sv_instance_norm", ptr(f), c_int64(V), c_int64(f.stride(0)), c_int(C), ptr(batch_start), c_int(B), ptr(w), ptr(b),
+             c_double(eps), c_int(act), ptr(ws), c_size_t(nbytes), ptr(y), c_int64(C), ptr(mean), ptr(inv_std), stream_ptr())
+        ctx.save_for_backward(f, w, b, mean, inv_std, batch_start)
+        ctx.B, ctx.act, ctx.wshape, ctx.bshape = B, act, weight.shape, bias.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        f, w, b, mean, inv_std, batch_start = ctx.saved_tensors
+        if dy.stride(1) != 1:
+            dy = dy.contiguous()
+        V, C = f.shape
+        nbytes = _lib.load().sv_instance_norm_workspace_bytes(c_int64(V), c_int(ctx.B), c_int(C))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        dx = torch.empty((V, C), dtype=torch.float32, device=f.device)
+        dw = torch.empty(C, dtype=torch.float32, device=f.device)
+        db = torch.empty(C, dtype=torch.float32, device=f.device)
+        call("sv_instance_norm_backward", ptr(f), c_int64(V), c_int64(f.stride(0)), c_int(C), ptr(batch_start), c_int(ctx.B),
+             ptr(w), ptr(b), ptr(mean), ptr(inv_std), c_int(ctx.act), ptr(dy), c_int64(dy.stride(0)), ptr(ws), c_size_t(nbytes),
+             ptr(dx), c_int64(C), ptr(dw), ptr(db), stream_ptr())
+        return dx, dw.reshape(ctx.wshape), db.reshape(ctx.bshape), None, None, None, None
+
+
+class MinkowskiInstanceNorm(nn.Module):
+    """ME.MinkowskiInstanceNorm(num_features): per (frame, channel) normalisation with biased variance, eps = 1e-8,
+    `weight` / `bias` of shape [1, C] (ME 0.5.4 from memory - include/sv_hip.h).  forward_fused applies the activation that
+    follows in the same call (SV_ACT_RELU / SV_ACT_GELU)."""
+
+    def __init__(self, num_features):
+        super().__init__()
+        self.num_features = num_features
+        self.eps = 1e-8
+        self.weight = nn.Parameter(torch.ones(1, num_features))
+        self.bias = nn.Parameter(torch.zeros(1, num_features))
+
+    def forward_fused(self, x, act=SV_ACT_NONE):
+        if x.F.shape[1] != self.num_features:
+            raise ValueError(f"input has {x.F.shape[1]} channels, MinkowskiInstanceNorm expects {self.num_features}")
+        bs, B = _frame_offsets(x)
+        return x.new(InstanceNormFunction.apply(x.F, self.weight, self.bias, bs, B, self.eps, act))
+
+    def forward(self, x):
+        return self.forward_fused(x)
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}"
+
+
+class MinkowskiGELU(nn.Module):
+    # exact (erf) GELU on the features; inside a ResNet in eval() it is fused into the instance norm before it
+    def forward(self, x):
+        f = torch.nn.functional.gelu
+        return x.new(f(x.F)) if isinstance(x, SparseTensor) else f(x)
+
+
+class MinkowskiDropout(nn.Module):
+    def __init__(self, p=0.5, inplace=False):
+        super().__init__()
+        self.p = p
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        return x.new(torch.dropout(x.F, self.p, True))
 
 
 class PooledTensor:

@@ -165,6 +165,7 @@ class CoordinateManager:
         self.device = device
         self.maps = {}  # stride -> CoordinateMap
         self.parents = {}  # fine stride -> (parent int32[V_fine], child_start int32[V_coarse+1])
+        self.general_parents = {}  # (fine stride, coarse stride) -> parent int32[V_fine] of the maps of _stride_map_general
         self.plans = {}
         self._batch_offsets = {}
         self._batch_bounds = {}
@@ -180,10 +181,13 @@ class CoordinateManager:
 
     # ---- coordinate maps -------------------------------------------------------------------
     def stride_map(self, stride):
-        """Map at tensor stride `stride` (power of two); created from the next finer one on demand."""
+        """Map at tensor stride `stride`; created on demand: a power of two from the next finer one (sv_stride_map, key bits
+        cleared), any other stride from the coarsest existing map whose stride divides it (sv_stride_map_general)."""
         if stride in self.maps:
             return self.maps[stride]
-        if stride <= 1 or (stride & (stride - 1)):
+        if stride > 1 and (stride & (stride - 1)):
+            return self._stride_map_general(stride)
+        if stride <= 1:
             raise _lib.SvHipError(f"no coordinate map at tensor stride {stride}")
         fine = self.stride_map(stride // 2)
         level = (stride // 2).bit_length() - 1
@@ -202,6 +206,29 @@ class CoordinateManager:
         m = CoordinateMap(keys[:V], coords[:V], V, stride)
         self.maps[stride] = m
         self.parents[stride // 2] = (parent[:V_in], child_start[: V + 1])
+        return m
+
+    def _stride_map_general(self, stride):
+        divisors = [s for s in self.maps if stride % s == 0]
+        if not divisors:
+            raise _lib.SvHipError(f"no coordinate map at tensor stride {stride}: no existing map's stride divides it")
+        fine = self.maps[max(divisors)]
+        dev, V_in = self.device, fine.V
+        ws_bytes = _lib.load().sv_stride_map_general_workspace_bytes(c_int64(V_in))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        keys = torch.empty(max(V_in, 1), dtype=torch.int64, device=dev)
+        coords = torch.empty((max(V_in, 1), 4), dtype=torch.int32, device=dev)
+        parent = torch.empty(max(V_in, 1), dtype=torch.int32, device=dev)
+        counters = torch.empty(4, dtype=torch.int32, device=dev)
+        call("sv_stride_map_general", ptr(fine.keys), c_int64(V_in), c_int(fine.stride), c_int(stride), ptr(ws),
+             c_size_t(ws_bytes), ptr(keys), ptr(coords), ptr(parent), ptr(counters), stream_ptr())
+        V, bad = counters.tolist()[:2]
+        if bad:
+            raise _lib.SvHipError(f"{bad} voxels leave the key range at tensor stride {stride} "
+                                  f"(floor(c / {stride}) * {stride} < -2^17)")
+        m = CoordinateMap(keys[:V], coords[:V], V, stride)
+        self.maps[stride] = m
+        self.general_parents[(fine.stride, stride)] = parent[:V_in]
         return m
 
     # ---- plans -----------------------------------------------------------------------------
@@ -298,6 +325,37 @@ class CoordinateManager:
                  c_int64(max(V, 1)), ptr(mask), stream_ptr())
             self.plans[key] = self._own(self._build_plan(nbr, max(V, 1), mask, 8, V), nbr, max(V, 1), mask, stride, fs)
         return self.plans[key]
+
+    def _plan_probe(self, key, q_stride, t_stride, kernel_size, step):
+        """kernel map between two maps (sv_kernel_map_probe): output rows = the map at q_stride, inputs from t_stride"""
+        if key not in self.plans:
+            q, t = self.stride_map(q_stride), self.stride_map(t_stride)
+            tkeys, tvals, cap = t.hash()
+            K, ld = kernel_size ** 3, max(q.V, 1)
+            nbr = torch.empty((K, ld), dtype=torch.int32, device=self.device)
+            mask = torch.empty(ld, dtype=torch.int32, device=self.device)
+            call("sv_kernel_map_probe", ptr(q.coords), c_int64(q.V), c_int(kernel_size), c_int(step), ptr(t.coords),
+                 c_int64(t.V), ptr(tkeys), ptr(tvals), c_int64(cap), ptr(nbr), c_int64(ld), ptr(mask), stream_ptr())
+            self.plans[key] = self._own(self._build_plan(nbr, ld, mask, K, q.V), nbr, ld, mask, t_stride, q_stride)
+        return self.plans[key]
+
+    def plan_strided(self, in_stride, kernel_size, stride, dilation=1):
+        """kernel_size 3 or 1 convolution (or pooling) of stride `stride` from tensor stride in_stride to in_stride * stride:
+        the output map's rows probe the input map's table at +in_stride * dilation (the kernel is centred on the output)."""
+        if kernel_size not in (1, 3) or stride < 1 or dilation < 1:
+            raise _lib.SvHipError(f"plan_strided: kernel_size {kernel_size} stride {stride} dilation {dilation}")
+        self.stride_map(in_stride)  # the input map first: the output map is derived from the existing ones
+        return self._plan_probe(("strided", in_stride, kernel_size, stride, dilation), in_stride * stride, in_stride,
+                                kernel_size, in_stride * dilation)
+
+    def plan_strided_t(self, in_stride, kernel_size, stride, dilation=1):
+        """the transpose of plan_strided's map (input gradient of the conv, backward of the pooling): the input map's rows
+        probe the output map's table at -in_stride * dilation; nbr[k][o] = i there exactly when nbr_t[k][i] = o here."""
+        if kernel_size not in (1, 3) or stride < 1 or dilation < 1:
+            raise _lib.SvHipError(f"plan_strided_t: kernel_size {kernel_size} stride {stride} dilation {dilation}")
+        self.stride_map(in_stride)
+        return self._plan_probe(("strided_t", in_stride, kernel_size, stride, dilation), in_stride, in_stride * stride,
+                                kernel_size, -in_stride * dilation)
 
     # ---- frame composites (sv_frame_plans): everything a U-Net asks for in one or two host calls ------------
     def split_cuts_for(self, rows):

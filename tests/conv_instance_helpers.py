@@ -73,16 +73,16 @@ SWEEP_VPAD = tuple(range(128, 136 * 1024 + 1, 128))
 
 def sweep():
     """{(name, fast, ring, full)} of every combination the public call reaches, each with the first shape that reaches it.
-    has_plan = (K > 1): nn.conv_forward gives dense rows no plan and every kernel map one.  vec_a is swept over both values
-    where Cin allows it (a view whose row stride or start is not 16-byte aligned); buf_ok = False only with a plan (a `perm`
-    off a 16-byte boundary; without a plan it takes a tensor beyond 2 GB, which sv_conv_fwd_acc splits into row ranges that
-    fit).  One library call per (scale, K, Cin, vec_a, Cout, buf_ok, acc_init) answers all its row counts."""
+    K > 1 always comes with a plan.  K = 1 is swept WITHOUT one (dense rows: kernel_size 1 stride 1, Linear) and WITH one (the
+    kernel_size 1 strided maps of plan_strided / plan_strided_t, tests/test_gpu_conv_strided.py).  vec_a is swept over both
+    values where Cin allows it (a view whose row stride or start is not 16-byte aligned); buf_ok = False only with a plan (a
+    `perm` off a 16-byte boundary; without a plan it takes a tensor beyond 2 GB, which sv_conv_fwd_acc splits into row ranges
+    that fit).  One library call per (scale, K, plan, Cin, vec_a, Cout, buf_ok, acc_init) answers all its row counts."""
     seen = {}
     shapes = np.zeros((len(SWEEP_VPAD), 5), np.int64)
     shapes[:, 3] = SWEEP_VPAD
     for ws in SWEEP_SCALES:
-        for K in SWEEP_K:
-            has_plan = K > 1
+        for K, has_plan in [(K, K > 1) for K in SWEEP_K] + [(1, True)]:
             for Cin in SWEEP_CIN:
                 for vec_a in ((True, False) if Cin % 4 == 0 else (False,)):
                     for Cout in SWEEP_COUT:

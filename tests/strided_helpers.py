@@ -1,5 +1,7 @@
 """Helpers shared by the strided-map, local-pooling, instance-norm and ResNet tests: numpy restatements of the definitions
-in include/sv_hip.h (block N8) and thin wrappers that call the library's entries on torch tensors."""
+in include/sv_hip.h (block N8) and thin wrappers that call the library's entries on torch tensors; at the end the map kinds,
+compact-blob frames and the case table of the convolution tests on these maps (tests/test_gpu_conv_strided.py)."""
+from collections import namedtuple
 from ctypes import c_double, c_int, c_int64, c_size_t
 
 import numpy as np
@@ -247,3 +249,180 @@ def blob_cloud(rng, n, centres, sigma, lo, hi):
         p = p[np.all((p >= lo) & (p < hi), axis=1)]
         pts = np.unique(np.concatenate([pts, p]), axis=0)
     return pts[rng.permutation(len(pts))[:n]]
+
+
+# ---- the strided / dilated kernel-map kinds of the convolution tests ----------------------------------------------------
+# (tests/test_conv_strided_cpu.py, tests/test_gpu_conv_strided.py, tests/test_gpu_conv_exact.py)
+# kind -> (kernel_size, stride, dilation, transposed), all from tensor stride 1; "k3d2" is the dilated stride-1 3x3x3 map
+MAP_KINDS = {"k3s2": (3, 2, 1, False), "k3s3": (3, 3, 1, False), "k1s2": (1, 2, 1, False), "k3s2d2": (3, 2, 2, False),
+             "k3s2_t": (3, 2, 1, True), "k3s3_t": (3, 3, 1, True), "k1s2_t": (1, 2, 1, True), "k3s2d2_t": (3, 2, 2, True),
+             "k3d2": (3, 1, 2, False)}
+EMPTY_TILE_KINDS = ("k1s2_t", "k3s2d2_t")  # about 7 of 8 output rows have no neighbour at all
+
+
+def compact_blob(V, batch=0, origin=(0, 0, 0)):
+    """V integer voxels [V, 4] of a compact block (x fastest) centred on `origin`: V is exact and 3x3x3 neighbours exist"""
+    if V == 0:
+        return np.zeros((0, 4), np.int64)
+    s = int(np.ceil(V ** (1.0 / 3.0)))
+    while s ** 3 < V:
+        s += 1
+    i = np.arange(V, dtype=np.int64)
+    c = np.stack([np.full(V, batch, np.int64), i % s, (i // s) % s, i // (s * s)], axis=1)
+    c[:, 1:] += np.asarray(origin, np.int64) - s // 2
+    return c
+
+
+# frame name -> [(voxels, origin)] per batch index; every fine map has V % 128 == 67 (707; 835 + 640 = 1475; 24003, the
+# size of the existing dual-body row); the second frame of "two" lies wholly at negative coordinates of mixed parity
+FRAMES = {"one": [(707, (0, 0, 0))], "two": [(835, (1, 0, 0)), (640, (-37, -20, -9))], "big": [(24003, (0, 0, 0))],
+          # four batch indices, one of them empty: the batch-range tests (ConvPlan.chunks)
+          "batch": [(419, (0, 0, 0)), (0, (0, 0, 0)), (707, (-21, 3, -8)), (349, (5, -30, 2))]}
+_coords, _tables = {}, {}
+
+
+def frame_input(name):
+    """the integer coordinates [N, 4] a frame's coordinate manager is built from"""
+    return np.concatenate([compact_blob(V, b, o) for b, (V, o) in enumerate(FRAMES[name])])
+
+
+def frame_coords(name):
+    """canonical stride-1 coordinates of a frame (the device's row order), computed once"""
+    if name not in _coords:
+        _coords[name] = canonical(frame_input(name))[0]
+    return _coords[name]
+
+
+def batch_bounds_ref(coords, B):
+    """first row of every batch index of canonical coordinates (rows ascend by batch first), [B + 1]"""
+    return [int(np.searchsorted(coords[:, 0], b)) for b in range(B + 1)]
+
+
+def kind_table_of(c1, kind):
+    """(nbr int32[K][V_out], V_in, V_out) of a map kind on canonical stride-1 coordinates, from probe_ref alone: a forward
+    kind's output rows probe the input map at +dilation, a transposed kind's rows (the input map) probe the output map at
+    -dilation"""
+    ks, st, dil, transposed = MAP_KINDS[kind]
+    if st == 1:
+        return probe_ref(c1, c1, ks, dil), len(c1), len(c1)
+    cs = stride_map_ref(c1, st)[0]
+    if transposed:
+        return probe_ref(c1, cs, ks, -dil), len(cs), len(c1)
+    return probe_ref(cs, c1, ks, dil), len(c1), len(cs)
+
+
+def kind_table(name, kind):
+    """kind_table_of on a named frame, computed once and never changed"""
+    if (name, kind) not in _tables:
+        nbr, V_in, V_out = kind_table_of(frame_coords(name), kind)
+        nbr.setflags(write=False)
+        _tables[(name, kind)] = (nbr, V_in, V_out)
+    return _tables[(name, kind)]
+
+
+def kind_plan(cm, kind):
+    """the library's plan of a map kind on a coordinate manager (tensor stride 1)"""
+    ks, st, dil, transposed = MAP_KINDS[kind]
+    if st == 1:
+        return cm.plan_k3(1, dil)
+    return cm.plan_strided_t(1, ks, st, dil) if transposed else cm.plan_strided(1, ks, st, dil)
+
+
+def plan_tile_census(plan):
+    """(all_empty bool[tiles], mixed bool[tiles]) of a plan's 128-row tiles: all_empty = every row is a real output row
+    (perm >= 0) and every submask word is zero; mixed = among the tile's 16-row sub-tiles that hold only real rows some have a
+    neighbour at some offset and some have none"""
+    perm = plan.perm.cpu().numpy().reshape(-1, 128)
+    sub = plan.submask.cpu().numpy().reshape(perm.shape[0], plan.K).astype(np.int64) & 0xFF
+    live = np.bitwise_or.reduce(sub, axis=1)                      # bit s: sub-tile s has a pair at some offset
+    real = (perm.reshape(-1, 8, 16) >= 0).all(2)                  # [tiles, 8]: the sub-tile holds only real rows
+    bits = (live[:, None] >> np.arange(8)[None]) & 1
+    all_empty = (perm >= 0).all(1) & (sub == 0).all(1)
+    mixed = ((bits == 1) & real).any(1) & ((bits == 0) & real).any(1)
+    return all_empty, mixed
+
+
+# ---- the table of tests/test_gpu_conv_strided.py (a): fp32 forward on the strided maps, bit-exact against the oracle ----
+# frame, kind: the map; scale: None = the library's default dispatch, 1.0 = under conv_dispatch(1.0); mis: `perm` 4 bytes off
+# a 16-byte boundary; name, fast, ring, full: what sv_conv_last_instance() must report, as literals
+# (tests/test_conv_strided_cpu.py holds them to the library's own host-side answer)
+StridedCase = namedtuple("StridedCase", "frame kind Cin Cout scale mis name fast ring full")
+
+FIRST_MFMA, FIRST_VALU = "conv_first_mfma_kernel<3, 32>", "conv_first_layer_kernel<3, 32>"
+THIN, THIN_LDS = "conv_thin_kernel<32, 32>", "conv_thin_lds_kernel<32, 32>"
+DUAL = "conv_fwd_dual_kernel<64, 32, 4, 3>"
+T16_64, T16_192 = "conv_fwd_kernel<16, 4, 1>", "conv_fwd_kernel<16, 4, 3>"
+F32, F64 = "conv_fwd_kernel<16, 4, 1, fused 32>", "conv_fwd_kernel<16, 4, 1, fused 64>"
+T64_16 = "conv_fwd_kernel<64, 1, 1>"
+
+STRIDED_CASES = tuple(StridedCase(*r) for r in (
+    # the 3 -> 32 first layer on the matrix pipe and, with a misaligned `perm`, on the vector ALU (K = 27 only)
+    ("one", "k3s2", 3, 32, None, False, FIRST_MFMA, 1, 0, 1),
+    ("one", "k3s2d2_t", 3, 32, None, False, FIRST_MFMA, 1, 0, 1),
+    ("one", "k3s2", 3, 32, None, True, FIRST_VALU, 0, 0, 0),
+    ("one", "k3s2d2_t", 3, 32, None, True, FIRST_VALU, 0, 0, 0),
+    # the thin 32 -> 32 layer, and its LDS-weights kernel when the frame is alone on the GPU
+    ("one", "k3s3", 32, 32, None, False, THIN, 1, 0, 1),
+    ("one", "k3s2d2_t", 32, 32, None, False, THIN, 1, 0, 1),
+    ("one", "k3s2", 32, 32, 1.0, False, THIN_LDS, 1, 0, 1),
+    ("one", "k3s2d2_t", 32, 32, 1.0, False, THIN_LDS, 1, 0, 1),
+    # the fused-offset tiles, FAST and guarded
+    ("one", "k3s2", 32, 64, None, False, F32, 1, 1, 0),
+    ("two", "k3s2d2_t", 32, 64, None, False, F32, 1, 1, 0),
+    ("one", "k3s2d2_t", 32, 64, None, True, F32, 0, 1, 0),
+    ("one", "k3d2", 64, 64, None, False, F64, 1, 1, 0),
+    ("one", "k3s2d2_t", 64, 64, None, False, F64, 1, 1, 0),
+    ("two", "k3s2_t", 64, 64, None, False, F64, 1, 1, 0),
+    ("one", "k3s3_t", 64, 64, None, True, F64, 0, 1, 0),
+    ("one", "k3s2d2", 64, 128, None, False, F64, 1, 1, 0),
+    ("one", "k3s2d2_t", 64, 128, None, False, F64, 1, 1, 0),
+    ("two", "k3s2d2_t", 64, 128, 1.0, True, F64, 0, 1, 0),
+    # the same widths at K = 1 WITH a plan: the plain lists, not the fused ones
+    ("one", "k1s2", 32, 64, None, False, T16_64, 1, 1, 0),
+    ("one", "k1s2_t", 32, 64, None, False, T16_64, 1, 1, 0),
+    ("one", "k1s2", 64, 64, None, False, T16_64, 1, 1, 0),
+    ("two", "k1s2_t", 64, 64, None, False, T16_64, 1, 1, 0),
+    ("one", "k1s2", 64, 128, None, False, T16_64, 1, 1, 0),
+    ("one", "k1s2_t", 64, 128, None, False, T16_64, 1, 1, 0),
+    ("one", "k1s2_t", 64, 128, None, True, T16_64, 0, 1, 0),
+    # the ResNet stem 3 -> 64 (odd Cin: guarded) and other guarded widths (odd Cin at K = 1, a partial column tile)
+    ("one", "k3s2", 3, 64, None, False, T16_64, 0, 1, 0),
+    ("one", "k3s2d2_t", 3, 64, None, False, T16_64, 0, 1, 0),
+    ("two", "k1s2_t", 131, 48, None, False, T16_64, 0, 1, 0),
+    ("one", "k3s2d2_t", 148, 80, None, False, "conv_fwd_kernel<32, 2, 2>", 0, 1, 0),
+    # a 64-column tile in FULL form
+    ("one", "k1s2", 256, 64, None, False, T16_64, 1, 1, 1),
+    ("one", "k1s2_t", 256, 64, None, False, T16_64, 1, 1, 1),
+    # the Bottleneck downsample 64 -> 256 k1 s2: on maps this small the 128-column list ends on its 64-column tile; the same
+    # layer's input gradient map at 24003 rows reaches a 128-column tile
+    ("one", "k1s2", 64, 256, None, False, T16_64, 1, 1, 0),
+    ("two", "k1s2_t", 64, 256, None, False, T16_64, 1, 1, 0),
+    ("big", "k1s2_t", 64, 256, None, False, "conv_fwd_kernel<64, 4, 2>", 1, 0, 0),
+    ("one", "k3s3", 512, 512, None, False, T16_64, 1, 1, 1),
+    ("one", "k3s2d2_t", 512, 512, None, False, T16_64, 1, 1, 1),
+    # a 192-column tile in FULL form
+    ("two", "k3s2", 256, 384, None, False, T16_192, 1, 1, 1),
+    ("one", "k1s2_t", 256, 384, None, False, T16_192, 1, 1, 1),
+    # the dual-body launch: its 32-row tail body runs the cheapest plan tiles, which on this map are the empty ones
+    ("big", "k1s2_t", 148, 384, None, False, DUAL, 1, 0, 0),
+    # K = 1 with a plan and at most four outputs: NOT the narrow (dense-row) kernel
+    ("one", "k1s2", 148, 1, None, False, T64_16, 0, 1, 0),
+    ("one", "k1s2_t", 148, 1, None, False, T64_16, 0, 1, 0),
+    ("one", "k1s2", 148, 3, None, False, T64_16, 0, 1, 0),
+    ("one", "k1s2_t", 148, 3, None, False, T64_16, 0, 1, 0),
+    ("one", "k1s2", 148, 4, None, False, T64_16, 0, 1, 0),
+    ("one", "k1s2_t", 148, 4, None, False, T64_16, 0, 1, 0),
+))
+
+
+def strided_case_id(c):
+    tile = c.name.replace("conv_", "").replace("_kernel", "").replace(" ", "")
+    return (f"{tile}-f{c.fast}r{c.ring}u{c.full}-{c.frame}-{c.kind}-{c.Cin}x{c.Cout}" + ("-alone" if c.scale else "") +
+            ("-perm_misaligned" if c.mis else ""))
+
+
+# (b) the special kernels at row edges on the k3s2d2_t map of a V-voxel blob centred on (1, 1, 1), so that the only voxel of
+# V = 1 has odd coordinates and no neighbour at all: (name, (fast, ring, full), Cin, Cout, scale, perm misaligned)
+EDGE_V = (1, 15, 16, 17, 127, 128, 129)
+EDGE_SPECIAL = ((THIN, (1, 0, 1), 32, 32, None, False), (THIN_LDS, (1, 0, 1), 32, 32, 1.0, False),
+                (FIRST_MFMA, (1, 0, 1), 3, 32, None, False), (FIRST_VALU, (0, 0, 0), 3, 32, None, True))

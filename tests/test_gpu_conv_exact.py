@@ -1,7 +1,8 @@
 """The bf16 forward (sv_conv_fwd_bf16) and both weight-gradient kernels (sv_conv_wgrad, sv_conv_wgrad_bf16) against
 exact integer references on EVERY element (tests/conv_exact_helpers.py): with small-integer operands every product and
 every partial sum is exact in fp32 in any order, so the kernels must return the int64 gather / index_add result of the
-raw kernel map bit for bit.  Covered: every column-block instance of the bf16 forward, dense row-count edges, offset-range
+raw kernel map bit for bit.  Covered: every column-block instance of the bf16 forward on every map kind (the strided maps
+with whole plan tiles of rows without a neighbour included), dense row-count edges, offset-range
 passes with empty workgroups, the in-register fp32 -> bf16 rounding of both kernels on a table of special values, odd
 shapes and misaligned bases of the fp32 weight gradient, and batch-range launches (ConvPlan.chunks) of everything but
 the fp32 forward.  Non-integer data stays under the tolerance tests (test_gpu_conv_bf16.py, test_gpu_conv_grad.py,
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 import conv_exact_helpers as H
+import strided_helpers as S
 
 pytestmark = pytest.mark.gpu
 
@@ -19,8 +21,12 @@ ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 # column tiles that divides Cout / 16)
 COUT_TN = {64: 64, 80: 16, 96: 96, 128: 128, 160: 32, 192: 192, 256: 256, 384: 384}
 KINDS = ("k3", "down", "up", "dense")
+# kernel maps of the strided layers: V_out < V_in, K = 1 with a plan, and the two transposed maps on which about 7 output rows
+# of 8 have no neighbour at all (whole plan tiles of real rows with all-zero submask words)
+STRIDED_KINDS = ("k3s2", "k1s2", "k1s2_t", "k3s2d2_t")
 
 _frames = {}
+_checked = set()
 
 
 def _frame(gpu, name, clouds):
@@ -51,6 +57,14 @@ def _scatter(gpu):
 def _map(cm, kind, V_dense=300):
     """(plan, nbr table, V_in, V_out, K) of a map kind on a frame"""
     V1, V2 = cm.stride_map(1).V, cm.stride_map(2).V
+    if kind in STRIDED_KINDS:  # the strided maps of the ResNets (strided_helpers.MAP_KINDS), raw table held to probe_ref
+        plan = S.kind_plan(cm, kind)
+        if (id(cm), kind) not in _checked:
+            nbr, V_in, V_out = S.kind_table_of(cm.stride_map(1).coords.cpu().numpy(), kind)
+            assert (plan.V_out, cm.stride_map(plan.in_stride).V) == (V_out, V_in)
+            assert np.array_equal(plan.raw[0][:, :V_out].cpu().numpy(), nbr)
+            _checked.add((id(cm), kind))
+        return plan, plan.raw[0], cm.stride_map(plan.in_stride).V, plan.V_out, plan.K
     if kind == "k3":
         plan = cm.plan_k3(1)
         return plan, plan.raw[0], V1, V1, 27
@@ -127,6 +141,18 @@ def test_bf16_forward_every_instance_every_map_exact(gpu, cin, cout):
     cm = _one(gpu)
     for j, kind in enumerate(KINDS):
         _fwd_case(gpu, cm, kind, cin, cout, seed=1000 * cout + 10 * cin + j)
+
+
+@pytest.mark.parametrize("cout", sorted(COUT_TN))
+def test_bf16_forward_every_instance_every_strided_map_exact(gpu, cout):
+    """every conv_bf16_kernel<128, TN> on the strided kinds; on the two transposed ones a tile of real rows without any pair
+    must still write act(scale * 0 + shift + residual) over the sentinel"""
+    cm = _one(gpu)
+    for kind in ("k1s2_t", "k3s2d2_t"):
+        all_empty, mixed = S.plan_tile_census(_map(cm, kind)[0])
+        assert all_empty.any() and mixed.any(), kind
+    for j, kind in enumerate(STRIDED_KINDS):
+        _fwd_case(gpu, cm, kind, 64, cout, seed=2000 * cout + j)
 
 
 @pytest.mark.parametrize("kind,cout", [("k3", 192), ("down", 80), ("up", 160), ("dense", 384)])

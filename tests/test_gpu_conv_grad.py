@@ -65,13 +65,13 @@ def _weight3_grad(layer):
     return g if g.dim() == 3 else g.unsqueeze(0)
 
 
-def _layer_case(gpu, cin, cout, ks=3, stride=1, transposed=False, bias=False, clouds=None, cat=0):
+def _layer_case(gpu, cin, cout, ks=3, stride=1, transposed=False, bias=False, clouds=None, cat=0, dilation=1):
     from mrcc_amd import MinkowskiEngine as ME
     from mrcc_amd import nn as svnn
 
     torch.manual_seed(cin * 1000 + cout)
     cls = ME.MinkowskiConvolutionTranspose if transposed else ME.MinkowskiConvolution
-    layer = cls(cin, cout, kernel_size=ks, stride=stride, bias=bias, dimension=3).to(gpu).train()
+    layer = cls(cin, cout, kernel_size=ks, stride=stride, dilation=dilation, bias=bias, dimension=3).to(gpu).train()
     clouds = clouds or [_cloud(1, 1500)]
     x0 = _tensor(gpu, clouds, cin + cat)
     x = x0
@@ -82,10 +82,11 @@ def _layer_case(gpu, cin, cout, ks=3, stride=1, transposed=False, bias=False, cl
         cm.plan_down(1)
         f2 = torch.randn(cm.stride_map(2).V, cin, generator=torch.Generator().manual_seed(3)).to(gpu).requires_grad_(True)
         x = x0.new(f2, tensor_stride=2)
-    plan, out_stride = layer._plan(x)
+    plan, out_stride = layer._plan(x)  # (a strided layer's plan creates its output map)
     whole = plan.whole if isinstance(plan, svnn.SplitPlan) else plan
     V_out = x.coordinate_manager.stride_map(out_stride).V
     nbr = whole.raw[0] if whole is not None else torch.arange(V_out, device=gpu, dtype=torch.int32)[None]
+    assert whole is None or (whole.V_out == V_out and nbr.shape[0] == ks ** 3)
     out = layer.forward_fused(x)
     dy = torch.randn(out.F.shape, generator=torch.Generator().manual_seed(9)).to(gpu)
     out.F.backward(dy)
@@ -95,9 +96,16 @@ def _layer_case(gpu, cin, cout, ks=3, stride=1, transposed=False, bias=False, cl
     W = layer.weight3().detach()
     fin = x.F.detach()
     want_dx, want_dw, terms_dx, terms_dw = _ref_grads(fin, W, nbr, V_out, dy)
-    tag = f"{cin}->{cout} k{ks} s{stride}{' tr' if transposed else ''}"
+    tag = f"{cin}->{cout} k{ks} s{stride}{f' d{dilation}' if dilation > 1 else ''}{' tr' if transposed else ''}"
     _check(tag + " dX", dx, want_dx, terms_dx)
     _check(tag + " dW", dw, want_dw, terms_dw)
+    if ks == 1 and stride > 1:
+        # input rows that no output reads: the reference gives exactly 0, and so must the kernel (its plan tiles without a
+        # single pair still write their rows)
+        unseen = torch.ones(fin.shape[0], dtype=torch.bool, device=gpu)
+        unseen[nbr[nbr >= 0].long()] = False
+        assert int(unseen.sum()) * 2 > fin.shape[0] and bool((want_dx[unseen] == 0).all())
+        assert bool((dx[unseen] == 0).all()), f"{tag}: {int((dx[unseen] != 0).sum())} nonzero elements in rows no output reads"
     if bias:
         assert torch.allclose(layer.bias.grad.double().flatten(), dy.double().sum(0), rtol=1e-5, atol=1e-4)
     # a second backward gives the same bits (no atomics in either gradient)
@@ -140,6 +148,31 @@ def test_1x1_with_bias(gpu):
 def test_batch_of_two_frames(gpu):
     _layer_case(gpu, 32, 64, clouds=[_cloud(7, 1200), _cloud(8, 800)])
     _layer_case(gpu, 32, 32, ks=2, stride=2, clouds=[_cloud(7, 1200), _cloud(8, 800)])
+
+
+# ---- the strided, kernel_size 1 strided and dilated layers of the classification ResNets: dX on plan_strided_t with W[k]^T
+#      (no mirror), dW on the forward plan; on the dilated stride-1 layer dX takes the mirror rule on a dilated map
+@pytest.mark.parametrize("cin,cout", [(3, 64), (64, 64)])
+def test_k3_stride2_layer_gradients(gpu, cin, cout):
+    _layer_case(gpu, cin, cout, ks=3, stride=2)
+
+
+def test_k3_stride3_layer_gradients(gpu):
+    _layer_case(gpu, 64, 64, ks=3, stride=3)
+
+
+def test_k1_stride2_with_bias(gpu):
+    _layer_case(gpu, 64, 256, ks=1, stride=2, bias=True)
+
+
+def test_k3_dilated_layer_gradients(gpu):
+    _layer_case(gpu, 32, 32, ks=3, stride=1, dilation=2)
+    _layer_case(gpu, 32, 64, ks=3, stride=2, dilation=2)
+
+
+def test_strided_layers_batch_of_two_frames(gpu):
+    _layer_case(gpu, 32, 64, ks=3, stride=2, clouds=[_cloud(7, 1200), _cloud(8, 800)])
+    _layer_case(gpu, 64, 96, ks=1, stride=2, clouds=[_cloud(7, 1200), _cloud(8, 800)])
 
 
 @pytest.mark.parametrize("cin,cout", [(256, 1024), (1024, 3)])

@@ -106,8 +106,8 @@ int sv_voxel_reduce(const float* feats, int C, const int32_t* order, const int32
  * ME.MinkowskiConvolution call of model/backbone/minkunet.py:55-121)
  * ------------------------------------------------------------------------------------------- */
 /* open-addressing hash  key -> row ;  capacity must be a power of two >= 2*V.  An empty slot holds the key ~0, which is
- * also the key of the voxel (1023, 2^17-1, 2^17-1, 2^17-1): that key is not stored; sv_kernel_map_k3 finds the voxel as the
- * last row of its (canonical) vcoords instead. */
+ * also the key of the voxel (1023, 2^17-1, 2^17-1, 2^17-1): that key is not stored; sv_kernel_map_k3 and
+ * sv_kernel_map_probe find the voxel as the last row of the table map's (canonical) vcoords instead. */
 int sv_hash_build(const uint64_t* keys, int64_t V, uint64_t* table_keys, int32_t* table_vals, int64_t capacity,
                   sv_stream_t stream);
 
@@ -1129,7 +1129,9 @@ int sv_select_equal(const void* v, int elem_bytes, int64_t n, int64_t value, con
  *   dilation.  nbr[k*ld + o] = row in the table's map of coords_q[o] + d_k * step, or -1 (also when that coordinate leaves
  *   the key range); mask[o] bit k = present.  Forward map of a strided conv: queries = output map, table = input map, +step;
  *   map of its input gradient (and of pooling's backward): queries = input map, table = output map, -step - the transpose:
- *   nbr[k][o] = i exactly when nbr_t[k][i] = o.
+ *   nbr[k][o] = i exactly when nbr_t[k][i] = o.  sv_kernel_map_k3(vcoords, V, tensor_stride, dilation, ...) is its
+ *   same-map case - (vcoords_q, V_q) = (vcoords_t, V_t) = (vcoords, V), kernel_size 3, step = tensor_stride * dilation - on
+ *   the same kernel, which then writes the centre offset's nbr[13][o] = o without a lookup; the tables are equal.
  * ------------------------------------------------------------------------------------------- */
 size_t sv_stride_map_general_workspace_bytes(int64_t V_in);
 int sv_stride_map_general(const uint64_t* keys_in, int64_t V_in, int s_in, int s_out, void* workspace, size_t workspace_bytes,

@@ -90,7 +90,7 @@ __host__ __device__ __forceinline__ void decode_key(uint64_t key, int& b, int& x
 }
 // Marker of an empty hash slot.  All 64 bits of a key are in use, so this value is also the key of ONE valid voxel: batch
 // 1023 at x = y = z = 2^17 - 1.  The table never stores that key (hash_insert_kernel skips it) and hash_find must not be asked
-// for it: being the largest key, the voxel can only be the LAST row of a canonical map, which is how kmap_k3_probe_kernel
+// for it: being the largest key, the voxel can only be the LAST row of a canonical map, which is how kmap_probe_kernel
 // resolves it.
 #define SV_EMPTY_KEY 0xffffffffffffffffull
 

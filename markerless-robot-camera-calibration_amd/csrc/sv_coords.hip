@@ -236,41 +236,51 @@ __global__ __launch_bounds__(256) void stride_scatter_kernel(const uint64_t* __r
 // ------------------------------------------------------------------------------------------------
 // kernel maps
 // ------------------------------------------------------------------------------------------------
-// One THREAD per (voxel, offset) probe: blockIdx.y = offset k, so a workgroup resolves offset k for 256 consecutive voxels
+// One THREAD per (query row, offset) probe: blockIdx.y = offset k, so a workgroup resolves offset k for 256 consecutive rows
 // (coalesced coordinate reads and nbr[k][.] writes).  The probe of a neighbour is a dependent chain (hash -> slot -> maybe
 // the next slot) that cannot be pipelined inside a thread; with one probe per thread the 27 V chains overlap through
 // occupancy instead (2.4 M threads at the 2 cm room level), where the thread-per-voxel form of round 1 walked its 27
 // chains one after the other on ~1.3 waves per SIMD (64 us alone on the GPU, ~320 us beside the convolutions).
-__global__ __launch_bounds__(256) void kmap_k3_probe_kernel(const int32_t* __restrict__ vcoords, int64_t V, int step,
-                                                             const uint64_t* __restrict__ tkeys,
-                                                             const int32_t* __restrict__ tvals, uint64_t cap_mask,
-                                                             int32_t* __restrict__ nbr, int64_t ld) {
+//
+// The query rows (vcoords_q) probe the hash table of the map (vcoords_t, V_t > 0): two maps for a strided layer, one and
+// the same for the 3x3x3 table.  Two arguments set by the host make the cases one kernel:
+//   self_k  the offset at which a query row is its own neighbour: 13 for kernel_size 3 on the same map, where r = o needs no
+//           lookup (no 27th probe chain per voxel on the per-frame path, and right for the voxel whose key is SV_EMPTY_KEY
+//           too); -1 between two maps, where the centre is a probe like any other;
+//   step    0 for kernel_size 1: a grid of one offset whose decoded (-1, -1, -1) then adds nothing.
+// What every wave reads - all but (vcoords_t, V_t) - fills the first 64 bytes of the arguments, as the arguments of the
+// same-map-only kernel did, and self_k is tested BEFORE the row bound: hipcc then fetches V_q, step and self_k in one
+// scalar-load wait and the coordinate pointer in a second one, that kernel's two waits in front of the coordinate load.
+// Tested after the bound it costs every wave a third wait, which this latency-bound kernel shows (+0.5 us in 39 us at
+// 88k voxels).
+__global__ __launch_bounds__(256) void kmap_probe_kernel(const int32_t* __restrict__ vcoords_q, int64_t V_q, int step, int self_k,
+                                                          const uint64_t* __restrict__ tkeys,
+                                                          const int32_t* __restrict__ tvals, uint64_t cap_mask,
+                                                          int32_t* __restrict__ nbr, int64_t ld,
+                                                          const int32_t* __restrict__ vcoords_t, int64_t V_t) {
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o >= V) return;
   const int k = blockIdx.y;
-  const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-  int r;
-  if (k == 13) {
-    r = (int)o;
-  } else {
-    const int4 c = ((const int4*)vcoords)[o];
+  int r = (int)o;
+  if (k != self_k) {
+    if (o >= V_q) return;
+    const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
+    const int4 c = ((const int4*)vcoords_q)[o];
     const int x = c.y + dx * step, y = c.z + dy * step, z = c.w + dz * step;
-    if (!coord_in_range(c.x, x, y, z)) {
-      r = -1;  // outside the key range: make_key would wrap it onto the opposite face
-    } else {
+    r = -1;
+    if (coord_in_range(c.x, x, y, z)) {  // outside the key range: make_key would wrap it onto the opposite face
       const uint64_t key = make_key(c.x, x, y, z);
       if (key != SV_EMPTY_KEY) {
         r = hash_find(tkeys, tvals, cap_mask, key);
-      } else {  // the largest key there is: present iff it is the last row of the (key-sorted) map
-        const int4 l = ((const int4*)vcoords)[V - 1];
-        r = (l.x == c.x && l.y == x && l.z == y && l.w == z) ? (int)(V - 1) : -1;
+      } else {  // the largest key there is: present iff it is the last row of the table's (key-sorted) map
+        const int4 l = ((const int4*)vcoords_t)[V_t - 1];
+        r = (l.x == c.x && l.y == x && l.z == y && l.w == z) ? (int)(V_t - 1) : -1;
       }
     }
   }
-  nbr[(int64_t)k * ld + o] = r;
+  if (o < V_q) nbr[(int64_t)k * ld + o] = r;
 }
 
-// mask[o] = bit k set iff nbr[k][o] >= 0 (27 coalesced reads per voxel)
+// mask[o] = bit k set iff nbr[k][o] >= 0 (K coalesced reads per voxel)
 __global__ __launch_bounds__(256) void kmap_mask_kernel(const int32_t* __restrict__ nbr, int64_t ld, int K, int64_t V,
                                                          uint32_t* __restrict__ mask) {
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -509,19 +519,47 @@ int sv_stride_map(const uint64_t* keys_in, int64_t V_in, int level, void* worksp
   return SV_OK;
 }
 
+// probe + mask of a kernel map between the query map (vcoords_q, V_q > 0) and the table's map; same_map: they are one map
+static int launch_kernel_map_probe(const int32_t* vcoords_q, int64_t V_q, int ks, int step, bool same_map,
+                                   const int32_t* vcoords_t, int64_t V_t, const uint64_t* table_keys, const int32_t* table_vals,
+                                   int64_t capacity, int32_t* nbr, int64_t ld, uint32_t* mask, hipStream_t stream) {
+  const int K = ks * ks * ks;
+  const unsigned nb = (unsigned)((V_q + 255) / 256);
+  if (V_t == 0) {  // an empty table map: no neighbour anywhere, and neither the table nor vcoords_t is read
+    SV_HIP(hipMemset2DAsync(nbr, (size_t)ld * sizeof(int32_t), 0xff, (size_t)V_q * sizeof(int32_t), K, stream));
+    SV_HIP(hipMemsetAsync(mask, 0, (size_t)V_q * sizeof(uint32_t), stream));
+    return SV_OK;
+  }
+  hipLaunchKernelGGL(kmap_probe_kernel, dim3(nb, K), dim3(256), 0, stream, vcoords_q, V_q, ks == 3 ? step : 0,
+                     (same_map && ks == 3) ? 13 : -1, table_keys, table_vals, (uint64_t)(capacity - 1), nbr, ld, vcoords_t, V_t);
+  hipLaunchKernelGGL(kmap_mask_kernel, dim3(nb), dim3(256), 0, stream, nbr, ld, K, V_q, mask);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}
+
 int sv_kernel_map_k3(const int32_t* vcoords, int64_t V, int tensor_stride, int dilation, const uint64_t* table_keys,
                      const int32_t* table_vals, int64_t capacity, int32_t* nbr, int64_t ld, uint32_t* mask,
                      sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   SV_CHECK_ARG(V >= 0 && ld >= V && tensor_stride > 0 && dilation > 0, "bad shape");
   SV_CHECK_ARG(capacity >= 2 && (capacity & (capacity - 1)) == 0, "capacity must be a power of two");
   if (V == 0) return SV_OK;
   SV_CHECK_ARG(vcoords && table_keys && table_vals && nbr && mask, "null pointer");
-  hipLaunchKernelGGL(kmap_k3_probe_kernel, dim3((unsigned)((V + 255) / 256), 27), dim3(256), 0, stream, vcoords, V,
-                     tensor_stride * dilation, table_keys, table_vals, (uint64_t)(capacity - 1), nbr, ld);
-  hipLaunchKernelGGL(kmap_mask_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, stream, nbr, ld, 27, V, mask);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  return launch_kernel_map_probe(vcoords, V, 3, tensor_stride * dilation, true, vcoords, V, table_keys, table_vals, capacity,
+                                 nbr, ld, mask, (hipStream_t)stream_);
+}
+
+int sv_kernel_map_probe(const int32_t* vcoords_q, int64_t V_q, int kernel_size, int step, const int32_t* vcoords_t, int64_t V_t,
+                        const uint64_t* table_keys, const int32_t* table_vals, int64_t capacity, int32_t* nbr, int64_t ld,
+                        uint32_t* mask, sv_stream_t stream_) {
+  SV_CHECK_ARG(kernel_size == 1 || kernel_size == 3, "kernel_size must be 1 or 3");
+  SV_CHECK_ARG(V_q >= 0 && V_t >= 0 && ld >= V_q, "bad shape (ld < V_q)");
+  SV_CHECK_ARG(step != 0 && step > -(1 << SV_COORD_BITS) && step < (1 << SV_COORD_BITS), "step out of range");
+  SV_CHECK_ARG(capacity >= 2 && (capacity & (capacity - 1)) == 0 && capacity >= 2 * V_t,
+               "capacity must be a power of two >= 2 * V_t");
+  if (V_q == 0) return SV_OK;
+  SV_CHECK_ARG(vcoords_q && table_keys && table_vals && nbr && mask && (vcoords_t || V_t == 0), "null pointer");
+  return launch_kernel_map_probe(vcoords_q, V_q, kernel_size, step, false, vcoords_t, V_t, table_keys, table_vals, capacity,
+                                 nbr, ld, mask, (hipStream_t)stream_);
 }
 
 int sv_kernel_map_down(const uint64_t* keys_fine, const int32_t* parent, int64_t V_fine, int level, int64_t V_coarse,

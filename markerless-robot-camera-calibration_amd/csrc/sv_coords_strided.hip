@@ -1,6 +1,6 @@
-// Coordinate maps and kernel maps of STRIDED convolutions and pooling (kernel_size 3 or 1, any integer stride >= 2): what
-// ME.MinkowskiConvolution(kernel_size=3, stride=2 / 3) and the 1x1x1 stride-2 residual convs of model/backbone/resnet.py:48-127
-// ask of the coordinate manager.  The power-of-two stride maps and the four U-Net kernel maps stay in sv_coords.hip.
+// Coordinate maps of STRIDED convolutions and pooling at a tensor stride that is no power of two: what
+// ME.MinkowskiConvolution(kernel_size=3, stride=3) of model/backbone/resnet.py:48-127 asks of the coordinate manager.  The
+// power-of-two stride maps and every kernel map (sv_kernel_map_probe among them) are in sv_coords.hip.
 //
 // A general tensor stride does not keep the canonical (batch | Morton) order under coordinate flooring - clearing key bits
 // does, which is all sv_stride_map does - so sv_stride_map_general re-keys every voxel, sorts (sv_sort.hip) and uniques.
@@ -54,46 +54,6 @@ __global__ __launch_bounds__(256) void stride_general_scatter_kernel(const uint6
   }
 }
 
-// One thread per (query row, offset), blockIdx.y = k: kmap_k3_probe_kernel (sv_coords.hip) with the query rows and the hash
-// table belonging to two different maps, so the centre offset is a probe like any other.
-__global__ __launch_bounds__(256) void kmap_probe_kernel(const int32_t* __restrict__ vcoords_q, int64_t V_q, int ks, int step,
-                                                          const int32_t* __restrict__ vcoords_t, int64_t V_t,
-                                                          const uint64_t* __restrict__ tkeys,
-                                                          const int32_t* __restrict__ tvals, uint64_t cap_mask,
-                                                          int32_t* __restrict__ nbr, int64_t ld) {
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o >= V_q) return;
-  const int k = blockIdx.y;
-  int dx = 0, dy = 0, dz = 0;
-  if (ks == 3) {
-    dx = k % 3 - 1;
-    dy = (k / 3) % 3 - 1;
-    dz = k / 9 - 1;
-  }
-  const int4 c = ((const int4*)vcoords_q)[o];
-  const int x = c.y + dx * step, y = c.z + dy * step, z = c.w + dz * step;
-  int r = -1;
-  if (V_t > 0 && coord_in_range(c.x, x, y, z)) {  // outside the key range: make_key would wrap it onto the opposite face
-    const uint64_t key = make_key(c.x, x, y, z);
-    if (key != SV_EMPTY_KEY) {
-      r = hash_find(tkeys, tvals, cap_mask, key);
-    } else {  // the largest key there is: present iff it is the last row of the table's (key-sorted) map
-      const int4 l = ((const int4*)vcoords_t)[V_t - 1];
-      r = (l.x == c.x && l.y == x && l.z == y && l.w == z) ? (int)(V_t - 1) : -1;
-    }
-  }
-  nbr[(int64_t)k * ld + o] = r;
-}
-
-__global__ __launch_bounds__(256) void kmap_probe_mask_kernel(const int32_t* __restrict__ nbr, int64_t ld, int K, int64_t V,
-                                                               uint32_t* __restrict__ mask) {
-  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o >= V) return;
-  uint32_t m = 0;
-  for (int k = 0; k < K; ++k) m |= (nbr[(int64_t)k * ld + o] >= 0) ? (1u << k) : 0u;
-  mask[o] = m;
-}
-
 }  // namespace sv
 
 using namespace sv;
@@ -145,26 +105,6 @@ int sv_stride_map_general(const uint64_t* keys_in, int64_t V_in, int s_in, int s
   if (rc) return rc;
   hipLaunchKernelGGL(stride_general_scatter_kernel, dim3(nb), dim3(256), 0, stream, keys_in, s_out, k_sorted, i_sorted, rank,
                      V_in, keys_out, vcoords_out, parent);
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
-int sv_kernel_map_probe(const int32_t* vcoords_q, int64_t V_q, int kernel_size, int step, const int32_t* vcoords_t, int64_t V_t,
-                        const uint64_t* table_keys, const int32_t* table_vals, int64_t capacity, int32_t* nbr, int64_t ld,
-                        uint32_t* mask, sv_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SV_CHECK_ARG(kernel_size == 1 || kernel_size == 3, "kernel_size must be 1 or 3");
-  SV_CHECK_ARG(V_q >= 0 && V_t >= 0 && ld >= V_q, "bad shape (ld < V_q)");
-  SV_CHECK_ARG(step != 0 && step > -(1 << SV_COORD_BITS) && step < (1 << SV_COORD_BITS), "step out of range");
-  SV_CHECK_ARG(capacity >= 2 && (capacity & (capacity - 1)) == 0 && capacity >= 2 * V_t,
-               "capacity must be a power of two >= 2 * V_t");
-  if (V_q == 0) return SV_OK;
-  SV_CHECK_ARG(vcoords_q && table_keys && table_vals && nbr && mask && (vcoords_t || V_t == 0), "null pointer");
-  const int K = kernel_size * kernel_size * kernel_size;
-  const unsigned nb = (unsigned)((V_q + 255) / 256);
-  hipLaunchKernelGGL(kmap_probe_kernel, dim3(nb, K), dim3(256), 0, stream, vcoords_q, V_q, kernel_size, step, vcoords_t, V_t,
-                     table_keys, table_vals, (uint64_t)(capacity - 1), nbr, ld);
-  hipLaunchKernelGGL(kmap_probe_mask_kernel, dim3(nb), dim3(256), 0, stream, nbr, ld, K, V_q, mask);
   SV_LAUNCH_CHECK();
   return SV_OK;
 }

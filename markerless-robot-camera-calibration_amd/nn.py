@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib, profiling
 from ._lib import SV_ACT_LEAKY_RELU, SV_ACT_NONE, SV_ACT_RELU, call, ptr, stream_ptr
-from .sparse import SparseTensor, SplitPlan
+from .sparse import SparseTensor, SplitPlan, layer_maps
 
 # Adapting a checkpoint written by a MinkowskiEngine build whose kernel-offset numbering differs from this build's
 # (include/sv_hip.h: k = (dx+1) + 3 (dy+1) + 9 (dz+1), x fastest; k = dx + 2 dy + 4 dz for kernel_size 2):
@@ -323,11 +323,7 @@ def affine_act(feats, scale=None, shift=None, residual=None, act=SV_ACT_NONE, sl
 
 def global_pool(x, mode):
     cm = x.coordinate_manager
-    m = x.coordinate_map
-    B = cm.num_batches
-    if B is None:
-        B = int(m.coords[:, 0].max().item()) + 1 if m.V else 1
-        cm.num_batches = B
+    B = cm.batches()
     bs = cm.batch_offsets(x.tensor_stride, B)
     F = x.F
     C = F.shape[1]
@@ -340,11 +336,7 @@ def global_pool(x, mode):
 def global_pool_train(x, mode):
     """global_pool as differentiable torch segment reductions over the batch ranges (training): amax (NaN propagates, a
     tie shares the gradient) / mean; an empty batch gives 0 as the kernel does"""
-    cm = x.coordinate_manager
-    if cm.num_batches is None:
-        m = x.coordinate_map
-        cm.num_batches = int(m.coords[:, 0].max().item()) + 1 if m.V else 1
-    bounds = cm.batch_bounds(x.tensor_stride)
+    bounds = x.coordinate_manager.batch_bounds(x.tensor_stride)
     F = x.F
     rows = []
     for b in range(len(bounds) - 1):
@@ -512,50 +504,36 @@ class _ConvBase(_Bf16Weights, nn.Module):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                                       error_msgs)
 
-    def _plan(self, x):
+    def _maps(self, x, plan=None):
+        """(plan, output stride, thunk of the input-gradient plan, mirror) of this layer on x's map (sparse.layer_maps).
+        plan None: the forward plan is chosen here - a wide 3x3x3 layer on a big map runs as offset-range passes."""
         cm, ts = x.coordinate_manager, x.tensor_stride
-        ks, st = self.kernel_size, self.stride
-        if not self.transposed:
-            if ks == 1 and st == 1:
-                return None, ts
-            if ks == 3 and st == 1:
-                if self.dilation == 1 and self.in_channels >= SPLIT_MIN_CHANNELS and self.out_channels >= SPLIT_MIN_CHANNELS:
-                    cuts = cm.split_cuts_for(cm.stride_map(ts).V)  # the frame's own rules, else SPLIT_RULES
-                    if cuts is not None:
-                        if cm.split_ready is not None:
-                            # the offset-range plans were built on the prep stream while this stream ran the encoder
-                            torch.cuda.current_stream().wait_event(cm.split_ready)
-                            cm.split_ready = None
-                        return cm.plan_k3_split(ts, cuts), ts
-                return cm.plan_k3(ts, self.dilation), ts
-            if ks == 2 and st == 2:
-                return cm.plan_down(ts), ts * 2
-            if ks in (1, 3) and isinstance(st, int) and st >= 2:
-                # the strided convs of the classification ResNets (model/backbone/resnet.py:53,76,99-105)
-                return cm.plan_strided(ts, ks, st, self.dilation), ts * st
-        else:
-            if ks == 2 and st == 2:
-                return cm.plan_up(ts), ts // 2
-        raise NotImplementedError(
-            f"kernel_size={ks} stride={st} transposed={self.transposed}: not used by the reference's U-Nets")
+        maps = layer_maps(self.kernel_size, self.stride, self.dilation, self.transposed)
+        if (plan is None and maps.forward == ("k3", "in", 1) and self.in_channels >= SPLIT_MIN_CHANNELS
+                and self.out_channels >= SPLIT_MIN_CHANNELS):
+            cuts = cm.split_cuts_for(cm.stride_map(ts).V)  # the frame's own rules, else SPLIT_RULES
+            if cuts is not None:
+                if cm.split_ready is not None:
+                    # the offset-range plans were built on the prep stream while this stream ran the encoder
+                    torch.cuda.current_stream().wait_event(cm.split_ready)
+                    cm.split_ready = None
+                plan = cm.plan_k3_split(ts, cuts)
+        return cm.layer_plans(maps, ts, plan)
+
+    def _plan(self, x):
+        return self._maps(x)[:2]
 
     def _grad_plan(self, x, plan):
-        """plan of the input gradient (a forward conv from the output map back to the input map): the 3x3x3 map is its
-        own mirror, a down conv's is the up map of the coarse level, a transposed conv's the down map of the fine one"""
-        cm, ts = x.coordinate_manager, x.tensor_stride
-        if self.kernel_size == 2 and self.stride == 2:
-            return lambda: cm.plan_down(ts // 2) if self.transposed else cm.plan_up(ts * 2)
-        if not self.transposed and self.stride >= 2:  # strided k3 / k1: the transposed probe map, W[k]^T (mirror=False)
-            return lambda: cm.plan_strided_t(ts, self.kernel_size, self.stride, self.dilation)
-        return lambda: plan
+        """plan of the input gradient (a forward conv from the output map back to the input map) of a layer whose forward
+        ran on `plan`, as a thunk"""
+        return self._maps(x, plan)[2]
 
     def forward_train(self, x, bn=None, residual=None, act=SV_ACT_NONE, slope=0.01, cat_with=None):
         """forward_fused's graph as differentiable ops: the autograd conv, then BN (batch statistics in train(),
         running statistics in eval()), + residual, activation, ME.cat"""
-        plan, out_stride = self._plan(x)
+        plan, out_stride, grad_plan, mirror = self._maps(x)
         V_out = x.coordinate_manager.stride_map(out_stride).V
-        mirror = self.kernel_size == 3 and self.stride == 1
-        out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, self._grad_plan(x, plan), mirror, layer=self)
+        out = sparse_conv(x.F, self.weight3(), self.bias, plan, V_out, grad_plan, mirror, layer=self)
         if bn is not None:
             out = bn.bn(out)
         if residual is not None:
@@ -778,14 +756,8 @@ class _LocalPoolBase(nn.Module):
         self.kernel_size, self.stride, self.dilation, self.dimension = kernel_size, stride, dilation, dimension
 
     def _plans(self, x):
-        cm, ts = x.coordinate_manager, x.tensor_stride
-        ks, st, dil = self.kernel_size, self.stride, self.dilation
-        if ks == 2 and st == 2 and dil == 1:
-            return cm.plan_down(ts), ts * 2, lambda: cm.plan_up(ts * 2)
-        if ks in (1, 3) and isinstance(st, int) and st >= 1:
-            plan = cm.plan_k3(ts, dil) if (ks, st) == (3, 1) else cm.plan_strided(ts, ks, st, dil)
-            return plan, ts * st, lambda: cm.plan_strided_t(ts, ks, st, dil)
-        raise NotImplementedError(f"pooling kernel_size={ks} stride={st} dilation={dil}: no kernel map of that shape")
+        maps = layer_maps(self.kernel_size, self.stride, self.dilation, pooling=True)
+        return x.coordinate_manager.layer_plans(maps, x.tensor_stride)[:3]
 
     def forward(self, x):
         plan, out_stride, t_plan = self._plans(x)
@@ -810,10 +782,7 @@ class MinkowskiSumPooling(_LocalPoolBase):
 def _frame_offsets(x):
     """(batch_start int32[B + 1] on the device, B) of a sparse tensor's map"""
     cm = x.coordinate_manager
-    if cm.num_batches is None:
-        m1 = cm.stride_map(1)
-        cm.num_batches = int(m1.coords[:, 0].max().item()) + 1 if m1.V else 1
-    return cm.batch_offsets(x.tensor_stride, cm.num_batches), cm.num_batches
+    return cm.batch_offsets(x.tensor_stride, cm.batches()), cm.batches()
 
 
 class InstanceNormFunction(torch.autograd.Function):

@@ -12,6 +12,7 @@ import threading
 import weakref
 from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 from enum import Enum
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -160,6 +161,54 @@ class SplitPlan:
         return self.whole.num_pairs()
 
 
+class LayerMaps(NamedTuple):
+    """The kernel maps of one layer shape (layer_maps).  A map is (name, at, *args): CoordinateManager.plan_<name>(stride,
+    *args) with stride = the layer's input ("in") or output ("out") tensor stride; None = dense rows, no plan."""
+    forward: Optional[tuple]
+    out_stride: tuple  # (mul, div): the output's tensor stride is ts * mul // div
+    backward: Optional[tuple]  # conv input gradient / pooling backward; SAME_PLAN = the forward plan itself
+    mirror: bool  # the input gradient runs on the offset-mirrored weights W[26 - k]^T (else W[k]^T)
+
+
+SAME_PLAN = ("forward",)
+
+
+def layer_maps(kernel_size, stride, dilation=1, transposed=False, pooling=False):
+    """THE table from a layer's shape to its kernel maps - which map a convolution (or, pooling=True, a local pooling)
+    runs on, its output stride, and the map of its backward pass:
+
+      conv k1 s1                         dense rows         ts        the same        W^T
+      conv k3 s1, any dilation           k3                 ts        the same plan   mirrored
+      k2 s2 (pooling: dilation 1)        down               ts * 2    up of ts * 2
+      conv k2 s2 transposed              up                 ts // 2   down of ts // 2
+      k in {1, 3}, integer s >= 2        strided            ts * s    strided_t
+      pooling k3 s1 / k1 s1              k3 / strided       ts        strided_t
+
+    Pure: no tensors, no GPU.  Any other shape raises NotImplementedError."""
+    ks, st, dil = kernel_size, stride, dilation
+    strided = ks in (1, 3) and isinstance(st, int)
+    if pooling:
+        if ks == 2 and st == 2 and dil == 1:
+            return LayerMaps(("down", "in"), (2, 1), ("up", "out"), False)
+        if strided and st >= 1:
+            fwd = ("k3", "in", dil) if (ks, st) == (3, 1) else ("strided", "in", ks, st, dil)
+            return LayerMaps(fwd, (st, 1), ("strided_t", "in", ks, st, dil), False)
+        raise NotImplementedError(f"pooling kernel_size={ks} stride={st} dilation={dil}: no kernel map of that shape")
+    if transposed:
+        if ks == 2 and st == 2:
+            return LayerMaps(("up", "in"), (1, 2), ("down", "out"), False)
+    elif ks == 1 and st == 1:
+        return LayerMaps(None, (1, 1), SAME_PLAN, False)
+    elif ks == 3 and st == 1:
+        return LayerMaps(("k3", "in", dil), (1, 1), SAME_PLAN, True)
+    elif ks == 2 and st == 2:
+        return LayerMaps(("down", "in"), (2, 1), ("up", "out"), False)
+    elif strided and st >= 2:  # the strided convs of the classification ResNets (model/backbone/resnet.py:53,76,99-105)
+        return LayerMaps(("strided", "in", ks, st, dil), (st, 1), ("strided_t", "in", ks, st, dil), False)
+    raise NotImplementedError(
+        f"kernel_size={ks} stride={st} transposed={transposed}: not used by the reference's U-Nets")
+
+
 class CoordinateManager:
     def __init__(self, device):
         self.device = device
@@ -190,22 +239,9 @@ class CoordinateManager:
         if stride <= 1:
             raise _lib.SvHipError(f"no coordinate map at tensor stride {stride}")
         fine = self.stride_map(stride // 2)
-        level = (stride // 2).bit_length() - 1
-        dev = self.device
-        V_in = fine.V
-        ws_bytes = _lib.load().sv_stride_map_workspace_bytes(c_int64(V_in))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        keys = torch.empty(max(V_in, 1), dtype=torch.int64, device=dev)
-        coords = torch.empty((max(V_in, 1), 4), dtype=torch.int32, device=dev)
-        parent = torch.empty(max(V_in, 1), dtype=torch.int32, device=dev)
-        child_start = torch.empty(V_in + 1, dtype=torch.int32, device=dev)
-        counters = torch.empty(4, dtype=torch.int32, device=dev)
-        call("sv_stride_map", ptr(fine.keys), c_int64(V_in), c_int(level), ptr(ws), c_size_t(ws_bytes), ptr(keys),
-             ptr(coords), ptr(parent), ptr(child_start), ptr(counters), stream_ptr())
-        V = int(counters[0].item())
-        m = CoordinateMap(keys[:V], coords[:V], V, stride)
-        self.maps[stride] = m
-        self.parents[stride // 2] = (parent[:V_in], child_start[: V + 1])
+        child_start = torch.empty(fine.V + 1, dtype=torch.int32, device=self.device)
+        m, parent = self._derive_map(fine, stride, "sv_stride_map", ((stride // 2).bit_length() - 1,), (child_start,))
+        self.parents[stride // 2] = (parent, child_start[: m.V + 1])
         return m
 
     def _stride_map_general(self, stride):
@@ -213,35 +249,45 @@ class CoordinateManager:
         if not divisors:
             raise _lib.SvHipError(f"no coordinate map at tensor stride {stride}: no existing map's stride divides it")
         fine = self.maps[max(divisors)]
-        dev, V_in = self.device, fine.V
-        ws_bytes = _lib.load().sv_stride_map_general_workspace_bytes(c_int64(V_in))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        keys = torch.empty(max(V_in, 1), dtype=torch.int64, device=dev)
-        coords = torch.empty((max(V_in, 1), 4), dtype=torch.int32, device=dev)
-        parent = torch.empty(max(V_in, 1), dtype=torch.int32, device=dev)
-        counters = torch.empty(4, dtype=torch.int32, device=dev)
-        call("sv_stride_map_general", ptr(fine.keys), c_int64(V_in), c_int(fine.stride), c_int(stride), ptr(ws),
-             c_size_t(ws_bytes), ptr(keys), ptr(coords), ptr(parent), ptr(counters), stream_ptr())
-        V, bad = counters.tolist()[:2]
-        if bad:
-            raise _lib.SvHipError(f"{bad} voxels leave the key range at tensor stride {stride} "
-                                  f"(floor(c / {stride}) * {stride} < -2^17)")
-        m = CoordinateMap(keys[:V], coords[:V], V, stride)
-        self.maps[stride] = m
-        self.general_parents[(fine.stride, stride)] = parent[:V_in]
+        bad = lambda n: _lib.SvHipError(f"{n} voxels leave the key range at tensor stride {stride} "  # noqa: E731
+                                        f"(floor(c / {stride}) * {stride} < -2^17)")
+        m, parent = self._derive_map(fine, stride, "sv_stride_map_general", (fine.stride, stride), bad=bad)
+        self.general_parents[(fine.stride, stride)] = parent
         return m
 
+    def _derive_map(self, fine, stride, fn, ints, more=(), bad=None):
+        """The map at `stride` from `fine` by fn = sv_stride_map (ints: level; more: child_start) or sv_stride_map_general
+        (ints: s_in, s_out; bad: the error for its count of voxels that leave the key range): workspace and outputs, the
+        call, the size read-back, and the map registered.  Returns (map, parent int32[fine.V])."""
+        dev, n = self.device, max(fine.V, 1)
+        ws_bytes = getattr(_lib.load(), fn + "_workspace_bytes")(c_int64(fine.V))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        parent = torch.empty(n, dtype=torch.int32, device=dev)
+        counters = torch.empty(4, dtype=torch.int32, device=dev)
+        call(fn, ptr(fine.keys), c_int64(fine.V), *map(c_int, ints), ptr(ws), c_size_t(ws_bytes),
+             *map(ptr, (keys, coords, parent, *more, counters)), stream_ptr())
+        V, n_bad = counters.tolist()[:2]
+        if bad is not None and n_bad:
+            raise bad(n_bad)
+        m = self.maps[stride] = CoordinateMap(keys[:V], coords[:V], V, stride)
+        return m, parent[:fine.V]
+
     # ---- plans -----------------------------------------------------------------------------
+    def batches(self):
+        """number of batch indices (largest + 1; 1 for an empty map): num_batches where the caller set it (app/pipeline.py
+        knows its group size), else one read-back from the stride-1 map, cached"""
+        if self.num_batches is None:
+            m1 = self.stride_map(1)
+            self.num_batches = int(m1.coords[:, 0].max().item()) + 1 if m1.V else 1
+        return self.num_batches
+
     def batch_bounds(self, stride):
         """host copy of the first row of every batch at tensor stride `stride` ([B + 1] python ints; one read-back per
         level, cached) - the ranges batched launches are split at (ConvPlan.chunks)"""
         if stride not in self._batch_bounds:
-            B = self.num_batches
-            if B is None:
-                m1 = self.stride_map(1)
-                B = int(m1.coords[:, 0].max().item()) + 1 if m1.V else 1
-                self.num_batches = B
-            self._batch_bounds[stride] = self.batch_offsets(stride, B).tolist()
+            self._batch_bounds[stride] = self.batch_offsets(stride, self.batches()).tolist()
         return self._batch_bounds[stride]
 
     def _build_plan(self, nbr, ld, mask, K, V_out, nbr_base=0):
@@ -258,18 +304,26 @@ class CoordinateManager:
              ptr(perm), ptr(nbr_s), ptr(submask), ptr(tile_order), c_int64(Vpad), stream_ptr())
         return ConvPlan(perm, nbr_s, submask, tile_order, V_out, Vpad, K)
 
-    def plan_k3(self, stride, dilation=1):
-        key = ("k3", stride, dilation)
+    def _kmap_plan(self, key, K, V_out, in_stride, out_stride, fill):
+        """The plan of a whole kernel map, cached under `key`: fill(nbr int32[K, ld], ld, mask int32[ld]) is the
+        sv_kernel_map_* call that writes the table of the V_out output rows (ld = max(V_out, 1))."""
         if key not in self.plans:
-            m = self.stride_map(stride)
-            tkeys, tvals, cap = m.hash()
-            V = m.V
-            nbr = torch.empty((27, max(V, 1)), dtype=torch.int32, device=self.device)
-            mask = torch.empty(max(V, 1), dtype=torch.int32, device=self.device)
-            call("sv_kernel_map_k3", ptr(m.coords), c_int64(V), c_int(stride), c_int(dilation), ptr(tkeys), ptr(tvals),
-                 c_int64(cap), ptr(nbr), c_int64(max(V, 1)), ptr(mask), stream_ptr())
-            self.plans[key] = self._own(self._build_plan(nbr, max(V, 1), mask, 27, V), nbr, max(V, 1), mask, stride, stride)
+            ld = max(V_out, 1)
+            nbr = torch.empty((K, ld), dtype=torch.int32, device=self.device)
+            mask = torch.empty(ld, dtype=torch.int32, device=self.device)
+            fill(nbr, ld, mask)
+            self.plans[key] = self._own(self._build_plan(nbr, ld, mask, K, V_out), nbr, ld, mask, in_stride, out_stride)
         return self.plans[key]
+
+    def plan_k3(self, stride, dilation=1):
+        m = self.stride_map(stride)
+
+        def fill(nbr, ld, mask):
+            tkeys, tvals, cap = m.hash()
+            call("sv_kernel_map_k3", ptr(m.coords), c_int64(m.V), c_int(stride), c_int(dilation), ptr(tkeys), ptr(tvals),
+                 c_int64(cap), ptr(nbr), c_int64(ld), ptr(mask), stream_ptr())
+
+        return self._kmap_plan(("k3", stride, dilation), 27, m.V, stride, stride, fill)
 
     def plan_k3_split(self, stride, split=14):
         """The 3x3x3 map of `stride` as passes over ascending offset ranges (SplitPlan): split = 14 -> [0, 14) and [14, 27)
@@ -291,71 +345,67 @@ class CoordinateManager:
 
     def plan_down(self, stride):
         """kernel_size 2, stride 2 convolution from tensor stride `stride` to 2*stride."""
-        key = ("down", stride)
-        if key not in self.plans:
-            fine = self.stride_map(stride)
-            coarse = self.stride_map(stride * 2)
-            parent, _ = self.parents[stride]
-            level = stride.bit_length() - 1
-            Vc = coarse.V
-            nbr = torch.empty((8, max(Vc, 1)), dtype=torch.int32, device=self.device)
-            mask = torch.empty(max(Vc, 1), dtype=torch.int32, device=self.device)
-            call("sv_kernel_map_down", ptr(fine.keys), ptr(parent), c_int64(fine.V), c_int(level), c_int64(Vc),
-                 ptr(nbr), c_int64(max(Vc, 1)), ptr(mask), stream_ptr())
-            self.plans[key] = self._own(self._build_plan(nbr, max(Vc, 1), mask, 8, Vc), nbr, max(Vc, 1), mask, stride,
-                                        stride * 2)
-        return self.plans[key]
+        fine, coarse = self.stride_map(stride), self.stride_map(stride * 2)
+
+        def fill(nbr, ld, mask):
+            call("sv_kernel_map_down", ptr(fine.keys), ptr(self.parents[stride][0]), c_int64(fine.V),
+                 c_int(stride.bit_length() - 1), c_int64(coarse.V), ptr(nbr), c_int64(ld), ptr(mask), stream_ptr())
+
+        return self._kmap_plan(("down", stride), 8, coarse.V, stride, stride * 2, fill)
 
     def plan_up(self, stride):
         """transposed kernel_size 2, stride 2 convolution from tensor stride `stride` to stride/2 (existing map)."""
-        key = ("up", stride)
-        if key not in self.plans:
-            fs = stride // 2
-            if fs not in self.maps or fs not in self.parents:
-                raise _lib.SvHipError(
-                    f"transposed conv to tensor stride {fs}: that coordinate map does not exist "
-                    "(ME semantics: the output reuses the encoder's map, model/backbone/minkunet.py:152-156)")
-            fine = self.maps[fs]
-            parent, _ = self.parents[fs]
-            level = fs.bit_length() - 1
-            V = fine.V
-            nbr = torch.empty((8, max(V, 1)), dtype=torch.int32, device=self.device)
-            mask = torch.empty(max(V, 1), dtype=torch.int32, device=self.device)
-            call("sv_kernel_map_up", ptr(fine.keys), ptr(parent), c_int64(V), c_int(level), ptr(nbr),
-                 c_int64(max(V, 1)), ptr(mask), stream_ptr())
-            self.plans[key] = self._own(self._build_plan(nbr, max(V, 1), mask, 8, V), nbr, max(V, 1), mask, stride, fs)
-        return self.plans[key]
+        fs = stride // 2
+        if fs not in self.maps or fs not in self.parents:
+            raise _lib.SvHipError(
+                f"transposed conv to tensor stride {fs}: that coordinate map does not exist "
+                "(ME semantics: the output reuses the encoder's map, model/backbone/minkunet.py:152-156)")
+        fine = self.maps[fs]
 
-    def _plan_probe(self, key, q_stride, t_stride, kernel_size, step):
-        """kernel map between two maps (sv_kernel_map_probe): output rows = the map at q_stride, inputs from t_stride"""
-        if key not in self.plans:
-            q, t = self.stride_map(q_stride), self.stride_map(t_stride)
+        def fill(nbr, ld, mask):
+            call("sv_kernel_map_up", ptr(fine.keys), ptr(self.parents[fs][0]), c_int64(fine.V), c_int(fs.bit_length() - 1),
+                 ptr(nbr), c_int64(ld), ptr(mask), stream_ptr())
+
+        return self._kmap_plan(("up", stride), 8, fine.V, stride, fs, fill)
+
+    def _plan_probe(self, name, in_stride, kernel_size, stride, dilation):
+        """kernel map between the maps at in_stride and in_stride * stride (sv_kernel_map_probe): the rows of one probe the
+        table of the other, at +in_stride * dilation for the layer's own map, minus that for its transpose"""
+        if kernel_size not in (1, 3) or stride < 1 or dilation < 1:
+            raise _lib.SvHipError(f"plan_{name}: kernel_size {kernel_size} stride {stride} dilation {dilation}")
+        t = self.stride_map(in_stride)  # the input map first: the output map is derived from the existing ones
+        q, step = self.stride_map(in_stride * stride), in_stride * dilation
+        if name == "strided_t":
+            q, t, step = t, q, -step
+
+        def fill(nbr, ld, mask):
             tkeys, tvals, cap = t.hash()
-            K, ld = kernel_size ** 3, max(q.V, 1)
-            nbr = torch.empty((K, ld), dtype=torch.int32, device=self.device)
-            mask = torch.empty(ld, dtype=torch.int32, device=self.device)
             call("sv_kernel_map_probe", ptr(q.coords), c_int64(q.V), c_int(kernel_size), c_int(step), ptr(t.coords),
                  c_int64(t.V), ptr(tkeys), ptr(tvals), c_int64(cap), ptr(nbr), c_int64(ld), ptr(mask), stream_ptr())
-            self.plans[key] = self._own(self._build_plan(nbr, ld, mask, K, q.V), nbr, ld, mask, t_stride, q_stride)
-        return self.plans[key]
+
+        return self._kmap_plan((name, in_stride, kernel_size, stride, dilation), kernel_size ** 3, q.V, t.stride, q.stride, fill)
 
     def plan_strided(self, in_stride, kernel_size, stride, dilation=1):
         """kernel_size 3 or 1 convolution (or pooling) of stride `stride` from tensor stride in_stride to in_stride * stride:
         the output map's rows probe the input map's table at +in_stride * dilation (the kernel is centred on the output)."""
-        if kernel_size not in (1, 3) or stride < 1 or dilation < 1:
-            raise _lib.SvHipError(f"plan_strided: kernel_size {kernel_size} stride {stride} dilation {dilation}")
-        self.stride_map(in_stride)  # the input map first: the output map is derived from the existing ones
-        return self._plan_probe(("strided", in_stride, kernel_size, stride, dilation), in_stride * stride, in_stride,
-                                kernel_size, in_stride * dilation)
+        return self._plan_probe("strided", in_stride, kernel_size, stride, dilation)
 
     def plan_strided_t(self, in_stride, kernel_size, stride, dilation=1):
         """the transpose of plan_strided's map (input gradient of the conv, backward of the pooling): the input map's rows
         probe the output map's table at -in_stride * dilation; nbr[k][o] = i there exactly when nbr_t[k][i] = o here."""
-        if kernel_size not in (1, 3) or stride < 1 or dilation < 1:
-            raise _lib.SvHipError(f"plan_strided_t: kernel_size {kernel_size} stride {stride} dilation {dilation}")
-        self.stride_map(in_stride)
-        return self._plan_probe(("strided_t", in_stride, kernel_size, stride, dilation), in_stride, in_stride * stride,
-                                kernel_size, -in_stride * dilation)
+        return self._plan_probe("strided_t", in_stride, kernel_size, stride, dilation)
+
+    def layer_plans(self, maps, ts, plan=None):
+        """A row of layer_maps applied at tensor stride ts: (forward plan, output stride, thunk of the backward plan,
+        mirror).  plan: what the caller runs in place of the row's forward map (the offset-range split of a 3x3x3 layer);
+        the backward plan is built when the thunk is called."""
+        mul, div = maps.out_stride
+        at = {"in": ts, "out": ts * mul // div}
+        build = lambda name, where, *args: getattr(self, "plan_" + name)(at[where], *args)  # noqa: E731
+        if plan is None and maps.forward is not None:
+            plan = build(*maps.forward)
+        backward = (lambda: plan) if maps.backward == SAME_PLAN else (lambda: build(*maps.backward))
+        return plan, at["out"], backward, maps.mirror
 
     # ---- frame composites (sv_frame_plans): everything a U-Net asks for in one or two host calls ------------
     def split_cuts_for(self, rows):
@@ -663,19 +713,19 @@ class SparseTensor:
     def __len__(self):
         return self._F.shape[0]
 
+    def _decomposed_bounds(self):
+        """first row of every batch on this tensor's map ([B + 1] python ints); an empty tensor has no batch at all"""
+        return self.coordinate_manager.batch_bounds(self.tensor_stride) if self.coordinate_map.V else [0]
+
     @property
     def decomposed_coordinates(self):
-        m = self.coordinate_map
-        B = int(m.coords[:, 0].max().item()) + 1 if m.V else 0
-        bs = self.coordinate_manager.batch_offsets(self.tensor_stride, max(B, 1)).tolist()
-        return [m.coords[bs[b]: bs[b + 1], 1:] for b in range(B)]
+        m, bs = self.coordinate_map, self._decomposed_bounds()
+        return [m.coords[bs[b]: bs[b + 1], 1:] for b in range(len(bs) - 1)]
 
     @property
     def decomposed_features(self):
-        m = self.coordinate_map
-        B = int(m.coords[:, 0].max().item()) + 1 if m.V else 0
-        bs = self.coordinate_manager.batch_offsets(self.tensor_stride, max(B, 1)).tolist()
-        return [self._F[bs[b]: bs[b + 1]] for b in range(B)]
+        bs = self._decomposed_bounds()
+        return [self._F[bs[b]: bs[b + 1]] for b in range(len(bs) - 1)]
 
     def new(self, features, tensor_stride=None):
         return SparseTensor(features, coordinate_manager=self.coordinate_manager,

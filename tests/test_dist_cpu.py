@@ -108,10 +108,13 @@ def test_strong_scaling_mode_partitions_a_fixed_job():
         assert len(out["per_rank"]["pinned_cores"]) == world and min(out["per_rank"]["pinned_cores"]) >= 1
 
 
-def test_rank_pinning_from_sysfs_topology(tmp_path):
+def test_rank_pinning_from_sysfs_topology(tmp_path, monkeypatch):
     """Ranks are pinned to their GPU's NUMA node before any GPU call (app/sharding.py pin_rank): fake sysfs with 4 GPUs on
     2 nodes (render nodes in minor order = device order), a non-AMD render node in between, and the no-information case."""
     from mrcc_amd.app import sharding
+
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):  # pin_rank reads them: the fake topology must not meet a
+        monkeypatch.delenv(var, raising=False)                   # device list of the machine the suite runs on
 
     def mk(minor, vendor, numa):
         d = tmp_path / "class" / "drm" / f"renderD{minor}" / "device"

@@ -31,15 +31,7 @@ def maps(gpu):
     return out
 
 
-def _features(rng, V, C, ties):
-    if ties:  # few distinct values: every window has ties; NaNs in a few places, one whole NaN row
-        x = rng.integers(-2, 3, size=(V, C)).astype(np.float32)
-        x[rng.integers(0, V, size=12), rng.integers(0, C, size=12)] = np.nan
-        x[V // 2] = np.nan
-        x[3, 0], x[4, 0] = np.inf, -np.inf
-    else:
-        x = rng.standard_normal((V, C)).astype(np.float32)
-    return x
+_features = H.pool_features
 
 
 @pytest.mark.parametrize("C", [1, 3, 64, 65])
@@ -110,18 +102,7 @@ def test_pool_backward(gpu, maps, table, C):
         if mode != AVG:
             assert np.array_equal(got[single].astype(np.float64), want[single])
         # and exactly the defined order in float32: ascending k over the transposed table
-        acc = np.zeros((maps["V_in"], C), np.float32)
-        count = (nbr_np >= 0).sum(0).astype(np.float32)
-        rows = np.arange(maps["V_in"])[:, None]
-        for k in range(nbr_t_np.shape[0]):
-            o = nbr_t_np[k]
-            oc = np.maximum(o, 0)
-            g = dy[oc]
-            if mode == MAX:
-                g = np.where(arg.cpu().numpy()[oc] == rows, g, np.float32(0))
-            elif mode == AVG:
-                g = (g / count[oc][:, None]).astype(np.float32)
-            acc = (acc + np.where((o >= 0)[:, None], g, np.float32(0))).astype(np.float32)
+        acc = H.pool_backward32_ref(dy, nbr_t_np, mode, arg.cpu().numpy() if arg is not None else None, (nbr_np >= 0).sum(0))
         assert np.array_equal(got, acc)
 
 

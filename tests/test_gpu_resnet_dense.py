@@ -374,3 +374,56 @@ def test_strided_conv_on_a_batch_equals_per_frame_results(gpu):
         one = run(np.concatenate([np.zeros((len(f), 1), np.int64), f], 1), ft)
         assert torch.equal(one.C[:, 1:], both.C[bounds[b]:bounds[b + 1], 1:])
         assert torch.equal(one.F, both.F[bounds[b]:bounds[b + 1]])
+
+
+def _three_frames():
+    """three frames of different sizes; the last is so small (a dozen voxels inside one stride-192 cell whose neighbours along
+    the negative axes are empty) that its stride-192 map has exactly one voxel"""
+    rng = np.random.default_rng(21)
+    big = H.blob_cloud(rng, 2600, [(-98, -160, -95), (24, -150, 20), (30, 40, -60)], 9.0, (-128, -192, -128), (80, 64, 64))
+    mid = H.blob_cloud(rng, 1100, [(-40, 10, 0), (60, -30, 20)], 9.0, (-100,) * 3, (100,) * 3)
+    tiny = H.blob_cloud(rng, 12, [(70, 75, 80)], 3.0, (64,) * 3, (96,) * 3)
+    frames = [big, mid, tiny]
+    feats = [rng.standard_normal((len(f), 3)).astype(np.float32) for f in frames]
+    return frames, feats
+
+
+@pytest.mark.parametrize("bottleneck", [False, True], ids=["BasicBlock", "Bottleneck"])
+def test_resnet_batched_logits_are_the_per_frame_bits(gpu, bottleneck):
+    """eval(): every operator depends on a frame's own rows only (the instance-norm tree is cut relative to the frame's first
+    row, every conv element is one fma chain whatever the instance or tile), so row b of the batched
+    logits has the bits of frame b run alone"""
+    import torch
+
+    frames, feats = _three_frames()
+    model = _model(bottleneck, gpu).eval()
+
+    def run(fs, ft):
+        pts = np.concatenate([np.concatenate([np.full((len(f), 1), b), f], 1) for b, f in enumerate(fs)]).astype(np.int32)
+        x = _sparse_input(pts, np.concatenate(ft), gpu)
+        with torch.no_grad():
+            return model(x), x.coordinate_manager
+
+    both, cm = run(frames, feats)
+    bounds = cm.batch_bounds(192)
+    assert len(bounds) == 4 and bounds[3] - bounds[2] == 1 and bounds[1] - bounds[0] > 1 and bounds[2] - bounds[1] > 1
+    assert both.shape == (3, 5) and torch.isfinite(both).all()
+    for b in range(3):
+        one, _ = run(frames[b:b + 1], feats[b:b + 1])
+        assert torch.equal(one[0], both[b]), (b, one[0].tolist(), both[b].tolist())
+
+
+@pytest.mark.parametrize("bottleneck", [False, True], ids=["BasicBlock", "Bottleneck"])
+def test_fused_instance_norm_relu_equals_the_plain_sequence(gpu, bottleneck):
+    """ResNetBase._run fuses InstanceNorm -> ReLU into one call that applies ReLU in float64 before the one rounding; rounding is
+    monotone and keeps 0, so relu(round(v)) == round(relu(v)) and the stem run as a plain nn.Sequential gives the same bits"""
+    import torch
+
+    frames, feats = _three_frames()
+    model = _model(bottleneck, gpu).eval()
+    pts = np.concatenate([np.concatenate([np.full((len(f), 1), b), f], 1) for b, f in enumerate(frames)]).astype(np.int32)
+    with torch.no_grad():
+        fused = model._run(model.conv1, _sparse_input(pts, np.concatenate(feats), gpu))
+        plain = model.conv1(_sparse_input(pts, np.concatenate(feats), gpu))
+    assert fused.tensor_stride == plain.tensor_stride == 4 and torch.equal(fused.C, plain.C)
+    assert torch.equal(fused.F, plain.F) and (fused.F == 0).any() and (fused.F > 0).any()

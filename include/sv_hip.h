@@ -51,6 +51,7 @@ extern "C" {
 
 #define SV_REDUCE_MEAN 0  /* ME.SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE */
 #define SV_REDUCE_FIRST 1 /* ME.utils.sparse_quantize: lowest original index represents the voxel */
+#define SV_REDUCE_SUM 2   /* ME.SparseTensorQuantizationMode.UNWEIGHTED_SUM; the backward of slicing */
 
 #define SV_TILE_ROWS 128 /* output rows per conv tile; plans are padded to a multiple of this */
 #define SV_COORD_BIAS 131072 /* 2^17 */
@@ -68,7 +69,7 @@ const char* sv_last_error(void);
  *    sv_key_point_predictions_batched; later additions that leave every earlier signature as it was: sv_conv_wgrad,
  *    sv_conv_wgrad_bf16, the PointNet++ training entries of A9, the pose losses of N4, the augmentation entries of N5, the label
  *    entries of N6, the segmentation criterion and step metrics of N7, the packed-record ingest of N3e, the RGB-D ingest of N3f
- *    and its lens models of N3g */
+ *    and its lens models of N3g, the field front end of N9 (sv_sinusoidal, sv_field_stage, SV_REDUCE_SUM) */
 #define SV_ABI_VERSION 4
 int sv_abi_version(void);
 
@@ -95,9 +96,10 @@ int sv_voxelize(const void* coords4, int coords_are_int, int64_t N, void* worksp
                 uint64_t* keys, int32_t* vcoords, int64_t* inverse, int32_t* order, int32_t* seg_start,
                 int32_t* counters, sv_stream_t stream);
 
-/* per-voxel feature reduction: out[v][c] = mean (or first) of feats[order[j]][c], j in the voxel's segment,
- * summed sequentially in ascending original point index (deterministic).  IEEE sums: a NaN feature makes its voxel's
- * mean NaN, +inf and -inf together give NaN.  Segments are never empty (sv_voxelize's seg_start). */
+/* per-voxel feature reduction: out[v][c] = mean (or first, or sum) of feats[order[j]][c], j in the voxel's segment,
+ * summed sequentially in ascending original point index (deterministic); SV_REDUCE_SUM is that sum without the division.
+ * IEEE sums: a NaN feature makes its voxel's mean NaN, +inf and -inf together give NaN.  Segments are never empty
+ * (sv_voxelize's seg_start). */
 int sv_voxel_reduce(const float* feats, int C, const int32_t* order, const int32_t* seg_start, int64_t V, int mode,
                     float* out, sv_stream_t stream);
 
@@ -1185,6 +1187,39 @@ int sv_instance_norm_backward(const float* x, int64_t V, int64_t ld, int C, cons
                               const float* bias, const double* mean, const double* inv_std, int act, const float* dy,
                               int64_t dy_ld, void* workspace, size_t workspace_bytes, float* dx, int64_t dx_ld, float* dweight,
                               float* dbias, sv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N9  field front end of the ResFieldNets (reference model/backbone/resnet.py:165-193): layers that run on the POINTS of a
+ * TensorField before voxelisation.  Semantics of ME 0.5.4 restated from memory (unverified).
+ *
+ * sv_sinusoidal - ME.MinkowskiSinusoidal:  out[p][n] = coef[n] * sin(sum_k x[p][k] kernel[k][n] + bias[n])
+ *   x: [N] rows of Cin floats, row stride ld >= Cin; kernel [Cin][Cout]; bias, coef [Cout]; out row stride out_ld >= Cout
+ *   (column views are fine on both sides).  Any Cin, Cout >= 1; N = 0 is valid.
+ *   Order: a = 0; a = fmaf(x[p][k], kernel[k][n], a) for k ascending; a = a + bias[n]  (all fp32).  The sine is evaluated in
+ *   float64 on that fp32 argument (full-range argument reduction) and rounded once to fp32; one more rounding for the
+ *   product with coef.  NaN or +-inf in a row give NaN in that row only.  Same bits on every call.
+ *
+ * sv_field_stage - the eval() form of one field network in one launch:
+ *     Sinusoidal -> BN -> ReLU -> Linear -> BN -> ReLU -> per-voxel mean            (the [N, C] intermediates stay on chip)
+ *   input row of point p: [G[inverse[p]][0..Cg), F[p][0..Cf)]  (SparseTensor.cat_slice's order); Cg = 0 with G = inverse =
+ *   NULL is a network on the field alone.  F row stride f_ld >= Cf, G row stride g_ld >= Cg, out [V] rows of C, out_ld >= C.
+ *   kernel [Cg + Cf][C], bias / coef [C]: the sinusoidal layer, computed exactly as sv_sinusoidal does.
+ *   scale1 / shift1, scale2 / shift2 [C]: the folded batch norms, y = fmaf(x, scale, shift).  relu(v) = v < 0 ? 0 : v.
+ *   W [C][C] (W[c][n], input channel first: MinkowskiLinear.weight3()), lin_bias [C] or NULL:
+ *     b = 0; b = fmaf(h[c], W[c][n], b) for c ascending; b = b + lin_bias[n].
+ *   order / seg_start / V: sv_voxelize's.  out[v][n] = the sequential fp32 sum over the voxel's points in ascending
+ *   original index, then ONE division by the voxel's count (sv_voxel_reduce's rule): a voxel's row does not depend on
+ *   the other voxels of the call nor on the kernel's tiles (a voxel longer than a tile is carried by one workgroup, in order).
+ *   A NaN point makes exactly its voxel's row NaN.  No float atomics; same bits on every call.
+ *   C in {32, 64} and Cg + Cf <= 128, else SV_ERR_UNSUPPORTED before anything is launched (the caller runs the layers one by
+ *   one).  N = 0 with V = 0 is valid.
+ * ------------------------------------------------------------------------------------------- */
+int sv_sinusoidal(const float* x, int64_t ld, int Cin, int64_t N, const float* kernel, const float* bias, const float* coef,
+                  int Cout, float* out, int64_t out_ld, sv_stream_t stream);
+int sv_field_stage(const float* F, int64_t f_ld, int Cf, int64_t N, const float* G, int64_t g_ld, int Cg, const int64_t* inverse,
+                   const float* kernel, const float* bias, const float* coef, const float* scale1, const float* shift1,
+                   const float* W, const float* lin_bias, const float* scale2, const float* shift2, int C,
+                   const int32_t* order, const int32_t* seg_start, int64_t V, float* out, int64_t out_ld, sv_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ name so reference-shaped model files import unchanged; the build's own model mir
 from ..nn import (BasicBlock, Bottleneck, MinkowskiAvgPooling, MinkowskiBatchNorm, MinkowskiConvolution,
                   MinkowskiConvolutionTranspose, MinkowskiDropout, MinkowskiGELU, MinkowskiGlobalAvgPooling,
                   MinkowskiGlobalMaxPooling, MinkowskiInstanceNorm, MinkowskiLeakyReLU, MinkowskiLinear, MinkowskiMaxPooling,
-                  MinkowskiReLU, MinkowskiSigmoid, MinkowskiSumPooling)
+                  MinkowskiReLU, MinkowskiSigmoid, MinkowskiSinusoidal, MinkowskiSumPooling, MinkowskiToSparseTensor)
 from ..sparse import (CoordinateManager, MinkowskiAlgorithm, SparseTensor, SparseTensorQuantizationMode, TensorField,
                       cat)
 from . import MinkowskiOps, modules, utils  # noqa: F401

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SVHIP_LIB") or os.path.join(_HERE, "libsvhip.so")  # 
 SV_ACT_NONE, SV_ACT_RELU, SV_ACT_LEAKY_RELU, SV_ACT_GELU = 0, 1, 2, 3
 SV_POOL_MAX, SV_POOL_AVG, SV_POOL_SUM = 0, 1, 2
 SV_NORM_CHUNK_ROWS = 256
-SV_REDUCE_MEAN, SV_REDUCE_FIRST = 0, 1
+SV_REDUCE_MEAN, SV_REDUCE_FIRST, SV_REDUCE_SUM = 0, 1, 2
 SV_TILE_ROWS = 128
 SV_ERR_UNSUPPORTED = -5
 SV_PN_MAX_LAYERS = 4
@@ -183,6 +183,9 @@ SIGNATURES = {
                                  _P, _P]),
     "sv_instance_norm_backward": (c_int, [_P, c_int64, c_int64, c_int, _P, c_int, _P, _P, _P, _P, c_int, _P, c_int64, _P,
                                           c_size_t, _P, c_int64, _P, _P, _P]),
+    "sv_sinusoidal": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, _P, c_int, _P, c_int64, _P]),
+    "sv_field_stage": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
+                               _P, c_int64, _P, c_int64, _P]),
 }
 
 _lib = None

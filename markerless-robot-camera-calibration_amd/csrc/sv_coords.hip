@@ -180,9 +180,9 @@ __global__ __launch_bounds__(256) void voxel_reduce_kernel(const float* __restri
   int c = (int)(t - v * C);
   int s = seg_start[v], e = seg_start[v + 1];
   float acc = feats[(int64_t)order[s] * C + c];
-  if (mode == SV_REDUCE_MEAN) {
+  if (mode != SV_REDUCE_FIRST) {
     for (int j = s + 1; j < e; ++j) acc += feats[(int64_t)order[j] * C + c];
-    acc = acc / (float)(e - s);
+    if (mode == SV_REDUCE_MEAN) acc = acc / (float)(e - s);
   }
   out[t] = acc;
 }
@@ -465,7 +465,7 @@ int sv_voxel_reduce(const float* feats, int C, const int32_t* order, const int32
                     float* out, sv_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SV_CHECK_ARG(C > 0 && V >= 0, "bad shape");
-  SV_CHECK_ARG(mode == SV_REDUCE_MEAN || mode == SV_REDUCE_FIRST, "bad mode");
+  SV_CHECK_ARG(mode == SV_REDUCE_MEAN || mode == SV_REDUCE_FIRST || mode == SV_REDUCE_SUM, "bad mode");
   if (V == 0) return SV_OK;
   SV_CHECK_ARG(feats && order && seg_start && out, "null pointer");
   int64_t total = V * C;

@@ -1,13 +1,15 @@
 """ResNetBase and the classification networks ResNet14 / 18 / 34 / 50 / 101; the U-Nets inherit `_make_layer` and
-`weight_initialization`.
+`weight_initialization`.  ResFieldNetBase and ResFieldNet14 / 18 / 34 / 50 / 101: the same trunk behind two small networks
+that run on the POINTS of a TensorField (sinusoidal layer, linear layer, per-voxel mean) before voxelisation.
 
-Mirror of the reference's model/backbone/resnet.py:34-162.  Same attribute names -> same state_dict keys.  The ResFieldNet
-classes there (:165-218) need MinkowskiSinusoidal, MinkowskiToSparseTensor and TensorField.cat_slice and are not rebuilt
-(DESIGN.md §9).
+Mirror of the reference's model/backbone/resnet.py:34-218.  Same attribute names -> same state_dict keys.  In eval() each
+field network is one sv_field_stage call.
 """
+import torch
 import torch.nn as nn
 
 from ... import MinkowskiEngine as ME
+from ... import nn as svnn
 from ..._lib import SV_ACT_GELU, SV_ACT_RELU
 
 
@@ -122,5 +124,76 @@ class ResNet50(ResNetBase):
 
 
 class ResNet101(ResNetBase):
+    BLOCK = ME.Bottleneck
+    LAYERS = (3, 4, 23, 3)
+
+
+class ResFieldNetBase(ResNetBase):
+    FUSE_FIELD = True  # eval(): each field network as ONE sv_field_stage call; False: module by module
+
+    def network_initialization(self, in_channels, out_channels, D):
+        # resnet.py:166-188: 3 -> 32 on the points, voxel mean; [32 voxel, 3 point] -> 64 on the points, voxel mean; the trunk
+        field_ch = 32
+        field_ch2 = 64
+        self.field_network = nn.Sequential(
+            ME.MinkowskiSinusoidal(in_channels, field_ch),
+            ME.MinkowskiBatchNorm(field_ch),
+            ME.MinkowskiReLU(inplace=True),
+            ME.MinkowskiLinear(field_ch, field_ch),
+            ME.MinkowskiBatchNorm(field_ch),
+            ME.MinkowskiReLU(inplace=True),
+            ME.MinkowskiToSparseTensor(),
+        )
+        self.field_network2 = nn.Sequential(
+            ME.MinkowskiSinusoidal(field_ch + in_channels, field_ch2),
+            ME.MinkowskiBatchNorm(field_ch2),
+            ME.MinkowskiReLU(inplace=True),
+            ME.MinkowskiLinear(field_ch2, field_ch2),
+            ME.MinkowskiBatchNorm(field_ch2),
+            ME.MinkowskiReLU(inplace=True),
+            ME.MinkowskiToSparseTensor(),
+        )
+        ResNetBase.network_initialization(self, field_ch2, out_channels, D)
+
+    def _run_field(self, seq, field, voxel=None):
+        """seq(field), or seq(voxel.cat_slice(field)): fused where seq is exactly the seven-module field network in eval(),
+        nothing carries a graph, the field averages and the kernel covers the widths; else module by module"""
+        fused = (self.FUSE_FIELD and svnn.is_field_stage(seq)
+                 and field.quantization_mode == ME.SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE
+                 and not (torch.is_grad_enabled() and (field.F.requires_grad or (voxel is not None and voxel.F.requires_grad))))
+        if fused:
+            out = svnn.field_stage(seq, field, voxel)
+            if out is not None:
+                return out
+        return seq(field if voxel is None else voxel.cat_slice(field))
+
+    def forward(self, x):
+        # resnet.py:190-193
+        otensor = self._run_field(self.field_network, x)
+        otensor2 = self._run_field(self.field_network2, x, otensor)
+        return ResNetBase.forward(self, otensor2)
+
+
+class ResFieldNet14(ResFieldNetBase):
+    BLOCK = ME.BasicBlock
+    LAYERS = (1, 1, 1, 1)
+
+
+class ResFieldNet18(ResFieldNetBase):
+    BLOCK = ME.BasicBlock
+    LAYERS = (2, 2, 2, 2)
+
+
+class ResFieldNet34(ResFieldNetBase):
+    BLOCK = ME.BasicBlock
+    LAYERS = (3, 4, 6, 3)
+
+
+class ResFieldNet50(ResFieldNetBase):
+    BLOCK = ME.Bottleneck
+    LAYERS = (3, 4, 6, 3)
+
+
+class ResFieldNet101(ResFieldNetBase):
     BLOCK = ME.Bottleneck
     LAYERS = (3, 4, 23, 3)

@@ -10,6 +10,9 @@ state_dict keys match ME 0.5.4 so utils/utils.py:87-126 checkpoint_restore-style
   MinkowskiBatchNorm: `bn.weight bn.bias bn.running_mean bn.running_var bn.num_batches_tracked`
   MinkowskiLinear: `linear.weight` [Cout, Cin], `linear.bias` [Cout]
   MinkowskiInstanceNorm: `weight` [1, C], `bias` [1, C] (from memory, unverified against ME)
+  MinkowskiSinusoidal: `kernel` [Cin, Cout], `bias` [1, Cout], `coef` [1, Cout] (from memory, unverified)
+Batch norm, the activations, MinkowskiLinear and MinkowskiSinusoidal take a TensorField as they take a SparseTensor: the same
+kernels on its features, the result a field on the same points (TensorField.new).
 Kernel-offset order inside `kernel` is this build's definition (include/sv_hip.h); `KERNEL_OFFSET_PERMUTATION` is the
 single hook for adapting a real ME checkpoint if its order turns out to differ.
 """
@@ -22,7 +25,7 @@ import torch.nn as nn
 
 from . import _lib, profiling
 from ._lib import SV_ACT_LEAKY_RELU, SV_ACT_NONE, SV_ACT_RELU, call, ptr, stream_ptr
-from .sparse import SparseTensor, SplitPlan, layer_maps
+from .sparse import SparseTensor, SplitPlan, TensorField, layer_maps
 
 # Adapting a checkpoint written by a MinkowskiEngine build whose kernel-offset numbering differs from this build's
 # (include/sv_hip.h: k = (dx+1) + 3 (dy+1) + 9 (dz+1), x fastest; k = dx + 2 dy + 4 dz for kernel_size 2):
@@ -602,6 +605,9 @@ class MinkowskiConvolutionTranspose(_ConvBase):
         super().__init__(in_channels, out_channels, kernel_size, stride, dilation, bias, dimension, transposed=True)
 
 
+_TENSORS = (SparseTensor, TensorField)  # what a pointwise layer maps to the same kind of tensor (x.F -> x.new)
+
+
 class MinkowskiBatchNorm(nn.Module):
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
         super().__init__()
@@ -635,8 +641,8 @@ class MinkowskiReLU(nn.Module):
 
     def forward(self, x):
         if self.training:
-            return x.new(torch.relu(x.F)) if isinstance(x, SparseTensor) else torch.relu(x)
-        if isinstance(x, SparseTensor):
+            return x.new(torch.relu(x.F)) if isinstance(x, _TENSORS) else torch.relu(x)
+        if isinstance(x, _TENSORS):
             return x.new(affine_act(x.F, act=SV_ACT_RELU))
         return affine_act(x, act=SV_ACT_RELU)
 
@@ -649,8 +655,8 @@ class MinkowskiLeakyReLU(nn.Module):
     def forward(self, x):
         if self.training:
             f = torch.nn.functional.leaky_relu
-            return (x.new(f(x.F, self.negative_slope)) if isinstance(x, SparseTensor) else f(x, self.negative_slope))
-        if isinstance(x, SparseTensor):
+            return (x.new(f(x.F, self.negative_slope)) if isinstance(x, _TENSORS) else f(x, self.negative_slope))
+        if isinstance(x, _TENSORS):
             return x.new(affine_act(x.F, act=SV_ACT_LEAKY_RELU, slope=self.negative_slope))
         return affine_act(x, act=SV_ACT_LEAKY_RELU, slope=self.negative_slope)
 
@@ -682,18 +688,123 @@ class MinkowskiLinear(_Bf16Weights, nn.Module):
         return self._packed_bf16(self.linear.weight, self.weight3())
 
     def forward_fused(self, x, act=SV_ACT_NONE, slope=0.01):
-        F = x.F if isinstance(x, SparseTensor) else x
+        F = x.F if isinstance(x, _TENSORS) else x
         if self.training:
             out = linear_train(self.linear, F, act, slope, layer=self)
-            return x.new(out) if isinstance(x, SparseTensor) else out
+            return x.new(out) if isinstance(x, _TENSORS) else out
         shift = self.linear.bias.detach() if self.linear.bias is not None else None
         wp = self._weight_bf16()
         bf16 = {} if wp is None else {"weight_bf16": wp}  # fp32 layers: the call conv_forward always got
         out = conv_forward(F, self.weight3(), None, F.shape[0], None, shift, None, act, slope, **bf16)
-        return x.new(out) if isinstance(x, SparseTensor) else out
+        return x.new(out) if isinstance(x, _TENSORS) else out
 
     def forward(self, x):
         return self.forward_fused(x)
+
+
+def sinusoidal(feats, kernel, bias, coef):
+    """coef * sin(feats @ kernel + bias) (sv_sinusoidal): fp32 fma chain over the input channels, the sine in float64"""
+    N, Cin = feats.shape
+    Cout = kernel.shape[1]
+    if feats.stride(1) != 1:
+        feats = feats.contiguous()
+    out = torch.empty((N, Cout), dtype=torch.float32, device=feats.device)
+    call("sv_sinusoidal", ptr(feats), c_int64(feats.stride(0) if N else Cin), c_int(Cin), c_int64(N), ptr(kernel), ptr(bias),
+         ptr(coef), c_int(Cout), ptr(out), c_int64(Cout), stream_ptr())
+    return out
+
+
+class MinkowskiSinusoidal(nn.Module):
+    """ME.MinkowskiSinusoidal: coef * sin(F @ kernel + bias) on a SparseTensor or a TensorField (restated from memory)."""
+
+    def __init__(self, in_channel, out_channel):
+        super().__init__()
+        self.in_channel, self.out_channel = in_channel, out_channel
+        self.kernel = nn.Parameter(torch.randn(in_channel, out_channel))
+        self.bias = nn.Parameter(torch.randn(1, out_channel))
+        self.coef = nn.Parameter(torch.randn(1, out_channel))
+
+    def packed(self):
+        """(kernel [Cin, Cout], bias [Cout], coef [Cout]) as the kernels read them: detached, contiguous"""
+        return self.kernel.detach().contiguous(), self.bias.detach().reshape(-1), self.coef.detach().reshape(-1)
+
+    def forward(self, x):
+        F = x.F
+        if self.training or (F.requires_grad and torch.is_grad_enabled()):
+            # torch.sin around the differentiable dense layer (sv_conv_fwd / sv_conv_wgrad: no GEMM with atomics)
+            if F.stride(1) != 1:
+                F = F.contiguous()
+            arg = sparse_conv(F, self.kernel.unsqueeze(0), self.bias, None, F.shape[0], lambda: None)
+            return x.new(self.coef * torch.sin(arg))
+        return x.new(sinusoidal(F, *self.packed()))
+
+    def extra_repr(self):
+        return f"in={self.in_channel}, out={self.out_channel}"
+
+
+class MinkowskiToSparseTensor(nn.Module):
+    """ME.MinkowskiToSparseTensor on a TensorField: field.sparse() - the per-voxel mean under the field's quantisation mode
+    (dense tensors, remove_zeros and coordinates= are not rebuilt)."""
+
+    def __init__(self, remove_zeros=False, coordinates=None):
+        super().__init__()
+        if remove_zeros or coordinates is not None:
+            raise NotImplementedError("MinkowskiToSparseTensor: only the TensorField form is built")
+
+    def forward(self, x):
+        if isinstance(x, TensorField):
+            return x.sparse()
+        if isinstance(x, SparseTensor):
+            return x
+        raise NotImplementedError("MinkowskiToSparseTensor takes a TensorField (dense tensors are not rebuilt)")
+
+
+FIELD_STAGE = (MinkowskiSinusoidal, MinkowskiBatchNorm, MinkowskiReLU, MinkowskiLinear, MinkowskiBatchNorm, MinkowskiReLU,
+               MinkowskiToSparseTensor)
+
+
+def is_field_stage(seq):
+    """exactly Sinusoidal -> BN -> ReLU -> Linear -> BN -> ReLU -> ToSparseTensor with matching widths, in eval()"""
+    mods = list(seq)
+    if len(mods) != len(FIELD_STAGE) or any(type(m) is not t for m, t in zip(mods, FIELD_STAGE)) or any(m.training for m in mods):
+        return False
+    C = mods[0].out_channel
+    return (mods[1].bn.num_features == C and mods[3].linear.in_features == C and mods[3].linear.out_features == C
+            and mods[4].bn.num_features == C and mods[3].compute_precision == "fp32")
+
+
+def field_stage(seq, field, voxel=None):
+    """One field network (is_field_stage) as ONE sv_field_stage call on the points of `field`, the input row of a point being
+    [voxel.F[row of its voxel], field.F] (voxel = None: the field alone) - what seq(voxel.cat_slice(field)) computes module
+    by module.  Returns the SparseTensor on the field's voxels, or None where the kernel does not cover the shape
+    (SV_ERR_UNSUPPORTED): the caller then runs the modules."""
+    sin, bn1, _, lin, bn2, _, _ = list(seq)
+    cm, inverse, order, seg_start = field.voxelisation(reuse=True)  # a field voxelised before goes on with that manager
+    V = cm.maps[1].V
+    F = field.F
+    G = voxel.F if voxel is not None else None
+    if G is not None and (voxel.coordinate_manager is not cm or voxel.tensor_stride != 1):
+        raise ValueError("the field was not voxelised into the voxel tensor's coordinate manager")
+    if G is not None and G.stride(1) != 1:
+        G = G.contiguous()
+    N, Cf = F.shape
+    Cg = G.shape[1] if G is not None else 0
+    if sin.in_channel != Cg + Cf:
+        raise ValueError(f"the field network takes {sin.in_channel} channels, the input rows have {Cg} + {Cf}")
+    C = sin.out_channel
+    kernel, bias, coef = sin.packed()
+    (scale1, shift1), (scale2, shift2) = bn1.folded(), bn2.folded()
+    lin_bias = lin.linear.bias.detach() if lin.linear.bias is not None else None
+    out = torch.empty((V, C), dtype=torch.float32, device=F.device)
+    rc = _lib.load().sv_field_stage(
+        ptr(F), c_int64(F.stride(0) if N else Cf), c_int(Cf), c_int64(N), ptr(G), c_int64(G.stride(0) if Cg and V else Cg),
+        c_int(Cg), ptr(inverse if Cg else None), ptr(kernel), ptr(bias), ptr(coef), ptr(scale1), ptr(shift1), ptr(lin.weight3()),
+        ptr(lin_bias), ptr(scale2), ptr(shift2), c_int(C), ptr(order), ptr(seg_start), c_int64(V), ptr(out), c_int64(C),
+        stream_ptr())
+    if rc == _lib.SV_ERR_UNSUPPORTED:
+        return None
+    _lib._check(rc, "sv_field_stage")
+    return SparseTensor(out, coordinate_manager=cm, tensor_stride=1, _internal=True)
 
 
 class MinkowskiGlobalMaxPooling(nn.Module):

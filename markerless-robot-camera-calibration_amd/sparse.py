@@ -1,7 +1,7 @@
 """Sparse-tensor runtime behind the MinkowskiEngine names the reference uses.
 
-  TensorField(features, coordinates, quantization_mode, minkowski_algorithm, device).sparse()
-  SparseTensor(features, coordinates=..., device=...)  / .F .C .slice(field) .decomposed_coordinates
+  TensorField(features, coordinates, quantization_mode, minkowski_algorithm, device).sparse() / .new(features)
+  SparseTensor(features, coordinates=..., device=...)  / .F .C .slice(field) .cat_slice(field) .decomposed_coordinates
   CoordinateManager: per-frame coordinate maps (stride 1,2,4,...), hash tables, kernel maps and conv plans,
   shared by every tensor derived from one input (what ME calls the coordinate manager).
 
@@ -584,8 +584,81 @@ def _voxel_reduce(feats, order, seg_start, V, mode):
     return out
 
 
+def _reduce_mode(quantization_mode):
+    mode = {SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE: _lib.SV_REDUCE_MEAN,
+            SparseTensorQuantizationMode.UNWEIGHTED_SUM: _lib.SV_REDUCE_SUM,
+            SparseTensorQuantizationMode.RANDOM_SUBSAMPLE: _lib.SV_REDUCE_FIRST}.get(quantization_mode)
+    if mode is None:
+        raise NotImplementedError(f"quantization_mode {quantization_mode}")
+    return mode
+
+
+def _slice_rows(F, inverse):
+    N, C = inverse.shape[0], F.shape[1]
+    if F.stride(1) != 1:
+        F = F.contiguous()
+    out = torch.empty((N, C), dtype=torch.float32, device=F.device)
+    call("sv_slice_rows", ptr(F), c_int64(F.stride(0)), c_int(C), ptr(inverse), c_int64(N), ptr(out), stream_ptr())
+    return out
+
+
+class VoxelReduceFunction(torch.autograd.Function):
+    """points -> voxels (sv_voxel_reduce, mean or sum) with its backward: the voxel gradient (divided by the voxel's count
+    for the mean) sliced back to the points - a gather (sv_slice_rows), the same bits on every run"""
+
+    @staticmethod
+    def forward(ctx, feats, inverse, order, seg_start, V, mode):
+        ctx.inverse, ctx.seg_start, ctx.mode = inverse, seg_start, mode
+        return _voxel_reduce(feats.contiguous(), order, seg_start, V, mode)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.mode == _lib.SV_REDUCE_MEAN:
+            dy = dy / (ctx.seg_start[1:] - ctx.seg_start[:-1]).to(torch.float32).unsqueeze(1)
+        return _slice_rows(dy, ctx.inverse), None, None, None, None, None
+
+
+class SliceFunction(torch.autograd.Function):
+    """voxels -> points (sv_slice_rows); backward: the point gradients summed per voxel in ascending point index
+    (sv_voxel_reduce, SV_REDUCE_SUM) - no index_add_, the same bits on every run"""
+
+    @staticmethod
+    def forward(ctx, F, inverse, order, seg_start):
+        ctx.order, ctx.seg_start, ctx.V = order, seg_start, F.shape[0]
+        return _slice_rows(F, inverse)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _voxel_reduce(dy.contiguous(), ctx.order, ctx.seg_start, ctx.V, _lib.SV_REDUCE_SUM), None, None, None
+
+
+def _has_graph(t):
+    return t.requires_grad and torch.is_grad_enabled()
+
+
+class _Voxelisation:
+    """what sv_voxelize made of a field's coordinates; ONE object shared by a field and every field derived from it
+    with .new(), as ME shares a field's coordinate map through the coordinate manager"""
+
+    __slots__ = ("coordinate_manager", "inverse_mapping", "order", "seg_start", "shared")
+
+    def __init__(self, coordinate_manager=None, inverse_mapping=None):
+        self.coordinate_manager, self.inverse_mapping = coordinate_manager, inverse_mapping
+        self.order = self.seg_start = None
+        self.shared = False
+
+
+def _vox_attr(name):
+    return property(lambda self: getattr(self._vox, name), lambda self, value: setattr(self._vox, name, value))
+
+
 class TensorField:
     """ME.TensorField: per-point features + continuous (pre-scaled) coordinates [N, 1+3] = (batch, x, y, z)."""
+
+    coordinate_manager = _vox_attr("coordinate_manager")
+    inverse_mapping = _vox_attr("inverse_mapping")
+    _order = _vox_attr("order")
+    _seg_start = _vox_attr("seg_start")
 
     def __init__(self, features, coordinates=None, quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE,
                  minkowski_algorithm=MinkowskiAlgorithm.DEFAULT, device=None, coordinate_manager=None,
@@ -595,16 +668,13 @@ class TensorField:
         self._F = features.to(device=device, dtype=torch.float32).contiguous()
         self.quantization_mode = quantization_mode
         self.minkowski_algorithm = minkowski_algorithm
-        self.coordinate_manager = coordinate_manager
-        self.inverse_mapping = inverse_mapping
+        self._vox = _Voxelisation(coordinate_manager, inverse_mapping)
         if coordinates is not None:
             if coordinates.shape[0] != features.shape[0] or coordinates.shape[1] != 4:
                 raise ValueError("coordinates must be [N, 4] = (batch, x, y, z) with one row per feature row")
             self._C = coordinates.to(device=device, dtype=torch.float32).contiguous()
         else:
             self._C = None
-        self._order = None
-        self._seg_start = None
 
     @property
     def F(self):
@@ -621,29 +691,54 @@ class TensorField:
     def __len__(self):
         return self._F.shape[0]
 
+    def new(self, features):
+        """A field with other features on the same points (what a layer applied to a field returns).  It shares this
+        field's voxelisation - made before or after the call, by either field: sparse() on any of them runs sv_voxelize
+        at most once, and their tensors live on one CoordinateManager.  A field without coordinates (the result of
+        slice) hands on its manager and inverse mapping."""
+        if features.shape[0] != self._F.shape[0]:
+            raise ValueError("a field's features have one row per point")
+        f = TensorField.__new__(TensorField)
+        f.device = self.device
+        f._F = features.to(device=self.device, dtype=torch.float32).contiguous()  # a graph stays attached
+        f.quantization_mode, f.minkowski_algorithm = self.quantization_mode, self.minkowski_algorithm
+        f._C = self._C
+        f._vox = self._vox
+        self._vox.shared = True
+        return f
+
+    def voxelisation(self, pyramid_levels=None, reuse=False):
+        """(CoordinateManager, inverse, order, seg_start) of this field's points: sv_voxelize on a field of its own (every
+        call, as sparse() always did), once for fields that share their voxelisation through new().  reuse: take the
+        existing one of a field of its own as well (what goes on with tensors that came from it)."""
+        if self._C is None:
+            raise ValueError("TensorField has no coordinates")
+        vox = self._vox
+        if not ((vox.shared or reuse) and vox.order is not None):
+            if pyramid_levels is not None and self._C.shape[0] > 0:
+                cm, inverse, order, seg_start = _voxelize_frame(self._C, self.device, False, pyramid_levels)
+            else:
+                cmap, inverse, order, seg_start = _voxelize(self._C, self.device, coords_are_int=False)
+                cm = CoordinateManager(self.device)
+                cm.maps[1] = cmap
+            vox.coordinate_manager, vox.inverse_mapping, vox.order, vox.seg_start = cm, inverse, order, seg_start
+        return vox.coordinate_manager, vox.inverse_mapping, vox.order, vox.seg_start
+
     def sparse(self, pyramid_levels=None):
         """Voxelise: floor the coordinates, unique voxels in canonical order, per-voxel feature mean.
         pyramid_levels = n (this build's extension): the stride-2 maps of the next n pyramid levels are built in the same
         host call (sv_frame_maps) - what a U-Net's strided convolutions would otherwise ask for one by one, each with
-        its own size read-back."""
+        its own size read-back.  A field that shares its voxelisation (new) and finds it made takes it as it is: pyramid_levels
+        then builds nothing ahead, and the coarser maps are made on demand (stride_map), with the same rows."""
         if self._C is None:
             raise ValueError("TensorField has no coordinates")
-        if self.quantization_mode not in (SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE,
-                                          SparseTensorQuantizationMode.RANDOM_SUBSAMPLE):
-            raise NotImplementedError(f"quantization_mode {self.quantization_mode}")
-        if pyramid_levels is not None and self._C.shape[0] > 0:
-            cm, inverse, order, seg_start = _voxelize_frame(self._C, self.device, False, pyramid_levels)
-            cmap = cm.maps[1]
+        mode = _reduce_mode(self.quantization_mode)
+        cm, inverse, order, seg_start = self.voxelisation(pyramid_levels)
+        V = cm.maps[1].V
+        if _has_graph(self._F) and mode != _lib.SV_REDUCE_FIRST:  # differentiable: the mean / sum of features with a graph
+            feats = VoxelReduceFunction.apply(self._F, inverse, order, seg_start, V, mode)
         else:
-            cmap, inverse, order, seg_start = _voxelize(self._C, self.device, coords_are_int=False)
-            cm = CoordinateManager(self.device)
-            cm.maps[1] = cmap
-        self.coordinate_manager = cm
-        self.inverse_mapping = inverse
-        self._order, self._seg_start = order, seg_start
-        mode = (_lib.SV_REDUCE_MEAN if self.quantization_mode == SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE
-                else _lib.SV_REDUCE_FIRST)
-        feats = _voxel_reduce(self._F, order, seg_start, cmap.V, mode)
+            feats = _voxel_reduce(self._F, order, seg_start, V, mode)
         return SparseTensor(feats, coordinate_manager=cm, tensor_stride=1, _internal=True)
 
 
@@ -680,8 +775,8 @@ class SparseTensor:
         cmap, inverse, order, seg_start = _voxelize(coords, device, coords_are_int=True)
         cm = CoordinateManager(device)
         cm.maps[1] = cmap
-        mode = (_lib.SV_REDUCE_MEAN if quantization_mode == SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE
-                else _lib.SV_REDUCE_FIRST)
+        mode = {SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE: _lib.SV_REDUCE_MEAN,
+                SparseTensorQuantizationMode.UNWEIGHTED_SUM: _lib.SV_REDUCE_SUM}.get(quantization_mode, _lib.SV_REDUCE_FIRST)
         self._F = _voxel_reduce(feats, order, seg_start, cmap.V, mode)
         if requires_grad:  # ME: the voxel features are a leaf of the graph; .F.grad holds dX after backward()
             self._F.requires_grad_(True)
@@ -757,12 +852,24 @@ class SparseTensor:
         inv = field.inverse_mapping
         if inv is None or field.coordinate_manager is not self.coordinate_manager:
             raise ValueError("the field was not voxelised into this tensor's coordinate manager")
-        N, C = inv.shape[0], self._F.shape[1]
-        out = torch.empty((N, C), dtype=torch.float32, device=self._F.device)
-        call("sv_slice_rows", ptr(self._F), c_int64(self._F.stride(0)), c_int(C), ptr(inv), c_int64(N), ptr(out),
-             stream_ptr())
-        return TensorField(out, coordinates=None, device=self._F.device, coordinate_manager=self.coordinate_manager,
-                           inverse_mapping=inv)
+        return TensorField(self._slice_features(field), coordinates=None, device=self._F.device,
+                           coordinate_manager=self.coordinate_manager, inverse_mapping=inv)
+
+    def _slice_features(self, field):
+        """this tensor's rows at field.inverse_mapping; differentiable when the features carry a graph and the field holds
+        its voxelisation's point order (a field without coordinates, the result of slice, does not: a plain gather, as before)"""
+        if _has_graph(self._F) and field._order is not None:
+            return SliceFunction.apply(self._F, field.inverse_mapping, field._order, field._seg_start)
+        return _slice_rows(self._F, field.inverse_mapping)
+
+    def cat_slice(self, field):
+        """ME.SparseTensor.cat_slice: a field on `field`'s points whose rows are [this tensor's row of the point's voxel,
+        the field's own features] - voxel features first (reference model/backbone/resnet.py:192)."""
+        if self.tensor_stride != 1:
+            raise ValueError("cat_slice needs a tensor at tensor stride 1")
+        if field.inverse_mapping is None or field.coordinate_manager is not self.coordinate_manager:
+            raise ValueError("the field was not voxelised into this tensor's coordinate manager")
+        return field.new(torch.cat([self._slice_features(field), field.F], dim=1))
 
     def slice_argmax(self, field, with_conf=True):
         """Fused slice + utils/output.py:67-73: per-point label (first row maximum, a row's first NaN beating any number, as

@@ -1221,6 +1221,74 @@ int sv_field_stage(const float* F, int64_t f_ld, int Cf, int64_t N, const float*
                    const float* W, const float* lin_bias, const float* scale2, const float* shift2, int C,
                    const int32_t* order, const int32_t* seg_start, int64_t V, float* out, int64_t out_ld, sv_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N10  metric-learning criterion (replaces the criterion of train_feature-extractor.py:65-81 and
+ *      train_feature-extractor-voxel.py, built by model/featurenet.py:30-34: miners.MultiSimilarityMiner() on
+ *      out.features, truncation of the mined pairs to batch_size * max_pair, losses.TripletMarginLoss() on what is left;
+ *      both classes are pytorch_metric_learning's, with their defaults).  Additions of ABI 4.
+ *      The semantics below are that library's published algorithm restated from memory; the library is not available to
+ *      this project, so parity with it is by construction and unverified.
+ *
+ * Common arguments: x float32[B][ld], columns 0 .. E-1 are the embedding (ld >= E >= 1; the padding is never read),
+ *   B in [1, SV_MAX_BATCH].  All arithmetic is float64 on the float32 inputs:
+ *     u_i = x_i / max(||x_i||_2, 1e-12)         (F.normalize)
+ *     S[i][j] = u_i . u_j                        (CosineSimilarity)
+ *     D[i][j] = ||u_i - u_j||_2                  (LpDistance(normalize_embeddings=True, p=2, power=1)), from the differences
+ *   Every entry validates on the host before any HIP call (null pointer, B outside [1, SV_MAX_BATCH], E < 1, ld < E, a
+ *   negative capacity, a cap below -1, a workspace below sv_metric_workspace_bytes(B, E): SV_ERR_INVALID), launches on the
+ *   stream and never waits or reads back; the same arguments give the same bits; no floating-point atomics (integer
+ *   atomics count the pairs of a given tuple).  Nothing is sized by the number of pairs or triplets: the workspace holds
+ *   [B][B] matrices and two [B][E] float64 copies of the embeddings.
+ *
+ * sv_ms_mine - MultiSimilarityMiner(epsilon) with CosineSimilarity, labels int64[B] (any values):
+ *   for anchor i the positives are j != i with labels[j] == labels[i], the negatives j with labels[j] != labels[i];
+ *   maxneg_i = the largest S[i][j] over its negatives (-inf without one), minpos_i = the smallest over its positives
+ *   (+inf without one).  Hard positive: S[i][j] - epsilon < maxneg_i.  Hard negative: S[i][j] + epsilon > minpos_i.
+ *   A batch without any positive pair, or without any negative pair, therefore has no hard pair at all (the library's
+ *   early return).
+ *   Order of each list: anchor ascending; within an anchor S ascending; equal S by column ascending (the order of
+ *   torch.sort followed by torch.where; the tie rule is this library's, torch leaves it open).
+ *   max_pos / max_neg (-1: none): only the first max_* pairs in that order are kept - the trainer's truncation.
+ *   a1, p int64[cap_pos] and a2, n int64[cap_neg]: the kept pairs; entries at and after the kept count are not written.
+ *   A capacity below the kept count truncates in the same way (cap_* = 0 with NULL lists just counts).
+ *   counts int64[4] = (kept positives, kept negatives, hard positives, hard negatives), on the device.
+ *   A row of x with a NaN or an infinity joins no pair, as anchor or as partner, and adds one to n_nonfinite[0] (int32);
+ *   the other rows mine as if it were absent.  No parity with the library is claimed there.
+ *
+ * sv_triplet_margin - TripletMarginLoss(margin) with the library's defaults (no swap, no smooth loss, all triplets per
+ *   anchor, AvgNonZeroReducer) on a tuple of pair lists in any order:
+ *   a1, p int64[cap_pos], a2, n int64[cap_neg]; the lengths are read from the device: counts[0] positives and counts[1]
+ *   negatives, each clamped to [0, cap_*] (counts is int64[>= 2]: sv_ms_mine's output fits).
+ *   Triplets: every (a1[s], p[s], n[t]) with a1[s] == a2[t]; a pair listed twice counts twice.
+ *   Triplet loss: max(D[a][p] - D[a][n] + margin, 0).
+ *   sums float64[2] = (sum over the triplets, number of triplets with loss > 0); the caller forms sums[0] / sums[1], or 0
+ *   when sums[1] == 0.  The sum's order depends on (B, E) and on the multiset of pairs only, not on their order in the
+ *   lists: anchors ascending, negatives by column, positives by column.
+ *   grad float32[B][E] dense (may be NULL): the UNSCALED d sums[0] / d x through the distance and the normalisation, in
+ *   float64 until the one rounding; the subgradient is 0 where D = 0 (torch.cdist's) and at the hinge; a row in no
+ *   violating triplet is exactly 0.  The caller multiplies by 1 / sums[1] and the incoming gradient.
+ *   n_triplets int64[1] = the number of triplets.  n_invalid int32[1] = pairs with an index outside [0, B): skipped.
+ *   A non-finite embedding that takes part in a triplet makes sums[0] NaN.
+ *
+ * sv_mined_triplet_step - sv_ms_mine(max_pos, max_neg) followed by sv_triplet_margin on the kept pairs, in one entry that
+ *   computes S and D together and never writes the lists: counts, n_nonfinite, sums, grad and n_triplets are bit-equal to
+ *   the two calls composed (with capacities that hold the kept pairs).  The trainer's randperm after the truncation only
+ *   reorders the kept pairs, which the loss does not see.
+ *
+ * workspace: sv_metric_workspace_bytes(B, E) for all three.
+ * ------------------------------------------------------------------------------------------- */
+size_t sv_metric_workspace_bytes(int B, int E);
+int sv_ms_mine(const float* x, int64_t ld, int B, int E, const int64_t* labels, double epsilon, int64_t max_pos, int64_t max_neg,
+               void* workspace, size_t workspace_bytes, int64_t* a1, int64_t* p, int64_t cap_pos, int64_t* a2, int64_t* n,
+               int64_t cap_neg, int64_t* counts, int32_t* n_nonfinite, sv_stream_t stream);
+int sv_triplet_margin(const float* x, int64_t ld, int B, int E, const int64_t* a1, const int64_t* p, int64_t cap_pos,
+                      const int64_t* a2, const int64_t* n, int64_t cap_neg, const int64_t* counts, double margin,
+                      void* workspace, size_t workspace_bytes, double* sums, float* grad, int64_t* n_triplets,
+                      int32_t* n_invalid, sv_stream_t stream);
+int sv_mined_triplet_step(const float* x, int64_t ld, int B, int E, const int64_t* labels, double epsilon, double margin,
+                          int64_t max_pos, int64_t max_neg, void* workspace, size_t workspace_bytes, double* sums, float* grad,
+                          int64_t* counts, int64_t* n_triplets, int32_t* n_nonfinite, sv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,13 @@ SIGNATURES = {
     "sv_sinusoidal": (c_int, [_P, c_int64, c_int, c_int64, _P, _P, _P, c_int, _P, c_int64, _P]),
     "sv_field_stage": (c_int, [_P, c_int64, c_int, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
                                _P, c_int64, _P, c_int64, _P]),
+    "sv_metric_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "sv_ms_mine": (c_int, [_P, c_int64, c_int, c_int, _P, c_double, c_int64, c_int64, _P, c_size_t, _P, _P, c_int64, _P, _P,
+                           c_int64, _P, _P, _P]),
+    "sv_triplet_margin": (c_int, [_P, c_int64, c_int, c_int, _P, _P, c_int64, _P, _P, c_int64, _P, c_double, _P, c_size_t, _P, _P,
+                                  _P, _P, _P]),
+    "sv_mined_triplet_step": (c_int, [_P, c_int64, c_int, c_int, _P, c_double, c_double, c_int64, c_int64, _P, c_size_t, _P, _P,
+                                      _P, _P, _P, _P]),
 }
 
 _lib = None

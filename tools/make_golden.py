@@ -811,6 +811,49 @@ def gen_rgbd(rng):
     return data
 
 
+def gen_pointnet_kp(rng):
+    """model/pointnet.py:8-36 PointNet(in_channel=6, out_channel=7, embedding_channel=64) (the regressor of
+    train_kp_to_pose.py:286-291 with a narrow embedding, so that the fixture stays small), eval, CPU float32: a seeded
+    state_dict with randomised BatchNorm statistics (stored under w_<key>, the ordered key list as the UTF-8 bytes of its
+    newline join), inputs [B, 6, 6] at B = 1 and B = 3 and the outputs.  The reference's squeeze() drops the batch dimension
+    of a single sample and BatchNorm1d then refuses the 1-D tensor: where the reference raises, raises<i> = 1 is stored in
+    place of an output."""
+    from model.pointnet import PointNet as RefPointNet
+
+    torch.manual_seed(4100)
+    net = RefPointNet(in_channel=6, out_channel=7, embedding_channel=64)
+    sd = net.state_dict()
+    vals = {}
+    for k in sd:
+        shape = tuple(sd[k].shape)
+        if k.endswith("num_batches_tracked"):
+            continue
+        if k.endswith("running_var"):
+            vals[k] = rng.uniform(0.5, 1.5, shape).astype(np.float32)
+        elif k.endswith("running_mean"):
+            vals[k] = (rng.standard_normal(shape) * 0.1).astype(np.float32)
+        elif k.startswith("bn"):
+            vals[k] = (rng.uniform(0.75, 1.25, shape) if k.endswith("weight") else rng.standard_normal(shape) * 0.1).astype(np.float32)
+        else:
+            vals[k] = sd[k].numpy().astype(np.float32)  # torch's seeded initialisation
+    net.load_state_dict({k: torch.from_numpy(vals[k]) if k in vals else sd[k] for k in sd})
+    net.eval()
+    out = {"w_" + k: v for k, v in vals.items()}
+    out["state_dict_keys"] = np.frombuffer("\n".join(sd.keys()).encode(), np.uint8)
+    out["embedding_channel"] = np.int64(64)
+    for i, B in enumerate((1, 3)):
+        x = rng.uniform(-0.2, 0.2, size=(B, 6, 6)).astype(np.float32)
+        out[f"x{i}"] = x
+        try:
+            with torch.no_grad():
+                out[f"out{i}"] = net(torch.from_numpy(x)).numpy().astype(np.float32)
+            out[f"raises{i}"] = np.int64(0)
+        except ValueError as e:
+            print(f"pointnet_kp: the reference raises at B = {B}: {e}")
+            out[f"raises{i}"] = np.int64(1)
+    return out
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     for name, fn, seed in [("kabsch", gen_kabsch, 100), ("quat_avg", gen_quat_avg, 101), ("add", gen_add, 102),
@@ -819,7 +862,7 @@ def main():
                            ("calib_chain", gen_calib_chain, 107), ("output_ops", gen_output_ops, 108),
                            ("pointnet2_ssg", gen_pointnet2, 109), ("pointnet2_msg", gen_pointnet2_msg, 110),
                            ("pose_losses", gen_pose_losses, 111), ("augmentation", gen_augmentation, 112),
-                           ("labels", gen_labels, 113), ("rgbd_ycb", gen_rgbd, 114)]:
+                           ("labels", gen_labels, 113), ("rgbd_ycb", gen_rgbd, 114), ("pointnet_kp", gen_pointnet_kp, 115)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:  # `make_golden.py NAME ...`: only those fixtures
             continue
         data = fn(np.random.default_rng(seed))
